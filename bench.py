@@ -30,7 +30,15 @@ the data path; a barrier + max-over-ranks bracket the timed region.
                           of the P shards of a block are the unsharded run's
                           (the host merges disjoint pattern_id keys)
 
-Besides `value` the line carries an end-to-end leg over the same batch (host
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what `value` needs
+and no more: it builds and uploads the batch, scans and reduces it once
+(untimed: the lists and buffers reach their size), warms up, times the K steps
+and prints the line (metric, value, unit, ms_per_step, dtype, config, rates).
+`--dump-outputs DIR` also writes what the last timed step computed, as numpy
+arrays a second build's run with the same arguments can be compared with
+(dump_outputs).  Everything else is behind `--full`:
+
+With `--full` the line also carries an end-to-end leg over the same batch (host
 prep + upload + scan + device key reduction + device per-sample encoding + the
 VCF rows as BGZF blocks made on the GPU), the roofline of the dominant kernel
 (HIP events around its launches on the ctx stream; traffic, the rocprofv3 MFMA
@@ -61,6 +69,8 @@ MFMA_F6_PEAK_TOPS = 10000.0
 # exact rescoring of the rare candidate windows excluded
 MFMA_OPS_PER_CELL = 8
 CPU_THREADS_MAX = 16        # the GPU box's CPU share for one GPU (os.cpu_count() shows the whole host)
+DUMP_BYTES_MAX = 48 << 20   # --dump-outputs: the sampled keys' count vectors (a dump stays under 64 MB)
+DUMP_REGIONS_MAX = 64       # --dump-outputs: regions whose keys are written in full
 
 WORKLOADS = {  # samples, regions per GPU, pwms, length config, indel %, seed
     "C2": (1000, 1000, 10, 2, 0, 2),
@@ -86,9 +96,14 @@ def parse():
     ap.add_argument("--indel-pct", type=int, default=None)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--threshold", type=float, default=1e-4)
-    ap.add_argument("--cpu-seconds", type=float, default=6.0, help="budget of each CPU baseline leg")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end leg (profiling passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the end-to-end leg, the per-kernel device times and rooflines, "
+                         "the dense download and the CPU baseline (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=6.0, help="--full: budget of each CPU baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the end-to-end leg (profiling passes)")
     ap.add_argument("--host-build", action="store_true",
                     help="reduce haplotypes to distinct ones on the host only (no device grouping)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -308,6 +323,60 @@ def launch_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
+def dump_outputs(T, sc, batch, directory, rank, threads):
+    """--dump-outputs: the last step's result as a caller of tfbs_step reads it --
+    tfbs_batch_reduce (after a step it only downloads), then the key functions
+    (count_matches_by_sample, main.rs:500-534) -- as DIR/<name>.npy (rank r > 0:
+    <name>.rank<r>.npy), float64 unless noted:
+      region_num_keys      [regions]     keys of every region
+      region_key_digests   [regions, 2]  every region's canonical key digest
+                                         (tfbs_batch_region_digests: all its keys' per-sample
+                                         vectors), high and low 32 bits
+      sample_key_ids       [K, 5]        (region, bed, start, end, pattern_id) of every key of a
+                                         fixed sample of regions (a seeded shuffle, at most
+                                         DUMP_REGIONS_MAX regions and DUMP_BYTES_MAX bytes of counts)
+      sample_key_counts    [K, 2, samples] float32: those keys' per-sample L and R counts
+    The generator, the seeds and the sample are fixed, so the same arguments give the
+    same arrays from run to run and from build to build."""
+    import random
+
+    import numpy as np
+
+    L = T.lib()
+    T.check(L.tfbs_batch_reduce(sc.h, batch.h))
+    n = batch.num_regions
+    num_keys = np.zeros(n, dtype=np.float64)
+    k = ctypes.c_size_t()
+    for r in range(n):
+        T.check(L.tfbs_batch_region_num_keys(batch.h, r, ctypes.byref(k)))
+        num_keys[r] = k.value
+    dk, _, _ = batch.region_digests(0, n, threads=threads, rows=False)
+    digests = np.stack([(dk >> np.uint64(32)).astype(np.float64),
+                        (dk & np.uint64(0xffffffff)).astype(np.float64)], axis=1)
+    order = list(range(n))
+    random.Random(0).shuffle(order)
+    per_key = 2 * batch.n_samples * 4
+    budget = DUMP_BYTES_MAX
+    ids, counts = [], []
+    for r in order[:DUMP_REGIONS_MAX]:
+        if num_keys[r] * per_key > budget:  # (the next regions of the shuffle may still fit)
+            continue
+        budget -= int(num_keys[r]) * per_key
+        for (bed, (s, e), pid), (left, right) in batch.keys_np(r).items():
+            ids.append((r, batch.beds.index(bed), s, e, pid))
+            counts.append(np.stack([left, right]).astype(np.float32))
+    arrays = {
+        "region_num_keys": num_keys,
+        "region_key_digests": digests,
+        "sample_key_ids": np.asarray(ids, dtype=np.float64).reshape(len(ids), 5),
+        "sample_key_counts": (np.stack(counts) if counts else
+                              np.zeros((0, 2, batch.n_samples), dtype=np.float32)),
+    }
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + (".rank%d" % rank if rank else "") + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -345,7 +414,9 @@ def main():
     sc = T.Scanner(ps, device=local)
     L = T.lib()
 
-    # ---- end-to-end leg, once: host prep, upload, scan, device key reduction, rows
+    # ---- setup, and with --full the end-to-end leg, once: host prep, upload, scan, device
+    # key reduction (a plain run stops here: the scan's lists and the assembly's buffers
+    # have their size before the first step), rows
     t_prep = time.perf_counter()
     batch = shard_batch(T, ps, args, rank, world, window_lmax=ps_all.max_length if parts > 1 else None,
                         build_device=None if args.host_build else local)
@@ -362,13 +433,14 @@ def main():
     T.check(L.tfbs_scan(sc.h, batch.h))
     T.check(L.tfbs_ctx_sync(sc.h))
     t_scan1 = time.perf_counter() - t_scan1
+    mfma_ms_setup = L.tfbs_ctx_last_mfma_ms(sc.h)  # (-1: the matrix-core kernel did not run; graph steps carry no events)
     t_red = time.perf_counter()
     T.check(L.tfbs_batch_reduce(sc.h, batch.h))
     t_red = time.perf_counter() - t_red
     n_rows = n_row_bytes = n_bgzf = 0
     t_rows = t_enc = 0.0
     host_bgzf = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         # device per-sample encoding, then the rows as BGZF blocks made on the device
         # (tfbs_batch_rows_bgzf: heads on the host, genotype text + deflate + CRC32 on the
         # GPU), 512 regions at a time (the run flow's batch); the blocks reach host memory
@@ -440,29 +512,34 @@ def main():
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier()
-    # the steps' device times (HIP events), read after further steps outside the timed
-    # loop: reading them syncs on each step's events, which is not part of a step
+    if args.dump_outputs:  # the last timed step's result, before anything else runs on the batch
+        dump_outputs(T, sc, batch, args.dump_outputs, rank, threads)
     kernel_ms, mfma_ms, asm_ms = [], [], []
-    for _ in range(min(args.steps, 10)):
-        step_plain()  # (graph steps carry no timing events)
-        kernel_ms.append(L.tfbs_ctx_last_scan_ms(sc.h))  # the scan's launches (HIP events)
-        mfma_ms.append(L.tfbs_ctx_last_mfma_ms(sc.h))   # the matrix-core kernel alone (-1: none ran)
-        asm_ms.append(L.tfbs_ctx_last_assemble_ms(sc.h))  # the assembly's launches
-    T.check(L.tfbs_ctx_sync(sc.h))
-    # the last step's list counters (device atomics, one per wave): candidates, the part
-    # of them in the waves' global lists, hit-list pairs, spill records, overflow
-    lc = (ctypes.c_uint64 * 5)()
-    T.check(L.tfbs_ctx_scan_counters(sc.h, lc))
-    list_counters = {"candidates": lc[2], "candidates_global": lc[3], "hit_pairs": lc[4], "spill_records": lc[0],
-                     "candidates_overflow": lc[1],
-                     # bytes the scan writes to its lists: 8 per global candidate and per hit pair,
-                     # 12 per spill / overflow record, 4 per wave's hit count
-                     "list_bytes": 8 * (lc[3] + lc[4]) + 12 * (lc[0] + lc[1])}
+    if args.full:
+        # the steps' device times (HIP events), read after further steps outside the timed
+        # loop: reading them syncs on each step's events, which is not part of a step
+        for _ in range(min(args.steps, 10)):
+            step_plain()  # (graph steps carry no timing events)
+            kernel_ms.append(L.tfbs_ctx_last_scan_ms(sc.h))  # the scan's launches (HIP events)
+            mfma_ms.append(L.tfbs_ctx_last_mfma_ms(sc.h))   # the matrix-core kernel alone (-1: none ran)
+            asm_ms.append(L.tfbs_ctx_last_assemble_ms(sc.h))  # the assembly's launches
+        T.check(L.tfbs_ctx_sync(sc.h))
+        # the last step's list counters (per-wave stores summed on the host): candidates, the
+        # part of them in the waves' global lists, hit-list pairs, spill records, overflow
+        lc = (ctypes.c_uint64 * 5)()
+        T.check(L.tfbs_ctx_scan_counters(sc.h, lc))
+        list_counters = {"candidates": lc[2], "candidates_global": lc[3], "hit_pairs": lc[4],
+                         "spill_records": lc[0], "candidates_overflow": lc[1],
+                         # bytes the scan writes to its lists: 8 per global candidate and per hit pair,
+                         # 12 per spill / overflow record, 4 per wave's hit count
+                         "list_bytes": 8 * (lc[3] + lc[4]) + 12 * (lc[0] + lc[1])}
 
-    # the dense download, for reference (the run flow uses the key reduction)
-    t_dense = time.perf_counter()
-    T.check(L.tfbs_batch_download(sc.h, batch.h))
-    t_dense = time.perf_counter() - t_dense
+        # the dense download, for reference (the run flow uses the key reduction)
+        t_dense = time.perf_counter()
+        T.check(L.tfbs_batch_download(sc.h, batch.h))
+        t_dense = time.perf_counter() - t_dense
+    else:  # which kernels scored the strands: the matrix-core kernel's time in the setup's scan
+        mfma_ms.append(mfma_ms_setup)
 
     e2e_s = prep_wall + t_up + t_scan1 + t_red + t_enc + t_rows
     if host_bgzf:
@@ -481,10 +558,54 @@ def main():
     if rank == 0:
         steps = args.steps
         value = tot_windows * steps / elapsed
-        kms = sum(kernel_ms) / len(kernel_ms)
         mms = sum(mfma_ms) / len(mfma_ms)
-        ams = sum(asm_ms) / len(asm_ms)
         path = "mfma" if mms > 0 else "lut"
+        out = {
+            "metric": "haplotype-windows scored/sec",
+            "value": value,
+            "unit": "windows/s",
+            "n_gpus": world,
+            "steps": steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed * 1e3 / steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "fp4xfp6->f32 bound + int32 exact" if path == "mfma" else "int32",
+            "data": "synthetic (SURVEY.md 8d generator; no HOCOMOCO/BCF download possible)",
+            "config": {
+                "workload": args.workload + ("-custom" if args.custom else ""),
+                "samples": args.samples, "haplotypes": 2 * args.samples, "regions_per_gpu": args.regions,
+                "regions_per_rank_batch": count,
+                "region_bp": 201, "pwms": args.pwms, "patterns": len(ps), "threshold": args.threshold,
+                "indel_pct": args.indel_pct, "seed": args.seed,
+                "distinct_haplotypes_per_gpu": batch.num_haplotypes,
+                "windows_per_step": int(tot_windows),
+                "parallelism": ("region shard x%d" % world if parts == 1 else
+                                "region x PWM shard: %d region blocks x %d pattern shards" % (world // parts, parts)),
+                "scan_path": path,
+                "scanned_windows_per_step": int(tot_scan),
+                "window_list_entries": [int(wl_entries[0]), int(wl_entries[1])],
+            },
+            "value_note": "windows of every distinct haplotype resolved per second, scan AND key assembly in "
+                          "the timed step (the reference scores each window and counts its hits per key, "
+                          "main.rs:94-154, 500-534); a haplotype's windows whose bases and positions equal the "
+                          "region's reference window take the reference window's hits in the assembly (reference-"
+                          "window reuse, exact; TFBS_DEDUP=0 scans them all); scanned_windows_per_s counts the "
+                          "windows the kernels read",
+            "step": "tfbs_step = tfbs_scan + tfbs_batch_assemble + tfbs_batch_assemble_wait (host sync and "
+                    "list check every step; from the third step alike the launches replay as one hipGraph): "
+                    "scan kernels, overflow rescoring, spill bucketing, key assembly + classification + "
+                    "varying-count compaction of every region of the batch",
+            "ranks": {"world_size": world, "backend": args.dist_backend if dist is not None else None,
+                      "ms_per_step": per_rank_ms},
+            "scanned_windows_per_s": tot_scan * steps / elapsed,
+            "scan_regions_per_s": tot_regions * steps / elapsed,
+            "effective_windows_per_s": tot_eff * steps / elapsed,
+        }
+    if rank == 0 and args.full:  # the device times, the rooflines, the end-to-end leg, the CPU baseline
+        kms = sum(kernel_ms) / len(kernel_ms)
+        ams = sum(asm_ms) / len(asm_ms)
         prof, traffic_src = pmc_profile(args, path)
         traffic = prof["hbm_bytes_per_step"] if prof else None
         pattern_bytes = 0
@@ -537,49 +658,8 @@ def main():
                            " (the sparse hit lists, 8 B per hit, are not counted)")}
         if roof is None:
             roof = hbm
-        out = {
-            "metric": "haplotype-windows scored/sec",
-            "value": value,
-            "unit": "windows/s",
-            "n_gpus": world,
-            "steps": steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed * 1e3 / steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "fp4xfp6->f32 bound + int32 exact" if path == "mfma" else "int32",
-            "data": "synthetic (SURVEY.md 8d generator; no HOCOMOCO/BCF download possible)",
-            "config": {
-                "workload": args.workload + ("-custom" if args.custom else ""),
-                "samples": args.samples, "haplotypes": 2 * args.samples, "regions_per_gpu": args.regions,
-                "regions_per_rank_batch": count,
-                "region_bp": 201, "pwms": args.pwms, "patterns": len(ps), "threshold": args.threshold,
-                "indel_pct": args.indel_pct, "seed": args.seed,
-                "distinct_haplotypes_per_gpu": batch.num_haplotypes,
-                "windows_per_step": int(tot_windows),
-                "parallelism": ("region shard x%d" % world if parts == 1 else
-                                "region x PWM shard: %d region blocks x %d pattern shards" % (world // parts, parts)),
-                "scan_path": path,
-                "scanned_windows_per_step": int(tot_scan),
-                "window_list_entries": [int(wl_entries[0]), int(wl_entries[1])],
-            },
-            "value_note": "windows of every distinct haplotype resolved per second, scan AND key assembly in "
-                          "the timed step (the reference scores each window and counts its hits per key, "
-                          "main.rs:94-154, 500-534); a haplotype's windows whose bases and positions equal the "
-                          "region's reference window take the reference window's hits in the assembly (reference-"
-                          "window reuse, exact; TFBS_DEDUP=0 scans them all); scanned_windows_per_s counts the "
-                          "windows the kernels read",
-            "step": "tfbs_step = tfbs_scan + tfbs_batch_assemble + tfbs_batch_assemble_wait (host sync and "
-                    "list check every step; from the third step alike the launches replay as one hipGraph): "
-                    "scan kernels, overflow rescoring, spill bucketing, key assembly + classification + "
-                    "varying-count compaction of every region of the batch",
+        out.update({
             "step_device_ms": {"scan": kms, "mfma_phase": mms, "assemble": ams},
-            "ranks": {"world_size": world, "backend": args.dist_backend if dist is not None else None,
-                      "ms_per_step": per_rank_ms},
-            "scanned_windows_per_s": tot_scan * steps / elapsed,
-            "scan_regions_per_s": tot_regions * steps / elapsed,
-            "effective_windows_per_s": tot_eff * steps / elapsed,
             "end_to_end": {
                 # definition v3 (round 3 on): host prep wall (build_region + commit; the synthetic
                 # generation excluded) + upload + scan + key reduction + device encode + device BGZF
@@ -620,9 +700,10 @@ def main():
                              "note": "not a roofline: the executed (window, strand, column) lookups per second "
                                      "against the chip's int32 VALU peak (one lane-op per lookup); > 1 means "
                                      "no VALU formulation of the scan could reach this rate"},
-        }
+        })
         if world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(T, ps, args, args.cpu_seconds)
+    if rank == 0:
         print(json.dumps(out), file=json_out, flush=True)
     sc.close()
     if dist is not None:

@@ -1,7 +1,7 @@
 """GPU occupancy of bench.py's end-to-end rows + encode window, from a rocprofv3 database.
 
 Usage: python3 tools/e2e_window.py <run_results.db>
-(rocprofv3 --kernel-trace --memory-copy-trace -d DIR -o run -- python3 bench.py --workload C5 ...)
+(rocprofv3 --kernel-trace --memory-copy-trace -d DIR -o run -- python3 bench.py --full --workload C5 ...)
 Prints the window (first key_encode_kernel to the last bgzf kernel), the time the GPU's kernels and
 copies were busy in it, the kernels' totals and the idle gaps by the operations on either side.
 """
