@@ -824,6 +824,7 @@ static inline uint32_t pack16(const uint8_t *p) {
 void commit_regions(Batch &B, std::vector<RegionBuilt> &built, uint32_t threads) {
     const size_t nr = built.size();
     if (!nr) return;
+    B.lists_counted = false;  // (the uploaded lists' statistics are not this batch's any more)
     // per haplotype: length, has N, affine positions (parallel scan of the sequences)
     struct HapInfo {
         uint32_t n;
@@ -1435,8 +1436,13 @@ size_t tfbs_batch_num_haplotypes(const tfbs_batch *b) {  // helper reference cop
 uint64_t tfbs_batch_num_windows(const tfbs_batch *b) { return b ? b->b.windows : 0; }
 uint64_t tfbs_batch_num_effective_windows(const tfbs_batch *b) { return b ? b->b.eff_windows : 0; }
 uint64_t tfbs_batch_num_cell_ops(const tfbs_batch *b) { return b ? b->b.cell_ops : 0; }
-uint64_t tfbs_batch_num_scan_windows(const tfbs_batch *b) { return b ? b->b.scan_windows : 0; }
-uint64_t tfbs_batch_num_scan_cell_ops(const tfbs_batch *b) { return b ? b->b.scan_cell_ops : 0; }
+// (after an upload that shares windows: what its lists hold, distinct windows)
+uint64_t tfbs_batch_num_scan_windows(const tfbs_batch *b) {
+    return !b ? 0 : b->b.lists_counted ? b->b.list_windows : b->b.scan_windows;
+}
+uint64_t tfbs_batch_num_scan_cell_ops(const tfbs_batch *b) {
+    return !b ? 0 : b->b.lists_counted ? b->b.list_cell_ops : b->b.scan_cell_ops;
+}
 uint64_t tfbs_batch_input_bytes(const tfbs_batch *b) { return b ? b->b.device_bytes() : 0; }
 uint64_t tfbs_batch_output_bytes(const tfbs_batch *b) { return b ? b->b.n_counts * 4ull : 0; }
 

@@ -188,6 +188,12 @@ struct Batch {
     bool dedup = true;
     bool dev_patch = true;   // device grouping + host patching of indel regions (TFBS_DEV_PATCH=0: off)
     uint64_t scan_windows = 0, scan_cell_ops = 0;
+    // shared windows (tfbs_batch_upload, TFBS_SHARE=0 turns them off): the two above
+    // counted from what the uploaded window lists hold -- a window shared by several
+    // haplotypes of a region once --, valid while lists_counted (an upload that shared
+    // windows, no region added since)
+    bool lists_counted = false;
+    uint64_t list_windows = 0, list_cell_ops = 0;
     // host prep seconds (tfbs_batch_prep_seconds): synthetic generation (thread
     // CPU-seconds), build_region (thread CPU-seconds), serial commit (wall), whole fill (wall)
     double prep_s[4] = {0, 0, 0, 0};

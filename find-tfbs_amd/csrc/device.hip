@@ -128,6 +128,7 @@ struct tfbs_ctx {
     uint32_t cand_cap = 1024;            // per scan workgroup (TFBS_CAND_CAP), per super tile it scans
     bool mfma_merged = true;             // TFBS_SCAN_MERGED=0: one launch per depth class (a workgroup per super tile)
     uint32_t scan_cand_cap = 1024;       // the last scan's list entries per workgroup (ScanArgs::cand_cap)
+    uint32_t scan_hit_cap = 1024;        // and its hit list entries per workgroup (ScanArgs::hit_cap)
     DevBuf<DevMSuper> m_supers;
     bool mfma = true;             // int8 matrix-core path for eligible strands (TFBS_MFMA=0: LUT only)
     uint32_t mfma_lds = 44 * 1024;  // LDS image budget of one MFMA super tile
@@ -150,6 +151,14 @@ struct tfbs_ctx {
     DevBuf<uint4> hd, hd2;     // the matrix-core scan's compact haplotype descriptors
     uint64_t wl_entries[2] = {0, 0};
     double wl_seconds = 0;                // the last build's wall time
+    // shared windows (ScanArgs::share; TFBS_SHARE=0: none), built with the lists
+    bool wl_share = false;                // the resident lists share windows
+    DevBuf<uint64_t> sh_off[2], sh_stat;
+    DevBuf<uint2> sh[2];
+    DevBuf<uint32_t> sh_cur;
+    DevBuf<ClassTab> sh_tab;
+    uint64_t sh_entries[2] = {0, 0};      // sharer entries per class
+    uint64_t sh_listed[2][2] = {{0, 0}, {0, 0}};  // per class: (window, strand) pairs and cells the lists hold
     DevBuf<DevRegion> regions;
     DevBuf<unsigned long long> hits;
     DevBuf<uint32_t> asm_scratch;         // key assembly counters of regions with many distinct haplotypes
@@ -315,8 +324,14 @@ static int env_int(const char *name, int dflt) {
 
 // The matrix-core window lists of the haplotypes just put on the device (one
 // per depth class the plan has; scan.hpp build_window_lists).
-static int build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t> &narrow) {
+// B: the batch whose haplotypes they are -- its windows are shared among the region's
+// haplotypes (scan_mfma.hip "Shared windows") unless TFBS_SHARE=0, read here --, or
+// null (a single haplotype: nothing to share).
+static int build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t> &narrow, Batch *B = nullptr) {
     const Plan &P = ctx->plan;
+    ctx->wl_share = false;
+    for (int c = 0; c < 2; c++) ctx->sh_entries[c] = ctx->sh_listed[c][0] = ctx->sh_listed[c][1] = 0;
+    if (B) B->lists_counted = false;
     if (P.m_supers.empty()) return TFBS_OK;
     const auto t0 = std::chrono::steady_clock::now();
     uint32_t lmin[2] = {0, 0}, span[2] = {0, 0};  // per depth class: shortest and longest strand
@@ -357,9 +372,57 @@ static int build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t
         *p16 = cx->wl16[c].p;
         return TFBS_OK;
     };
+    const bool share = B && B->dedup && n_haps && env_int("TFBS_SHARE", 1) != 0;
+    std::vector<std::pair<uint32_t, uint32_t>> rest;  // (length, strands) the matrix cores do not score
+    if (share) {
+        // the strand lengths of each depth class (a tile's class is its longest strand's):
+        // per columns left, the strands a listed window is scored for and their cells
+        std::vector<ClassTab> tab(2, ClassTab{});
+        rest = B->pwm_len_hist;
+        for (size_t t = 0; t * kGMetaInts < P.m_meta.size(); t++) {
+            const int32_t *gm = &P.m_meta[t * kGMetaInts];
+            ClassTab &ct = tab[gm[kGDepth] > 2];
+            for (int sn = 0; sn < kMStrands; sn++) {
+                if (gm[kGOrig + sn] < 0) continue;  // tile padding
+                const uint32_t L = (uint32_t)gm[kGStrandInts * sn + kGLen];
+                for (uint32_t r = L; r <= 32; r++) ct.w[r] += 1, ct.c[r] += L;
+                for (auto &lc : rest)
+                    if (lc.first == L && lc.second) lc.second--;
+            }
+        }
+        if ((rc = ctx->sh_tab.put(tab, ctx->stream)) || (rc = ctx->sh_stat.ensure(4)) ||
+            (rc = ctx->sh_cur.ensure(2 * (size_t)n_haps)))
+            return rc;
+        for (int c = 0; c < 2; c++)
+            if (lmin[c] && (rc = ctx->sh_off[c].ensure((size_t)n_haps + 1))) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // (tab is copied from this scope)
+        for (int c = 0; c < 2; c++) bufs.soff[c] = lmin[c] ? ctx->sh_off[c].p : nullptr;
+        bufs.scur = ctx->sh_cur.p;
+        bufs.stat = ctx->sh_stat.p;
+    }
+    auto ensure_share = [](void *x, int c, uint64_t n, uint2 **p) {
+        tfbs_ctx *cx = static_cast<tfbs_ctx *>(x);
+        if (int e = cx->sh[c].ensure(n)) return e;
+        *p = cx->sh[c].p;
+        return TFBS_OK;
+    };
     if ((rc = build_window_lists(ctx->haps.p, n_haps, ctx->druns.p, lmin, span, ctx->mfma_hpb, 1, bufs, ctx->wl_entries,
-                                 ctx->stream, ensure, ctx)))
+                                 ctx->stream, ensure, ctx, share ? 1u : 0u, ctx->regions.p, ctx->words.p, ctx->sh_tab.p,
+                                 ensure_share, ctx->sh_entries, ctx->sh_listed)))
         return rc;
+    ctx->wl_share = share;
+    if (share) {  // the scan statistics from what the lists hold (+ the other kernels' strands: every window)
+        B->list_windows = ctx->sh_listed[0][0] + ctx->sh_listed[1][0];
+        B->list_cell_ops = ctx->sh_listed[0][1] + ctx->sh_listed[1][1];
+        for (const auto &lc : rest) {
+            if (!lc.second) continue;
+            uint64_t nw = 0;
+            for (const DevHap &h : B->haps) nw += h.len >= lc.first ? h.len - lc.first + 1 : 0;
+            B->list_windows += nw * lc.second;
+            B->list_cell_ops += nw * lc.second * lc.first;
+        }
+        B->lists_counted = true;
+    }
     for (int c = 0; c < 2; c++)
         if (!lmin[c]) ctx->wl_off[c].release(), ctx->wl[c].release(), ctx->wl16[c].release();
     // The merged scan's workgroup order: groups by descending work (window pairs x the
@@ -445,13 +508,18 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
         const uint32_t cand_cap = ctx->mfma_merged
                                       ? (uint32_t)std::min<uint64_t>(1u << 16, (uint64_t)ctx->cand_cap * P.m_supers.size())
                                       : ctx->cand_cap;
+        // (shared windows: a donor's wave lists its sharers' pairs too -- at C3 a per-wave share
+        // of cand_cap / 8 sent 152 000 of 4.27 M pairs to the spill list)
+        const uint32_t hit_cap = (uint32_t)std::min<uint64_t>(1u << 16, (uint64_t)cand_cap * (ctx->wl_share ? 4 : 1));
         int rc;
-        if ((rc = ctx->cands.ensure(n_wg * cand_cap * kCandWords)) || (rc = ctx->hitl.ensure(n_wg * cand_cap * 2)) ||
+        if ((rc = ctx->cands.ensure(n_wg * cand_cap * kCandWords)) || (rc = ctx->hitl.ensure(n_wg * hit_cap * 2)) ||
             (rc = ctx->hitn.ensure(n_wg * (kMBlockWaves))) || (rc = ctx->candn.ensure(n_wg * (kMBlockWaves))))
             return rc;
         m.cands = ctx->cands.p;
         m.cand_cap = cand_cap;
         ctx->scan_cand_cap = cand_cap;
+        ctx->scan_hit_cap = hit_cap;
+        m.hit_cap = hit_cap;
         m.hitl = ctx->hitl.p;
         m.hitn = ctx->hitn.p;
         m.candn = ctx->candn.p;
@@ -486,6 +554,9 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
             m.wlist[c] = ctx->wl[c].p;
             m.wlist16[c] = ctx->wl16[c].p;
             m.wlist_off[c] = ctx->wl_off[c].p;
+            const bool sh = ctx->wl_share && ctx->wl_off[c].p && ctx->sh_entries[c];
+            m.share_off[c] = sh ? ctx->sh_off[c].p : nullptr;
+            m.share[c] = sh ? ctx->sh[c].p : nullptr;
         }
         {
             const uint32_t na = (uint32_t)(kAsmCtrWords + nr + 1);
@@ -668,7 +739,7 @@ static AsmArgs asm_args(tfbs_ctx *ctx, const Batch &B, int mode) {
     a.hpb = ctx->mfma_hpb;
     a.hitl = ctx->hitl.p;
     a.hitn = ctx->hitn.p;
-    a.cand_cap = ctx->scan_cand_cap;
+    a.cand_cap = ctx->scan_hit_cap;  // (the hit lists' geometry)
     a.srcs = ctx->srcs.p;
     a.mfma = ctx->plan.m_supers.empty() ? 0 : 1;
     a.n_srcs = a.mfma ? ctx->n_srcs : 0;
@@ -732,6 +803,8 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     ctx->words.release(); ctx->nmask.release(); ctx->counts.release(); ctx->posrel.release();
     ctx->druns.release(); ctx->wl_tmp.release();
     for (int c = 0; c < 2; c++) ctx->wl_off[c].release(), ctx->wl[c].release(), ctx->wl16[c].release();
+    for (int c = 0; c < 2; c++) ctx->sh_off[c].release(), ctx->sh[c].release();
+    ctx->sh_stat.release(); ctx->sh_cur.release(); ctx->sh_tab.release();
     ctx->gnarrow.release();
     ctx->gorder.release();
     ctx->gcost.release();
@@ -990,7 +1063,7 @@ int tfbs_batch_upload(tfbs_ctx *ctx, tfbs_batch *b) {
     std::vector<uint8_t> narrow((B.haps.size() + ctx->mfma_hpb - 1) / ctx->mfma_hpb, 1);  // (alive until the sync)
     for (size_t h = 0; h < B.haps.size(); h++)
         if (B.haps[h].len > kWlNarrowLen) narrow[h / ctx->mfma_hpb] = 0;
-    if ((rc = build_lists(ctx, (uint32_t)B.haps.size(), narrow))) return rc;
+    if ((rc = build_lists(ctx, (uint32_t)B.haps.size(), narrow, &B))) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->counts_live = dense;
     ctx->resident = b;
@@ -1366,9 +1439,13 @@ static uint64_t step_signature(const tfbs_ctx *ctx, const tfbs_batch *b) {
         buf(ctx->wl_off[c]);
         buf(ctx->wl[c]);
         buf(ctx->wl16[c]);
+        buf(ctx->sh_off[c]);
+        buf(ctx->sh[c]);
+        mix(ctx->sh_entries[c]);
     }
+    mix((uint64_t)ctx->wl_share);
     for (uint64_t v : {(uint64_t)ctx->spill_cap, (uint64_t)ctx->cand_over_cap, (uint64_t)ctx->cand_cap,
-                       (uint64_t)ctx->scan_cand_cap, (uint64_t)ctx->var_keys_cap, ctx->var_cap,
+                       (uint64_t)ctx->scan_cand_cap, (uint64_t)ctx->scan_hit_cap, (uint64_t)ctx->var_keys_cap, ctx->var_cap,
                        (uint64_t)ctx->cor_cap, (uint64_t)ctx->n_regions, (uint64_t)ctx->asm_order_n,
                        (uint64_t)ctx->asm_order_big, (uint64_t)ctx->n_srcs, (uint64_t)ctx->srcs_on_dev,
                        (uint64_t)ctx->counts_live, (uint64_t)ctx->mfma_group_words,

@@ -49,10 +49,12 @@ struct ScanArgs {
     // matrix-core hits, sparse (no count matrix, no atomics): the wave that
     // rescores its candidates appends one (haplotype, key = slot * n_inner +
     // range) pair per hit and overlapped inner range to its part of the
-    // workgroup's hit list (hitl + 2 (wg cand_cap + wave cand_cap / 8), the same
-    // geometry as the candidate list) and stores their number at hitn[8 wg +
-    // wave]; the excess goes to the spill list
+    // workgroup's hit list (hitl + 2 (wg hit_cap + wave hit_cap / 8), the candidate
+    // list's geometry with hit_cap entries per workgroup: cand_cap, or four times that
+    // when windows are shared -- a donor's wave lists its sharers' pairs too) and stores
+    // their number at hitn[8 wg + wave]; the excess goes to the spill list
     uint32_t *hitl;
+    uint32_t hit_cap;
     uint32_t *hitn;
     uint32_t *candn;  // per wave (as hitn): the candidates it found (tfbs_ctx_scan_counters; no atomics)
     // matrix-core window lists (build_window_lists), per depth class (2, 4): the
@@ -71,6 +73,15 @@ struct ScanArgs {
     // descending order of work, so the launch ends on the small ones); null: group b
     const uint32_t *gorder;
     const uint64_t *wlist_off[2];
+    // shared windows (build_window_lists, share != 0), per depth class: a window listed
+    // for its donor haplotype only stands for the same window of the region's other
+    // haplotypes whose bases and diff columns in it are the donor's.  Donor d's
+    // sharers are the entries [share_off[c][d], share_off[c][d + 1]) of share[c]: (the
+    // sharer's index in this launch's haps, i_lo | i_hi << 16) = "the sharer takes the
+    // donor's windows [i_lo, i_hi)"; every hit of the donor is listed for them too
+    // (scan_mfma.hip, expansion).  null: nothing is shared
+    const uint64_t *share_off[2];
+    const uint2 *share[2];
     // reference-window reuse (HAP_DEDUP haplotypes, tfbs_internal.hpp): dedup
     // != 0 scans only their dirty windows (the lists); the HAP_REF haplotypes' hits
     // (strand, window) are listed per region (ref_count[r] of kRefPerRegion at
@@ -171,6 +182,20 @@ struct WindowListBufs {
     uint4 *hd;             // n_haps compact descriptors (ScanArgs::hd), written here
     uint4 *hd2;            // and ScanArgs::hd2
     uint64_t list_cap[2];  // entries
+    // shared windows (share != 0): per class n_haps + 1 offsets by donor, the entries
+    // (grown with ensure_share), 2 n_haps words of scratch (per-haplotype statistics,
+    // then the fill cursors); stat: 2 u64 per class, the (window, strand) pairs and
+    // cells of the windows the lists hold
+    uint64_t *soff[2];
+    uint32_t *scur;
+    uint2 *share[2];
+    uint64_t *stat;
+};
+// Per depth class: the strands a listed window with r columns left in its haplotype
+// is scored for (those of length <= r), w[min(r, 32)] of them with c[min(r, 32)]
+// cells in all (the scan statistics of lists with shared windows).
+struct ClassTab {
+    uint32_t w[33], c[33];
 };
 size_t scan_tmp_words(size_t n);
 // Per haplotype group of hpb (n_groups): the window tiles of its lists, cost[g] =
@@ -178,10 +203,18 @@ size_t scan_tmp_words(size_t n);
 // depth class's super tiles), for the scan's workgroup order.
 int group_costs(const uint64_t *off0, const uint64_t *off1, uint32_t n_haps, uint32_t hpb, uint32_t w0, uint32_t w1,
                 uint32_t *cost, hipStream_t stream);
+// share != 0: shared windows (ScanArgs::share) -- regions / words: the batch's; a
+// HAP_DEDUP haplotype without indels or N lists a dirty window only when no
+// lower-indexed haplotype of its region has the same window; shared[c] gets the
+// sharer entries of class c (ensure_share grows bufs.share[c]), tab[c] the class's
+// strand lengths, listed[c] the (window, strand) pairs and cells its list holds.
 int build_window_lists(const DevHap *haps, uint32_t n_haps, const uint32_t *druns, const uint32_t lmin[2],
                        const uint32_t span[2], uint32_t hpb, uint32_t dedup, WindowListBufs &bufs, uint64_t total[2], hipStream_t stream,
                        int (*ensure_list)(void *ctx, int c, uint64_t n, uint32_t **p, uint16_t **p16),
-                       void *ensure_ctx);
+                       void *ensure_ctx, uint32_t share = 0, const DevRegion *regions = nullptr,
+                       const uint32_t *words = nullptr, const ClassTab *tab = nullptr,
+                       int (*ensure_share)(void *ctx, int c, uint64_t n, uint2 **p) = nullptr,
+                       uint64_t shared[2] = nullptr, uint64_t listed[2][2] = nullptr);
 // Super tile image budgets per K depth (1-8) that let each depth's kernel reach
 // the waves per SIMD its registers allow.
 void mfma_depth_budgets(uint32_t out[9]);

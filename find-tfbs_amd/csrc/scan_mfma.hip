@@ -245,6 +245,23 @@ __device__ __forceinline__ void spill_record(const ScanArgs &A, uint32_t head, u
     }
 }
 
+// Shared windows (ScanArgs::share): f(s) for every sharer s of donor `hap`'s window i
+// in depth class c (one thread walks the donor's entries: the rare paths; the wave
+// lists' expansion is wave-cooperative, rescore_list).
+template <class F>
+__device__ __forceinline__ void for_sharers(const ScanArgs &A, uint32_t c, uint32_t hap, uint32_t i, F &&f) {
+    const uint64_t *so = A.share_off[c];
+    if (!so) return;
+    const uint64_t e1 = so[hap + 1];
+    for (uint64_t e = so[hap]; e < e1; e++) {
+        const uint2 s = A.share[c][e];
+        if (i >= (s.y & 0xFFFFu) && i < (s.y >> 16)) f(s.x);
+    }
+}
+__device__ __forceinline__ uint32_t strand_class(const ScanArgs &A, uint32_t g) {  // 0: depth 1-2, 1: depth 3-4
+    return A.mmeta[(size_t)(g >> 6) * kGMetaInts + kGDepth] > 2 ? 1u : 0u;
+}
+
 // Exact rescoring of one candidate: window i of haplotype hp (hits index hap)
 // for the strand g = global tile * 64 + strand in tile.  A HAP_DEDUP haplotype's
 // window read because it meets a diff run within the class span, but whose strand
@@ -280,9 +297,15 @@ __device__ __forceinline__ uint32_t score_candidate(const ScanArgs &A, const uin
             dirty = run_meets(A.druns[2 * k], A.druns[2 * k + 1], i, L);
         if (!dirty) return 0;
     }
-    if (A.hits && i / 64 < A.hits_wpp)
-        atomicOr(A.hits + ((size_t)hap * A.n_patterns_total + (uint32_t)meta[kGOrig + sn]) * A.hits_wpp + i / 64,
-                 1ull << (i & 63));
+    const bool donor = (hp.flags & HAP_DEDUP) && (A.share_off[0] || A.share_off[1]);  // its sharers hit too
+    if (A.hits && i / 64 < A.hits_wpp) {
+        auto mark = [&](uint32_t x) {
+            atomicOr(A.hits + ((size_t)x * A.n_patterns_total + (uint32_t)meta[kGOrig + sn]) * A.hits_wpp + i / 64,
+                     1ull << (i & 63));
+        };
+        mark(hap);
+        if (donor) for_sharers(A, strand_class(A, g), hap, i, mark);
+    }
     if ((hp.flags & HAP_REF) && A.dedup) {  // for the HAP_DEDUP haplotypes' unscanned windows
         const uint32_t at = atomicAdd(A.ref_count + hp.region, 1u);
         if (at < kRefPerRegion) {
@@ -306,16 +329,20 @@ __device__ __forceinline__ uint32_t score_candidate(const ScanArgs &A, const uin
     for (uint32_t k = 32; k < rg.n_inner; k++) {        // ranges past 32 (rare)
         const int32_t s = inner[2 * k], en = inner[2 * k + 1];
         const uint32_t span = (uint32_t)(en - s);
-        if ((uint32_t)(p - s) <= span || (uint32_t)(p + (int32_t)L - 1 - s) <= span)
+        if ((uint32_t)(p - s) <= span || (uint32_t)(p + (int32_t)L - 1 - s) <= span) {
             spill_record(A, hp.region, A.hap_base + hap, off0 + k);
+            if (donor)
+                for_sharers(A, strand_class(A, g), hap, i,
+                            [&](uint32_t x) { spill_record(A, hp.region, A.hap_base + x, off0 + k); });
+        }
     }
     *key0 = off0;
     return mask;
 }
 
-// The hit lists' room per wave (A.cand_cap per workgroup), and the candidates': the
-// LDS list's (at most kWaveCands) followed by the wave's region of the global list
-// (TFBS_CAND_CAP makes all of them small in the spill tests).
+// The candidate lists' room per wave (A.cand_cap per workgroup; the hit lists':
+// A.hit_cap, rescore_list): the LDS list's (at most kWaveCands) followed by the wave's
+// region of the global list (TFBS_CAND_CAP makes all of them small in the spill tests).
 __device__ __forceinline__ uint32_t wave_cand_cap(const ScanArgs &A) { return A.cand_cap / (kMBlock / 64); }
 __device__ __forceinline__ uint32_t wave_lds_cap(const ScanArgs &A) { return min(wave_cand_cap(A), kWaveCands); }
 // slot: the workgroup's place in the per-workgroup lists (region_base + its
@@ -332,21 +359,35 @@ __device__ __forceinline__ uint2 *cand_list(const ScanArgs &A, uint32_t slot, ui
 // list in lane order (ballot prefix: no atomics), the excess spilled.
 __device__ __forceinline__ void rescore_list(const ScanArgs &A, const uint32_t *words, uint32_t h0, uint32_t slot, uint32_t wave,
                                              uint32_t lane, uint32_t cn) {
-    const uint32_t cap = wave_cand_cap(A);
-    const size_t part = (size_t)slot * A.cand_cap + (size_t)wave * cap;
+    const uint32_t cap = A.hit_cap / (kMBlock / 64);  // the hit list's room per wave
+    const size_t part = (size_t)slot * A.hit_cap + (size_t)wave * cap;
     uint2 *out = reinterpret_cast<uint2 *>(A.hitl) + part;
     uint32_t hn = 0;  // wave-uniform
-    const uint32_t lcap = wave_lds_cap(A), n = min(cn, lcap + cap);
+    const uint32_t lcap = wave_lds_cap(A), n = min(cn, lcap + wave_cand_cap(A));
     const uint2 *glist = cand_list(A, slot, wave);
+    const bool shared = A.share_off[0] || A.share_off[1];
     for (uint32_t k0 = 0; k0 < n; k0 += 64) {
         const uint32_t k = k0 + lane;
-        uint32_t mask = 0, key0 = 0, hap = 0;
+        uint32_t mask = 0, key0 = 0, hap = h0, g = 0, win = 0;
         if (k < n) {
             const uint2 c = k < lcap ? s_cand[wave][k] : glist[k - lcap];
             hap = h0 + (c.x >> 24);
             const uint32_t hl = c.x >> 24;  // the haplotype's descriptors, staged in LDS
-            mask = score_candidate(A, words, CandHap::of(s_hd[hl], s_hd2[hl]), hap, c.x & 0xFFFFFFu, c.y, &key0);
+            g = c.x & 0xFFFFFFu;
+            win = c.y;
+            mask = score_candidate(A, words, CandHap::of(s_hd[hl], s_hd2[hl]), hap, g, win, &key0);
         }
+        // a donor's hit is its sharers' too (shared windows): the lane's class and entries
+        uint32_t sc = 0, sn = 0;
+        uint64_t se = 0;
+        if (shared && mask && (s_hd[hap - h0].z & HAP_DEDUP)) {
+            sc = strand_class(A, g);
+            if (A.share_off[sc]) {
+                se = A.share_off[sc][hap];
+                sn = (uint32_t)(A.share_off[sc][hap + 1] - se);
+            }
+        }
+        const uint32_t mask0 = mask;
         uint64_t act;
         while ((act = __ballot(mask != 0)) != 0) {
             if (mask) {
@@ -358,6 +399,34 @@ __device__ __forceinline__ void rescore_list(const ScanArgs &A, const uint32_t *
                 else spill_record(A, s_hd2[hap - h0].x, A.hap_base + hap, key);
             }
             hn += (uint32_t)__popcll(act);
+        }
+        // expansion, one hit at a time: 64 lanes test 64 of the donor's entries, each
+        // covering entry's sharer gets the hit's pairs (the same ballot-prefix append)
+        for (uint64_t todo = __ballot(sn != 0); todo; todo &= todo - 1) {
+            const int src = __builtin_ctzll(todo);
+            const uint32_t d_c = (uint32_t)__shfl((int)sc, src), d_n = (uint32_t)__shfl((int)sn, src);
+            const uint64_t d_e = (uint64_t)(uint32_t)__shfl((int)(uint32_t)se, src) |
+                                 ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(se >> 32), src) << 32);
+            const uint32_t d_i = (uint32_t)__shfl((int)win, src), d_key0 = (uint32_t)__shfl((int)key0, src);
+            const uint32_t d_mask = (uint32_t)__shfl((int)mask0, src);
+            const uint32_t d_region = s_hd2[(uint32_t)__shfl((int)hap, src) - h0].x;
+            for (uint32_t e0 = 0; e0 < d_n; e0 += 64) {
+                uint2 s = make_uint2(0, 0);
+                if (e0 + lane < d_n) s = A.share[d_c][d_e + e0 + lane];
+                const bool mine = d_i >= (s.y & 0xFFFFu) && d_i < (s.y >> 16);  // (no entry: [0, 0))
+                const uint64_t cov = __ballot(mine);
+                if (!cov) continue;
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(cov >> 32),
+                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)cov, 0));
+                for (uint32_t m = d_mask; m; m &= m - 1) {
+                    if (mine) {
+                        const uint32_t at = hn + rank, key = d_key0 + __builtin_ctz(m);
+                        if (at < cap) out[at] = make_uint2(A.hap_base + s.x, key);
+                        else spill_record(A, d_region, A.hap_base + s.x, key);
+                    }
+                    hn += (uint32_t)__popcll(cov);
+                }
+            }
         }
     }
     if (lane == 0) {
@@ -955,9 +1024,13 @@ __global__ __launch_bounds__(256) void cand_over_kernel(ScanArgs A) {
         const uint32_t hap = A.cand_over[3 * (size_t)k], g = A.cand_over[3 * (size_t)k + 1];
         const DevHap hp = A.haps[hap];
         uint32_t key0 = 0;
-        for (uint32_t m = score_candidate(A, A.words, CandHap::of(hp), hap, g, A.cand_over[3 * (size_t)k + 2], &key0); m;
-             m &= m - 1)
-            spill_record(A, hp.region, hap, key0 + __builtin_ctz(m));
+        const uint32_t i = A.cand_over[3 * (size_t)k + 2];
+        const uint32_t m0 = score_candidate(A, A.words, CandHap::of(hp), hap, g, i, &key0);
+        for (uint32_t m = m0; m; m &= m - 1) spill_record(A, hp.region, hap, key0 + __builtin_ctz(m));
+        if (m0 && (hp.flags & HAP_DEDUP))  // shared windows: the sharers' pairs
+            for_sharers(A, strand_class(A, g), hap, i, [&](uint32_t x) {
+                for (uint32_t m = m0; m; m &= m - 1) spill_record(A, hp.region, A.hap_base + x, key0 + __builtin_ctz(m));
+            });
     }
 }
 
@@ -1013,6 +1086,207 @@ __global__ __launch_bounds__(256) void wl_fill_kernel(const DevHap *__restrict__
         }
         at += hi - lo;
     });
+}
+
+// ---------------------------------------------------------------------------
+// Shared windows.  Haplotypes of one region mostly differ at sites far apart, so near
+// any one site many of them are base for base the same: window i of a depth class of
+// span S is *shared* by two HAP_DEDUP haplotypes of the region without indels or N, of
+// equal length, when it is dirty in both and their bases AND diff columns on [i, i + S)
+// (clipped to the length) are equal -- the exact 64-bit base image and 32-bit column
+// mask are compared, no hash.  The lowest-indexed such haplotype is the window's
+// *donor*: only the donor lists it; the others (its sharers) get one (sharer, [i_lo,
+// i_hi)) entry per run of consecutive windows taken from the same donor, in the
+// donor's entry range (ScanArgs::share), and the rescoring lists a donor's hits for
+// every sharer whose entry covers the window.  That is exact: position, inner ranges
+// and length are the region's, score and the dirty-for-L test depend only on the
+// window's bases and diff columns.  Everything else (the reference, a helper, indel
+// or N haplotypes, haplotypes scanned whole) lists its windows as before.
+__device__ __forceinline__ bool hap_shares(uint32_t flags) {
+    return (flags & (HAP_DEDUP | HAP_REF | HAP_HAS_POS | HAP_HAS_N)) == HAP_DEDUP;
+}
+// bit j: column i + j (j < n <= 32) lies in one of the haplotype's diff runs
+__device__ __forceinline__ uint32_t run_mask(const uint32_t *__restrict__ druns, uint32_t off, uint32_t nr, uint32_t i,
+                                             uint32_t n) {
+    uint32_t m = 0;
+    for (uint32_t k = 0; k < nr; k++) {
+        const uint32_t a = druns[2 * (off + k)], b = druns[2 * (off + k) + 1];
+        const uint32_t lo = max(a, i), hi = min(b, i + n - 1);
+        if (hi < lo) continue;  // (also a boundary run [a, a - 1])
+        const uint32_t cnt = hi - lo + 1;
+        m |= (cnt >= 32 ? 0xFFFFFFFFu : (1u << cnt) - 1) << (lo - i);
+    }
+    return m;
+}
+// the 2-bit bases of columns [i, i + n), n <= 32 (the words carry 3 pad words)
+__device__ __forceinline__ uint64_t window_bases(const uint32_t *__restrict__ words, uint32_t word_off, uint32_t i,
+                                                 uint32_t n) {
+    const uint32_t *w = words + word_off + (i >> 4);
+    const uint32_t sh = 2 * (i & 15);
+    const uint64_t v = (uint64_t)__builtin_amdgcn_alignbit(w[1], w[0], sh) |
+                       ((uint64_t)__builtin_amdgcn_alignbit(w[2], w[1], sh) << 32);
+    return n >= 32 ? v : v & ((1ull << (2 * n)) - 1);
+}
+
+// The donor of window i of haplotype h (hm; `active` lanes, one window each, windows
+// [c_lo, c_hi] over the wave): the lowest-indexed haplotype of the region sharing it,
+// h itself when none does.  h and hm are wave-uniform.
+__device__ __forceinline__ uint32_t find_donor(const DevHap *__restrict__ haps, const DevRegion *__restrict__ regions,
+                                               const uint32_t *__restrict__ druns, const uint32_t *__restrict__ words,
+                                               uint32_t h, const DevHap &hm, uint32_t i, bool active, uint32_t S,
+                                               uint32_t c_lo, uint32_t c_hi, uint32_t lane) {
+    if (!hap_shares(hm.flags)) return h;
+    const uint32_t n = active ? min(S, hm.len - i) : 1u;
+    const uint32_t ii = active ? i : 0u;
+    const uint32_t rm = run_mask(druns, hm.drun_off, hm.n_druns, ii, n);
+    const uint64_t key = window_bases(words, hm.word_off, ii, n);
+    uint32_t donor = h;
+    uint64_t open = __ballot(active);
+    // 64 lower-indexed haplotypes at a time, one per lane: those that may share (some run
+    // of theirs meets the columns of the wave's windows); then the wave compares its
+    // windows with each of them in ascending order
+    for (uint32_t b0 = regions[hm.region].hap_begin; b0 < h && open; b0 += 64) {
+        bool cand = false;
+        if (b0 + lane < h) {
+            const DevHap o = haps[b0 + lane];
+            if (hap_shares(o.flags) && o.len == hm.len)
+                for (uint32_t k = 0; k < o.n_druns && !cand; k++)
+                    cand = druns[2 * (o.drun_off + k)] <= c_hi + S - 1 && druns[2 * (o.drun_off + k) + 1] >= c_lo;
+        }
+        for (uint64_t cm = __ballot(cand); cm && open; cm &= cm - 1) {
+            const uint32_t h2 = b0 + (uint32_t)__builtin_ctzll(cm);
+            const uint32_t o_runs = haps[h2].drun_off, o_nr = haps[h2].n_druns, o_words = haps[h2].word_off;
+            bool eq = false;
+            if (active && donor == h && run_mask(druns, o_runs, o_nr, ii, n) == rm)
+                eq = window_bases(words, o_words, ii, n) == key;
+            if (eq) donor = h2;
+            open &= ~__ballot(eq);
+        }
+    }
+    return donor;
+}
+
+// One wave per haplotype h, its listed windows (for_windows) 64 at a time: f(w, active,
+// donor) with the lane's window, whether it has one, and the window's donor.
+template <class F>
+__device__ __forceinline__ void for_shared_windows(const DevHap *__restrict__ haps,
+                                                   const DevRegion *__restrict__ regions,
+                                                   const uint32_t *__restrict__ druns,
+                                                   const uint32_t *__restrict__ words, uint32_t h, const DevHap &hm,
+                                                   uint32_t lmin, uint32_t S, uint32_t lane, F &&f) {
+    for_windows(hm, druns, lmin, S, 1u, [&](uint32_t lo, uint32_t hi) {
+        for (uint32_t w0 = lo; w0 < hi; w0 += 64) {
+            const uint32_t w = w0 + lane;
+            const bool active = w < hi;
+            f(w, active, find_donor(haps, regions, druns, words, h, hm, w, active, S, w0, min(w0 + 63, hi - 1), lane));
+        }
+    });
+}
+
+// Of the lanes with `sh` (a sharer's window, its donor d): whether the lane starts a
+// run of consecutive lanes with the same donor, and the run's length.
+__device__ __forceinline__ bool sharer_run(bool sh, uint32_t d, uint32_t lane, uint32_t *len) {
+    const uint32_t pd = (uint32_t)__shfl_up((int)d, 1);
+    const bool psh = __shfl_up((int)sh, 1) != 0;
+    const bool start = sh && (lane == 0 || !psh || pd != d);
+    const uint64_t cont = __ballot(sh && !start);
+    const uint64_t after = lane == 63 ? 0ull : cont >> (lane + 1);
+    *len = 1 + (uint32_t)__builtin_ctzll(~after);
+    return start;
+}
+
+// cnt[h]: the windows haplotype h lists itself; scnt[d] += the sharer entries of donor
+// d (zeroed before); hstat[2 h], [2 h + 1]: the (window, strand) pairs and cells of the
+// windows h lists (tab: the class's strand lengths).
+__global__ __launch_bounds__(256) void wl_share_count_kernel(const DevHap *__restrict__ haps, uint32_t n,
+                                                             const DevRegion *__restrict__ regions,
+                                                             const uint32_t *__restrict__ druns,
+                                                             const uint32_t *__restrict__ words, uint32_t lmin,
+                                                             uint32_t S, const ClassTab *__restrict__ tab,
+                                                             uint64_t *__restrict__ cnt,
+                                                             unsigned long long *__restrict__ scnt,
+                                                             uint32_t *__restrict__ hstat) {
+    const uint32_t h = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    if (h > n) return;
+    if (h == n) {
+        if (lane == 0) cnt[n] = 0;
+        return;
+    }
+    const DevHap hm = haps[h];
+    uint32_t own = 0, rw = 0, rc = 0;
+    for_shared_windows(haps, regions, druns, words, h, hm, lmin, S, lane, [&](uint32_t w, bool active, uint32_t d) {
+        const bool mine = active && d == h;
+        own += (uint32_t)__popcll(__ballot(mine));
+        uint32_t len;
+        if (sharer_run(active && !mine, d, lane, &len)) atomicAdd(scnt + d, 1ull);
+        if (mine) {
+            const uint32_t r = min(hm.len - w, 32u);
+            rw += tab->w[r];
+            rc += tab->c[r];
+        }
+    });
+    for (uint32_t o = 32; o; o >>= 1) {
+        rw += (uint32_t)__shfl_down((int)rw, o);
+        rc += (uint32_t)__shfl_down((int)rc, o);
+    }
+    if (lane == 0) {
+        cnt[h] = own;
+        hstat[2 * (size_t)h] = rw;
+        hstat[2 * (size_t)h + 1] = rc;
+    }
+}
+
+// The haplotype's own windows to its list range (ascending), its sharer entries to
+// their donors' ranges (soff; scur: fill cursors, zeroed before).
+__global__ __launch_bounds__(256) void wl_share_fill_kernel(const DevHap *__restrict__ haps, uint32_t n,
+                                                            const DevRegion *__restrict__ regions,
+                                                            const uint32_t *__restrict__ druns,
+                                                            const uint32_t *__restrict__ words, uint32_t lmin, uint32_t S,
+                                                            uint32_t hpb, const uint64_t *__restrict__ off,
+                                                            uint32_t *__restrict__ list, uint16_t *__restrict__ list16,
+                                                            const uint8_t *__restrict__ gnarrow,
+                                                            const uint64_t *__restrict__ soff,
+                                                            uint32_t *__restrict__ scur, uint2 *__restrict__ share) {
+    const uint32_t h = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    if (h >= n) return;
+    const DevHap hm = haps[h];
+    uint64_t at = off[h];
+    const uint64_t end = off[h + 1];
+    const uint32_t hl = h % hpb;
+    const bool narrow = gnarrow && gnarrow[h / hpb];
+    for_shared_windows(haps, regions, druns, words, h, hm, lmin, S, lane, [&](uint32_t w, bool active, uint32_t d) {
+        const bool own = active && d == h;
+        const uint64_t ob = __ballot(own);
+        const uint64_t q = at + __builtin_amdgcn_mbcnt_hi((uint32_t)(ob >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ob, 0));
+        if (own && q < end) {  // (q < end: the count pass's number, whatever happens)
+            if (narrow) list16[q] = (uint16_t)((w << 6) | hl);
+            else list[q] = (w << 6) | hl;
+        }
+        at += (uint32_t)__popcll(ob);
+        uint32_t len;
+        if (sharer_run(active && d != h, d, lane, &len)) {
+            const uint64_t e = soff[d] + atomicAdd(scur + d, 1u);
+            if (e < soff[d + 1]) share[e] = make_uint2(h, w | ((w + len) << 16));
+        }
+    });
+}
+
+// sum[0], sum[1] += the even and the odd words of x[0 .. 2 n)
+__global__ __launch_bounds__(256) void pair_sum_kernel(const uint32_t *__restrict__ x, uint32_t n,
+                                                       unsigned long long *__restrict__ sum) {
+    unsigned long long a = 0, b = 0;
+    for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
+        a += x[2 * (size_t)k];
+        b += x[2 * (size_t)k + 1];
+    }
+    for (uint32_t o = 32; o; o >>= 1) {
+        a += (unsigned long long)__shfl_down((long long)a, o);
+        b += (unsigned long long)__shfl_down((long long)b, o);
+    }
+    if ((threadIdx.x & 63) == 0 && (a | b)) {
+        atomicAdd(sum, a);
+        atomicAdd(sum + 1, b);
+    }
 }
 
 __global__ __launch_bounds__(256) void group_cost_kernel(const uint64_t *__restrict__ off0,
@@ -1150,15 +1424,20 @@ __device__ void post_candidates(const ScanArgs &A, uint32_t tid, uint32_t blk, u
     const uint32_t n = min(A.over[1], A.cand_over_cap), lane = tid & 63;
     for (uint32_t k0 = blk * NT; k0 < n; k0 += nblk * NT) {
         const uint32_t k = k0 + tid;
-        uint32_t m = 0, key0 = 0, region = 0, hap = 0;
+        uint32_t m = 0, key0 = 0, region = 0, hap = 0, sc = 0, si = 0, ns = 0;  // ns: sharers of the hit's window
         if (k < n) {
             hap = A.cand_over[3 * (size_t)k];
             const uint32_t g = A.cand_over[3 * (size_t)k + 1];
             const DevHap hp = A.haps[hap];
             region = hp.region;
-            m = score_candidate(A, A.words, CandHap::of(hp), hap, g, A.cand_over[3 * (size_t)k + 2], &key0);
+            si = A.cand_over[3 * (size_t)k + 2];
+            m = score_candidate(A, A.words, CandHap::of(hp), hap, g, si, &key0);
+            if (m && (hp.flags & HAP_DEDUP)) {
+                sc = strand_class(A, g);
+                for_sharers(A, sc, hap, si, [&](uint32_t) { ns++; });
+            }
         }
-        const uint32_t c = (uint32_t)__builtin_popcount(m);
+        const uint32_t c = (uint32_t)__builtin_popcount(m) * (1 + ns);
         uint32_t inc = c;
 #pragma unroll
         for (uint32_t o = 1; o < 64; o <<= 1) {
@@ -1169,12 +1448,16 @@ __device__ void post_candidates(const ScanArgs &A, uint32_t tid, uint32_t blk, u
         uint32_t base = 0;
         if (lane == 0 && total) base = atomicAdd(A.over, total);
         uint32_t at = (uint32_t)__shfl((int)base, 0) + inc - c;
-        for (; m; m &= m - 1, at++)
-            if (at < A.spill_cap) {
-                A.spill[3 * (size_t)at] = region;
-                A.spill[3 * (size_t)at + 1] = hap;
-                A.spill[3 * (size_t)at + 2] = key0 + __builtin_ctz(m);
-            }
+        auto put = [&](uint32_t x) {
+            for (uint32_t mm = m; mm; mm &= mm - 1, at++)
+                if (at < A.spill_cap) {
+                    A.spill[3 * (size_t)at] = region;
+                    A.spill[3 * (size_t)at + 1] = x;
+                    A.spill[3 * (size_t)at + 2] = key0 + __builtin_ctz(mm);
+                }
+        };
+        if (m) put(hap);
+        if (ns) for_sharers(A, sc, hap, si, [&](uint32_t x) { put(A.hap_base + x); });
     }
 }
 
@@ -1319,13 +1602,54 @@ size_t scan_tmp_words(size_t n) {
 int build_window_lists(const DevHap *haps, uint32_t n_haps, const uint32_t *druns, const uint32_t lmin[2],
                        const uint32_t span[2], uint32_t hpb, uint32_t dedup, WindowListBufs &bufs, uint64_t total[2], hipStream_t stream,
                        int (*ensure_list)(void *ctx, int c, uint64_t n, uint32_t **p, uint16_t **p16),
-                       void *ensure_ctx) {
+                       void *ensure_ctx, uint32_t share, const DevRegion *regions, const uint32_t *words,
+                       const ClassTab *tab, int (*ensure_share)(void *ctx, int c, uint64_t n, uint2 **p),
+                       uint64_t shared[2], uint64_t listed[2][2]) {
     if (n_haps && bufs.hd) hipLaunchKernelGGL(hd_kernel, dim3((n_haps + 255) / 256), dim3(256), 0, stream, haps, n_haps,
                                              bufs.hd, bufs.hd2);
+    share = share && dedup && n_haps;
+    if (share) {
+        hipError_t e = hipMemsetAsync(bufs.stat, 0, 4 * sizeof(uint64_t), stream);
+        if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("window lists: ") + hipGetErrorString(e));
+    }
     for (int c = 0; c < 2; c++) {
         total[c] = 0;
+        if (shared) shared[c] = 0;
+        if (listed) listed[c][0] = listed[c][1] = 0;
         if (!lmin[c]) continue;
         const uint32_t S = span[c] ? span[c] : kMChunkCols * (c ? 4 : 2);  // the windows dirty for the longest strand
+        if (share) {  // count (own windows, sharer entries per donor) -> offsets -> fill
+            unsigned long long *scnt = reinterpret_cast<unsigned long long *>(bufs.soff[c]);
+            hipError_t e = hipMemsetAsync(bufs.soff[c], 0, ((size_t)n_haps + 1) * 8, stream);
+            if (e == hipSuccess) e = hipMemsetAsync(bufs.scur, 0, (size_t)n_haps * 8, stream);  // (the count's hstat)
+            if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("window lists: ") + hipGetErrorString(e));
+            hipLaunchKernelGGL(wl_share_count_kernel, dim3(n_haps / 4 + 1), dim3(256), 0, stream, haps, n_haps, regions,
+                               druns, words, lmin[c], S, tab + c, bufs.off[c], scnt, bufs.scur);
+            hipLaunchKernelGGL(pair_sum_kernel, dim3(256), dim3(256), 0, stream, bufs.scur, n_haps,
+                               reinterpret_cast<unsigned long long *>(bufs.stat) + 2 * c);
+            int rc;
+            if ((rc = exclusive_scan(bufs.off[c], (uint64_t)n_haps + 1, bufs.scan_tmp, stream)) ||
+                (rc = exclusive_scan(bufs.soff[c], (uint64_t)n_haps + 1, bufs.scan_tmp, stream)))
+                return rc;
+            uint64_t ns = 0;
+            e = hipMemcpyAsync(&total[c], bufs.off[c] + n_haps, 8, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&ns, bufs.soff[c] + n_haps, 8, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(listed[c], bufs.stat + 2 * c, 16, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("window list size: ") + hipGetErrorString(e));
+            shared[c] = ns;
+            if ((rc = ensure_list(ensure_ctx, c, std::max<uint64_t>(total[c], 1), &bufs.list[c], &bufs.list16[c])) ||
+                (rc = ensure_share(ensure_ctx, c, std::max<uint64_t>(ns, 1), &bufs.share[c])))
+                return rc;
+            e = hipMemsetAsync(bufs.scur, 0, (size_t)n_haps * 4, stream);
+            if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("window lists: ") + hipGetErrorString(e));
+            hipLaunchKernelGGL(wl_share_fill_kernel, dim3((n_haps + 3) / 4), dim3(256), 0, stream, haps, n_haps, regions,
+                               druns, words, lmin[c], S, hpb, bufs.off[c], bufs.list[c], bufs.list16[c], bufs.gnarrow,
+                               bufs.soff[c], bufs.scur, bufs.share[c]);
+            e = hipGetLastError();
+            if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("wl_share_fill_kernel: ") + hipGetErrorString(e));
+            continue;
+        }
         hipLaunchKernelGGL(wl_count_kernel, dim3(n_haps / 256 + 1), dim3(256), 0, stream, haps, n_haps, druns, lmin[c],
                            S, dedup, bufs.off[c]);
         if (int rc = exclusive_scan(bufs.off[c], (uint64_t)n_haps + 1, bufs.scan_tmp, stream)) return rc;

@@ -237,7 +237,10 @@ uint64_t tfbs_batch_num_effective_windows(const tfbs_batch *b);
 /* Windows and column lookups the scan executes: a window of an SNV-only haplotype
    whose bases and positions equal the region's reference window takes the
    reference window's result (reference-window reuse, TFBS_DEDUP=0 disables it);
-   helper reference haplotypes of regions without a reference group count here. */
+   helper reference haplotypes of regions without a reference group count here.
+   After tfbs_batch_upload they count what the uploaded window lists hold: a window
+   that several SNV-only haplotypes of a region have in common once (shared windows,
+   TFBS_SHARE=0 at the upload disables them). */
 uint64_t tfbs_batch_num_scan_windows(const tfbs_batch *b);
 uint64_t tfbs_batch_num_scan_cell_ops(const tfbs_batch *b);
 /* Packed bytes the scan reads from HBM per launch (sequence + masks + positions + metadata). */
