@@ -8,13 +8,18 @@ LIBDIR := $(PKG)/lib
 OBJDIR := $(PKG)/lib/obj
 JOBS ?= 8
 
-HOST_SRCS := $(SRC)/patterns.cpp $(SRC)/plan.cpp $(SRC)/mfma.cpp $(SRC)/batch.cpp $(SRC)/aggregate.cpp $(SRC)/synth.cpp $(SRC)/io.cpp $(SRC)/inflate.cpp $(SRC)/run.cpp
-HIP_SRCS := $(SRC)/device.hip $(SRC)/scan_kernels.hip $(SRC)/scan_mfma.hip $(SRC)/key_kernels.hip $(SRC)/bgzf_gpu.hip $(SRC)/build_gpu.hip
+HOST_SRCS := $(SRC)/patterns.cpp $(SRC)/plan.cpp $(SRC)/plan_dinuc.cpp $(SRC)/mfma.cpp $(SRC)/batch.cpp $(SRC)/aggregate.cpp $(SRC)/synth.cpp $(SRC)/io.cpp $(SRC)/inflate.cpp $(SRC)/run.cpp
+HIP_SRCS := $(SRC)/device.hip $(SRC)/scan_kernels.hip $(SRC)/scan_dinuc.hip $(SRC)/scan_mfma.hip $(SRC)/key_kernels.hip $(SRC)/bgzf_gpu.hip $(SRC)/build_gpu.hip
 HDRS := $(wildcard $(SRC)/*.hpp) include/tfbs_amd.h
 HOST_OBJS := $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
 HIP_OBJS := $(patsubst $(SRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))
 
 CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter
+# DINUC_K=5: the dinucleotide kernel's other lookup width ("scan_dinuc_kernel"), built beside
+# the default, e.g. make DINUC_K=5 LIBDIR=$(PKG)/lib_k5 OBJDIR=$(PKG)/lib_k5/obj $(PKG)/lib_k5/libtfbs_amd.so
+ifdef DINUC_K
+CXXFLAGS += -DTFBS_DINUC_K=$(DINUC_K)
+endif
 HIPFLAGS := $(CXXFLAGS) --offload-arch=$(ARCH) -munsafe-fp-atomics
 
 all: $(LIBDIR)/libtfbs_amd.so $(PKG)/bin/find-tfbs-amd oracle

@@ -27,7 +27,7 @@ from ._capi import TfbsError, check, lib, tfbs_pattern_desc  # noqa: F401
 
 TFBS_OK = 0
 TFBS_E_NODEVICE = -10
-KIND_PWM, KIND_OTHER = 0, 1
+KIND_PWM, KIND_OTHER, KIND_DIPWM = 0, 1, 2
 DIR_P, DIR_N = 0, 1
 NUCLEOTIDES = "ACGTN"  # types.rs:5-8, the weight index order
 
@@ -54,7 +54,9 @@ class Weight:
 
 
 class Pattern:
-    """types.rs:86-90: PWM (kind 0) or OtherPattern (kind 1)."""
+    """types.rs:86-90: PWM (kind 0) or OtherPattern (kind 1); DiPWM (kind 2) is a
+    dinucleotide PWM: weights = L - 1 rows of 16 ints indexed 4 a + b for the pair
+    (base a, next base b), len() = L bases."""
 
     def __init__(self, name, pattern_id, weights=None, min_score=0, direction=DIR_P, kind=KIND_PWM):
         self.name = name
@@ -72,7 +74,13 @@ class Pattern:
     def OtherPattern(cls, name, pattern_id):
         return cls(name, pattern_id, [], 0, DIR_P, KIND_OTHER)
 
-    def __len__(self):  # pattern_length (types.rs:92-101)
+    @classmethod
+    def DiPWM(cls, rows16, name, pattern_id, min_score, direction=DIR_P):
+        return cls(name, pattern_id, [list(r) for r in rows16], min_score, direction, KIND_DIPWM)
+
+    def __len__(self):  # pattern_length (types.rs:92-101); a dinucleotide PWM counts bases
+        if self.kind == KIND_DIPWM:
+            return len(self.weights) + 1
         return len(self.weights) if self.kind == KIND_PWM else 0
 
     def __eq__(self, o):
@@ -113,7 +121,12 @@ class PatternSet:
         descs = (tfbs_pattern_desc * max(1, n))()
         keep = []
         for i, p in enumerate(patterns):
-            flat = [x for w in p.weights for x in (w.acgtn if isinstance(w, Weight) else list(w)[:4] + [0])]
+            if p.kind == KIND_DIPWM:
+                if any(len(r) != 16 for r in p.weights):
+                    raise ValueError("a dinucleotide PWM row has 16 weights")
+                flat = [x for r in p.weights for x in r]
+            else:
+                flat = [x for w in p.weights for x in (w.acgtn if isinstance(w, Weight) else list(w)[:4] + [0])]
             arr = (C.c_int32 * max(1, len(flat)))(*flat)
             name = _u(p.name)
             keep.append((arr, name))
@@ -133,7 +146,10 @@ class PatternSet:
     def __getitem__(self, i):
         d = tfbs_pattern_desc()
         check(lib().tfbs_patterns_get(self.h, i, C.byref(d)))
-        ws = [Weight(*(d.weights[5 * j + c] for c in range(4))) for j in range(d.length)]
+        if d.kind == KIND_DIPWM:
+            ws = [[d.weights[16 * j + c] for c in range(16)] for j in range(d.length - 1)]
+        else:
+            ws = [Weight(*(d.weights[5 * j + c] for c in range(4))) for j in range(d.length)]
         return Pattern(d.name.decode(), d.pattern_id, ws, d.min_score, d.direction, d.kind)
 
     def to_list(self):
@@ -169,11 +185,26 @@ class PatternSet:
         return {n: getattr(st, n) for n, _ in st._fields_}
 
 
-def parse_pwm_files(pwm_file, threshold_dir, pwm_threshold, wanted_pwms, add_reverse_patterns=True):
-    """pattern.rs:37-87.  Returns a PatternSet (index it or .to_list() for Pattern objects)."""
+    def dinuc_stats(self):
+        """The dinucleotide part of the device plan: dict(n_strands, n_tiles, lut_bytes)."""
+        ns, nt, nb = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        check(lib().tfbs_patterns_dinuc_stats(self.h, C.byref(ns), C.byref(nt), C.byref(nb)))
+        return {"n_strands": ns.value, "n_tiles": nt.value, "lut_bytes": nb.value}
+
+
+def parse_pwm_files(pwm_file, threshold_dir, pwm_threshold, wanted_pwms, add_reverse_patterns=True, dipwm_file=None):
+    """pattern.rs:37-87.  Returns a PatternSet (index it or .to_list() for Pattern objects).
+    dipwm_file: a dinucleotide PWM file (rows of 16 weights, AA AC .. TT) whose pattern ids
+    continue after pwm_file's; pwm_file may then be None."""
     h = C.c_void_p()
-    check(lib().tfbs_patterns_from_files(_u(pwm_file), _u(threshold_dir), pwm_threshold,
-                                         _u(",".join(wanted_pwms)), 1 if add_reverse_patterns else 0, C.byref(h)))
+    if dipwm_file is None:
+        check(lib().tfbs_patterns_from_files(_u(pwm_file), _u(threshold_dir), pwm_threshold,
+                                             _u(",".join(wanted_pwms)), 1 if add_reverse_patterns else 0,
+                                             C.byref(h)))
+    else:
+        check(lib().tfbs_patterns_from_files_di(_u(pwm_file), _u(dipwm_file), _u(threshold_dir), pwm_threshold,
+                                                _u(",".join(wanted_pwms)), 1 if add_reverse_patterns else 0,
+                                                C.byref(h)))
     return PatternSet(h)
 
 
@@ -600,7 +631,7 @@ def select_inner_peaks(merged, beds):
 
 def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_file, pwm_threshold_directory,
         pwm_threshold, wanted_pwms, output_file, forward_only=False, run_tabix=False, min_maf=0, threads=1,
-        after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None):
+        after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None):
     """main.rs:234-393 `run` with the reference's argument order; writes the BGZF VCF.
     devices: list of HIP devices; batch g of merged regions runs on devices[g % n] (same
     text for any list; a device may repeat)."""
@@ -621,6 +652,8 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     a.regions_per_batch = regions_per_batch
     dev = _u(",".join(str(int(d)) for d in devices)) if devices else None
     a.devices = dev
+    di = _u(dipwm_file) if dipwm_file is not None else None
+    a.dipwm_file = di
     check(lib().tfbs_run(C.byref(a)))
 
 

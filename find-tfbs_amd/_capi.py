@@ -50,6 +50,7 @@ class tfbs_run_args(C.Structure):
         ("pwm_names", C.c_char_p), ("output", C.c_char_p), ("pwm_threshold", C.c_float), ("forward_only", C.c_int),
         ("min_maf", C.c_uint32), ("threads", C.c_uint32), ("after_position", C.c_uint64), ("tabix", C.c_int),
         ("verbose", C.c_int), ("device", C.c_int), ("regions_per_batch", C.c_uint32), ("devices", C.c_char_p),
+        ("dipwm_file", C.c_char_p),
     ]
 
 
@@ -60,12 +61,15 @@ SIGNATURES = [
     ("tfbs_version", C.c_char_p, []),
     ("tfbs_patterns_create", C.c_int, [C.POINTER(tfbs_pattern_desc), C.c_size_t, C.POINTER(vp)]),
     ("tfbs_patterns_from_files", C.c_int, [C.c_char_p, C.c_char_p, C.c_float, C.c_char_p, C.c_int, C.POINTER(vp)]),
+    ("tfbs_patterns_from_files_di", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_float, C.c_char_p, C.c_int,
+                                              C.POINTER(vp)]),
     ("tfbs_patterns_count", C.c_size_t, [vp]),
     ("tfbs_patterns_get", C.c_int, [vp, C.c_size_t, C.POINTER(tfbs_pattern_desc)]),
     ("tfbs_patterns_name_of", C.c_char_p, [vp, C.c_uint16]),
     ("tfbs_patterns_max_length", C.c_uint32, [vp]),
     ("tfbs_patterns_destroy", None, [vp]),
     ("tfbs_patterns_plan_stats", C.c_int, [vp, C.c_uint32, C.c_int, C.POINTER(tfbs_plan_stats)]),
+    ("tfbs_patterns_dinuc_stats", C.c_int, [vp, u32p, u32p, u64p]),
     ("tfbs_patterns_mfma_bound", C.c_int, [vp, C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(tfbs_mfma_bound)]),
     ("tfbs_parse_weight", C.c_int, [C.c_char_p, i32p]),
     ("tfbs_parse_threshold_file", C.c_int, [C.c_char_p, C.c_float, i32p]),

@@ -13,10 +13,13 @@ static void usage() {
             "find-tfbs-amd 1.0.1 (MI355X)\nFind patterns in a VCF file\n\n"
             "USAGE: find-tfbs-amd --chromosome CHROM --input IN --output OUT --reference REF --bed BED[,BED..]\n"
             "       --pwm_names N1[,N2..] --pwm_file PWM --pwm_threshold_directory DIR --pwm_threshold T\n"
+            "       [--dipwm_file DIPWM]\n"
             "       [--forward_only] [--threads N] [--min_maf N] [--after_position P] [--samples FILE]\n"
             "       [--tabix] [--verbose] [--device D | --devices D1,D2,.. | --gpus N] [--regions_per_batch N]\n"
             "  --devices: one contiguous block of merged regions per listed HIP device (a device may repeat);\n"
-            "  --gpus N: devices 0..N-1.  The output is the same for any device list.\n");
+            "  --gpus N: devices 0..N-1.  The output is the same for any device list.\n"
+            "  --dipwm_file: dinucleotide PWMs (rows of 16 weights, AA AC .. TT); --pwm_file is then optional\n"
+            "  and --pwm_names selects from both files.\n");
 }
 
 int main(int argc, char **argv) {
@@ -41,6 +44,7 @@ int main(int argc, char **argv) {
         else if (k == "--bed" || k == "-b") a.bed_files = val("--bed");
         else if (k == "--pwm_names" || k == "-n") a.pwm_names = val("--pwm_names");
         else if (k == "--pwm_file" || k == "-p") a.pwm_file = val("--pwm_file");
+        else if (k == "--dipwm_file") a.dipwm_file = val("--dipwm_file");
         else if (k == "--pwm_threshold_directory") a.pwm_threshold_dir = val(k.c_str());
         else if (k == "--pwm_threshold" || k == "-t") {
             a.pwm_threshold = strtof(val(k.c_str()), nullptr);
@@ -80,8 +84,8 @@ int main(int argc, char **argv) {
             return 2;
         }
     }
-    if (!a.chromosome || !a.bcf || !a.output || !a.reference || !a.bed_files || !a.pwm_names || !a.pwm_file ||
-        !a.pwm_threshold_dir || !have_thr) {
+    if (!a.chromosome || !a.bcf || !a.output || !a.reference || !a.bed_files || !a.pwm_names ||
+        (!a.pwm_file && !a.dipwm_file) || !a.pwm_threshold_dir || !have_thr) {
         usage();
         return 2;
     }

@@ -100,6 +100,9 @@ struct tfbs_ctx {
     DevBuf<DevPattern> gen_pats;
     DevBuf<DevTile> fast_tiles, gen_tiles;
     DevBuf<int32_t> lut, wfull, gen_w, m_image, m_weights, m_meta;
+    DevBuf<DevUnit> di_units;  // dinucleotide path (scan_dinuc.hip)
+    DevBuf<DevTile> di_tiles;
+    DevBuf<int32_t> di_lut, di_w;
     DevBuf<uint8_t> slot_mfma;           // Plan::slot_mfma
     DevBuf<uint32_t> cands;              // matrix-core candidate lists (scan.hpp)
     DevBuf<uint32_t> hitl, hitn;         // matrix-core hit lists (scan.hpp)
@@ -662,6 +665,17 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
         if (n < 0) return n;
         launches += n;
     }
+    if (!P.di_tiles.empty()) {
+        ScanArgs d = a;
+        d.tiles = ctx->di_tiles.p;
+        d.n_tiles = (uint32_t)P.di_tiles.size();
+        d.units = ctx->di_units.p;
+        d.lut = ctx->di_lut.p;
+        d.wfull = ctx->di_w.p;
+        const int n = launch_dinuc(d, (size_t)P.max_di_tile_blocks * kDiBlockBytes, n_haps, ctx->stream);
+        if (n < 0) return n;
+        launches += n;
+    }
     return launches;
 }
 
@@ -734,7 +748,7 @@ static AsmArgs asm_args(tfbs_ctx *ctx, const Batch &B, int mode) {
     a.inner = ctx->inner.p;
     a.mmeta = ctx->m_meta.p;
     a.slot_mfma = ctx->slot_mfma.p;
-    a.any_dense = (!ctx->plan.fast_tiles.empty() || !ctx->plan.gen_tiles.empty()) ? 1 : 0;
+    a.any_dense = (!ctx->plan.fast_tiles.empty() || !ctx->plan.gen_tiles.empty() || !ctx->plan.di_tiles.empty()) ? 1 : 0;
     a.n_slots = B.n_slots;
     a.hpb = ctx->mfma_hpb;
     a.hitl = ctx->hitl.p;
@@ -791,6 +805,7 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     }
     ctx->fast_units.release(); ctx->gen_pats.release(); ctx->fast_tiles.release(); ctx->gen_tiles.release();
     ctx->lut.release(); ctx->wfull.release(); ctx->gen_w.release(); ctx->slot_mfma.release();
+    ctx->di_units.release(); ctx->di_tiles.release(); ctx->di_lut.release(); ctx->di_w.release();
     ctx->m_image.release(); ctx->m_weights.release(); ctx->m_meta.release(); ctx->m_supers.release();
     ctx->cands.release(); ctx->hitl.release(); ctx->hitn.release(); ctx->candn.release(); ctx->cand_over.release(); ctx->ref_hits.release();
     ctx->ref_count.release(); ctx->spill.release(); ctx->over.release(); ctx->spill_sorted.release();
@@ -927,7 +942,8 @@ int tfbs_ctx_create(int device, const tfbs_patterns *p, tfbs_ctx **out) {
         tfbs_ctx_destroy(ctx);
         return tfbs::fail(TFBS_E_ARG, "MFMA super tile exceeds the 160 KiB LDS");
     }
-    if ((rc = fast_kernel_set_lds(ctx->cfg))) {
+    if ((rc = fast_kernel_set_lds(ctx->cfg)) ||
+        (rc = dinuc_kernel_set_lds((size_t)P.max_di_tile_blocks * kDiBlockBytes))) {
         tfbs_ctx_destroy(ctx);
         return rc;
     }
@@ -936,7 +952,9 @@ int tfbs_ctx_create(int device, const tfbs_patterns *p, tfbs_ctx **out) {
         (rc = ctx->gen_pats.put(P.gen_pats, ctx->stream)) || (rc = ctx->gen_tiles.put(P.gen_tiles, ctx->stream)) ||
         (rc = ctx->gen_w.put(P.gen_w, ctx->stream)) || (rc = ctx->m_image.put(P.m_image, ctx->stream)) ||
         (rc = ctx->m_weights.put(P.m_weights, ctx->stream)) || (rc = ctx->m_meta.put(P.m_meta, ctx->stream)) ||
-        (rc = ctx->m_supers.put(P.m_supers, ctx->stream)) || (rc = ctx->slot_mfma.put(P.slot_mfma, ctx->stream))) {
+        (rc = ctx->m_supers.put(P.m_supers, ctx->stream)) || (rc = ctx->slot_mfma.put(P.slot_mfma, ctx->stream)) ||
+        (rc = ctx->di_units.put(P.di_units, ctx->stream)) || (rc = ctx->di_tiles.put(P.di_tiles, ctx->stream)) ||
+        (rc = ctx->di_lut.put(P.di_lut, ctx->stream)) || (rc = ctx->di_w.put(P.di_w, ctx->stream))) {
         tfbs_ctx_destroy(ctx);
         return rc;
     }
@@ -1037,7 +1055,7 @@ int tfbs_batch_upload(tfbs_ctx *ctx, tfbs_batch *b) {
         if (rg.hap_count > key_asm_lds_counters()) big += rg.hap_count;
     }
     // dense counts only for the LUT / generic kernels' slots (they store theirs)
-    const bool dense = !ctx->plan.fast_tiles.empty() || !ctx->plan.gen_tiles.empty();
+    const bool dense = !ctx->plan.fast_tiles.empty() || !ctx->plan.gen_tiles.empty() || !ctx->plan.di_tiles.empty();
     int rc;
     if ((rc = ctx->words.put(B.words, ctx->stream)) || (rc = ctx->nmask.put(B.nmask, ctx->stream)) ||
         (rc = ctx->posrel.put(B.posrel, ctx->stream)) || (rc = ctx->haps.put(B.haps, ctx->stream)) ||

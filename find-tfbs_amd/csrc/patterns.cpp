@@ -5,6 +5,8 @@
 // the pattern list into what the scan kernels consume: pattern_id slots, tiles
 // of strands whose 4-mer lookup tables fit the LDS budget, the tables
 // themselves and the per-column A weights used for N correction.
+// Dinucleotide PWMs (TFBS_KIND_DIPWM; no counterpart in the reference) parse
+// from a second file of 16-column rows and plan into plan_dinuc.cpp's tiles.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -132,7 +134,7 @@ int Patterns::slot_order(std::vector<uint16_t> &slot_pid, bool &zero_len_panics)
 
 uint32_t Patterns::max_length() const {
     uint32_t m = 0;
-    for (auto &p : pats) m = std::max<uint32_t>(m, p.kind == TFBS_KIND_PWM ? p.len : 0);
+    for (auto &p : pats) m = std::max<uint32_t>(m, p.kind == TFBS_KIND_PWM || p.kind == TFBS_KIND_DIPWM ? p.len : 0);
     return m;
 }
 
@@ -146,23 +148,28 @@ static std::vector<int32_t> revcomp(const std::vector<int32_t> &w5, uint32_t L) 
     return o;
 }
 
-int parse_pwm_files(const std::string &pwm_file, const std::string &thr_dir, float thr,
-                    const std::vector<std::string> &wanted, bool add_reverse, Patterns *out) {
-    std::map<std::string, int32_t> thresholds;
-    std::string dir = thr_dir;
-    while (!dir.empty() && dir.back() == '/') dir.pop_back();
-    for (auto &name : wanted) {
-        int32_t v;
-        int r = parse_threshold_file(dir + "/" + name + ".thr", thr, &v);
-        if (r < 0) return r;
-        if (r == 1) thresholds[name] = v;
-    }
+// The reverse strand of a dinucleotide PWM: W'[i][4a + b] = W[R-1-i][4(3-b) + (3-a)],
+// so its score on s is the forward strand's on the reverse complement of s.
+static std::vector<int32_t> revcomp_di(const std::vector<int32_t> &w16) {
+    const size_t R = w16.size() / 16;
+    std::vector<int32_t> o(w16.size());
+    for (size_t i = 0; i < R; i++)
+        for (int a = 0; a < 4; a++)
+            for (int b = 0; b < 4; b++) o[16 * i + 4 * a + b] = w16[16 * (R - 1 - i) + 4 * (3 - b) + (3 - a)];
+    return o;
+}
+
+// One definitions file (pattern.rs:37-87): rows of ncol weights (4: a PWM, 16: a
+// dinucleotide PWM), pattern ids from *next_id on.
+static int parse_definitions(const std::string &pwm_file, int ncol, const std::map<std::string, int32_t> &thresholds,
+                             const std::vector<std::string> &wanted, bool add_reverse, uint16_t *next_id,
+                             Patterns *out) {
     std::ifstream in(pwm_file, std::ios::binary);
     if (!in) return fail(TFBS_E_IO, "Could not open file " + pwm_file);
     std::stringstream ss;
     ss << in.rdbuf();
     const std::string content = ss.str();
-    uint16_t pattern_id = 0;
+    uint16_t pattern_id = *next_id;
     size_t start = 0;
     while (start <= content.size()) {
         size_t gt = content.find('>', start);
@@ -181,20 +188,38 @@ int parse_pwm_files(const std::string &pwm_file, const std::string &thr_dir, flo
         }
         if (lines.empty()) return fail(TFBS_E_PARSE, "empty PWM definition");
         const std::string name = lines[0];
-        std::vector<int32_t> w5;
+        std::vector<int32_t> w5, w16;
         for (size_t i = 1; i < lines.size(); i++) {
             auto f = split_ws(lines[i]);
-            if (f.size() != 4) continue;
-            int32_t v[4];
-            for (int k = 0; k < 4; k++) {
+            if (f.size() != (size_t)ncol) continue;
+            int32_t v[16];
+            for (int k = 0; k < ncol; k++) {
                 int rc = parse_weight(f[k], &v[k]);
                 if (rc) return rc;
             }
-            w5.insert(w5.end(), {v[0], v[1], v[2], v[3], 0});
+            if (ncol == 4) w5.insert(w5.end(), {v[0], v[1], v[2], v[3], 0});
+            else w16.insert(w16.end(), v, v + 16);
         }
         if (std::find(wanted.begin(), wanted.end(), name) == wanted.end()) continue;
         auto it = thresholds.find(name);
-        if (it != thresholds.end()) {
+        if (it != thresholds.end() && ncol == 16) {
+            Pat p;
+            p.kind = TFBS_KIND_DIPWM;
+            p.direction = TFBS_DIR_P;
+            p.pattern_id = pattern_id;
+            p.min_score = it->second;
+            p.len = (uint32_t)(w16.size() / 16) + 1;  // bases
+            int rc = check_dipwm_length(p.len, name);
+            if (rc) return rc;
+            p.w16 = w16;
+            p.name = name;
+            out->add(p);
+            if (add_reverse) {
+                p.direction = TFBS_DIR_N;
+                p.w16 = revcomp_di(w16);
+                out->add(p);
+            }
+        } else if (it != thresholds.end()) {
             Pat p;
             p.kind = TFBS_KIND_PWM;
             p.direction = TFBS_DIR_P;
@@ -212,8 +237,33 @@ int parse_pwm_files(const std::string &pwm_file, const std::string &thr_dir, flo
         }
         pattern_id = (uint16_t)(pattern_id + 1);  // pattern.rs:81
     }
+    *next_id = pattern_id;
+    return TFBS_OK;
+}
+
+int parse_pwm_files_di(const std::string *pwm_file, const std::string *dipwm_file, const std::string &thr_dir,
+                       float thr, const std::vector<std::string> &wanted, bool add_reverse, Patterns *out) {
+    std::map<std::string, int32_t> thresholds;
+    std::string dir = thr_dir;
+    while (!dir.empty() && dir.back() == '/') dir.pop_back();
+    for (auto &name : wanted) {
+        int32_t v;
+        int r = parse_threshold_file(dir + "/" + name + ".thr", thr, &v);
+        if (r < 0) return r;
+        if (r == 1) thresholds[name] = v;
+    }
+    uint16_t next_id = 0;
+    int rc = 0;
+    if (pwm_file) rc = parse_definitions(*pwm_file, 4, thresholds, wanted, add_reverse, &next_id, out);
+    if (!rc && dipwm_file) rc = parse_definitions(*dipwm_file, 16, thresholds, wanted, add_reverse, &next_id, out);
+    if (rc) return rc;
     if (out->pats.empty()) return fail(TFBS_E_NOPATTERN, "no pattern loaded");  // main.rs:238
     return TFBS_OK;
+}
+
+int parse_pwm_files(const std::string &pwm_file, const std::string &thr_dir, float thr,
+                    const std::vector<std::string> &wanted, bool add_reverse, Patterns *out) {
+    return parse_pwm_files_di(&pwm_file, nullptr, thr_dir, thr, wanted, add_reverse, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -240,9 +290,14 @@ int Patterns::build_plan(const PlanOptions &opt, Plan *plan) const {
     // Scannable strands: PWM with length >= 1.  A length-0 PWM with a negative
     // min_score panics in the reference at the first region (pattern.rs:150-156
     // reads haplotype[len]); with min_score >= 0 it never matches.
-    std::map<uint16_t, std::vector<int>> by_pid;
+    std::map<uint16_t, std::vector<int>> by_pid, di_by_pid;
+    if (int rc = check_kinds(*this)) return rc;
     for (size_t i = 0; i < pats.size(); i++) {
         const Pat &p = pats[i];
+        if (p.kind == TFBS_KIND_DIPWM) {
+            if (int rc = check_dipwm_length(p.len, p.name)) return rc;
+            di_by_pid[p.pattern_id].push_back((int)i);
+        }
         if (p.kind != TFBS_KIND_PWM) continue;
         if (p.len == 0) {
             if (p.min_score < 0) plan->zero_len_panics = true;
@@ -303,6 +358,27 @@ int Patterns::build_plan(const PlanOptions &opt, Plan *plan) const {
         plan->gen_tiles.push_back(t);
     }
     for (auto &t : plan->fast_tiles) plan->max_tile_blocks = std::max(plan->max_tile_blocks, t.nblocks);
+    // --- dinucleotide strands: slots after every other group's, ordered by (longest
+    // strand, pattern_id); dense counts (slot_mfma 0), scored by scan_dinuc_kernel
+    if (!di_by_pid.empty()) {
+        std::vector<Group> dg;
+        for (auto &kv : di_by_pid) {
+            Group g{kv.first, false, 0, kv.second};
+            for (int i : g.strands) g.maxlen = std::max(g.maxlen, pats[i].len);
+            dg.push_back(std::move(g));
+        }
+        std::stable_sort(dg.begin(), dg.end(), [](const Group &a, const Group &b) {
+            if (a.maxlen != b.maxlen) return a.maxlen < b.maxlen;
+            return a.pid < b.pid;
+        });
+        std::vector<SlotGroup> di;
+        for (auto &g : dg) {
+            di.push_back({(uint32_t)plan->slot_pid.size(), g.strands});
+            plan->slot_pid.push_back(g.pid);
+            plan->slot_mfma.push_back(0);
+        }
+        if (int rc = build_dinuc_tiles(*this, di, plan)) return rc;
+    }
     return TFBS_OK;
 }
 
@@ -355,6 +431,19 @@ int tfbs_parse_threshold_file(const char *path, float thr, int32_t *out) {
     return tfbs::parse_threshold_file(path, thr, out);
 }
 
+static std::vector<std::string> split_names(const char *names_csv) {
+    std::vector<std::string> wanted;
+    std::string s(names_csv);
+    size_t a = 0;
+    for (;;) {  // split(',') keeps empty pieces (main.rs:197)
+        size_t c = s.find(',', a);
+        wanted.push_back(s.substr(a, c == std::string::npos ? std::string::npos : c - a));
+        if (c == std::string::npos) break;
+        a = c + 1;
+    }
+    return wanted;
+}
+
 int tfbs_patterns_create(const tfbs_pattern_desc *d, size_t n, tfbs_patterns **out) {
     if (!out || (n && !d)) return tfbs::fail(TFBS_E_ARG, "null argument");
     auto *ps = new tfbs_patterns();
@@ -364,11 +453,22 @@ int tfbs_patterns_create(const tfbs_pattern_desc *d, size_t n, tfbs_patterns **o
         p.direction = d[i].direction;
         p.pattern_id = d[i].pattern_id;
         p.min_score = d[i].min_score;
-        p.len = d[i].kind == TFBS_KIND_PWM ? d[i].length : 0;
+        p.len = d[i].kind == TFBS_KIND_PWM || d[i].kind == TFBS_KIND_DIPWM ? d[i].length : 0;
         p.name = d[i].name ? d[i].name : "";
-        if (p.kind != TFBS_KIND_PWM && p.kind != TFBS_KIND_OTHER) {
+        if (p.kind != TFBS_KIND_PWM && p.kind != TFBS_KIND_OTHER && p.kind != TFBS_KIND_DIPWM) {
             delete ps;
             return tfbs::fail(TFBS_E_ARG, "unknown pattern kind");
+        }
+        if (p.kind == TFBS_KIND_DIPWM) {  // length bases, (length - 1) x 16 pair weights
+            int rc = tfbs::check_dipwm_length(p.len, p.name);
+            if (!rc && !d[i].weights) rc = tfbs::fail(TFBS_E_ARG, "dinucleotide PWM without weights");
+            if (rc) {
+                delete ps;
+                return rc;
+            }
+            p.w16.assign(d[i].weights, d[i].weights + 16 * (size_t)(p.len - 1));
+            ps->p.add(p);
+            continue;
         }
         if (p.len && !d[i].weights) {
             delete ps;
@@ -381,6 +481,28 @@ int tfbs_patterns_create(const tfbs_pattern_desc *d, size_t n, tfbs_patterns **o
         }
         ps->p.add(p);
     }
+    if (int rc = tfbs::check_kinds(ps->p)) {
+        delete ps;
+        return rc;
+    }
+    *out = ps;
+    return TFBS_OK;
+}
+
+int tfbs_patterns_from_files_di(const char *pwm_file, const char *dipwm_file, const char *thr_dir, float thr,
+                                const char *names_csv, int add_reverse, tfbs_patterns **out) {
+    if ((!pwm_file && !dipwm_file) || !thr_dir || !names_csv || !out)
+        return tfbs::fail(TFBS_E_ARG, "null argument");
+    const std::vector<std::string> wanted = split_names(names_csv);
+    auto *ps = new tfbs_patterns();
+    const std::string mono = pwm_file ? pwm_file : "", di = dipwm_file ? dipwm_file : "";
+    int rc = tfbs::parse_pwm_files_di(pwm_file ? &mono : nullptr, dipwm_file ? &di : nullptr, thr_dir, thr, wanted,
+                                      add_reverse != 0, &ps->p);
+    if (!rc) rc = tfbs::check_kinds(ps->p);
+    if (rc) {
+        delete ps;
+        return rc;
+    }
     *out = ps;
     return TFBS_OK;
 }
@@ -388,15 +510,7 @@ int tfbs_patterns_create(const tfbs_pattern_desc *d, size_t n, tfbs_patterns **o
 int tfbs_patterns_from_files(const char *pwm_file, const char *thr_dir, float thr, const char *names_csv,
                              int add_reverse, tfbs_patterns **out) {
     if (!pwm_file || !thr_dir || !names_csv || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
-    std::vector<std::string> wanted;
-    std::string s(names_csv);
-    size_t a = 0;
-    for (;;) {  // split(',') keeps empty pieces (main.rs:197)
-        size_t c = s.find(',', a);
-        wanted.push_back(s.substr(a, c == std::string::npos ? std::string::npos : c - a));
-        if (c == std::string::npos) break;
-        a = c + 1;
-    }
+    const std::vector<std::string> wanted = split_names(names_csv);
     auto *ps = new tfbs_patterns();
     int rc = tfbs::parse_pwm_files(pwm_file, thr_dir, thr, wanted, add_reverse != 0, &ps->p);
     if (rc) {
@@ -416,7 +530,7 @@ int tfbs_patterns_get(const tfbs_patterns *p, size_t i, tfbs_pattern_desc *out) 
     out->direction = (uint8_t)q.direction;
     out->kind = (uint8_t)q.kind;
     out->length = q.len;
-    out->weights = q.w5.empty() ? nullptr : q.w5.data();
+    out->weights = q.kind == TFBS_KIND_DIPWM ? q.w16.data() : q.w5.empty() ? nullptr : q.w5.data();
     out->min_score = q.min_score;
     out->name = q.name.c_str();
     return TFBS_OK;
@@ -452,6 +566,18 @@ int tfbs_patterns_plan_stats(const tfbs_patterns *p, uint32_t tile_blocks, int m
     out->n_mfma_strands = plan.n_mfma_strands;
     out->n_mfma_tiles = plan.n_mfma_tiles;
     out->n_mfma_supers = (uint32_t)plan.m_supers.size();
+    return TFBS_OK;
+}
+
+int tfbs_patterns_dinuc_stats(const tfbs_patterns *p, uint32_t *n_strands, uint32_t *n_tiles, uint64_t *lut_bytes) {
+    if (!p) return tfbs::fail(TFBS_E_ARG, "null argument");
+    tfbs::Plan plan;
+    tfbs::PlanOptions opt;
+    int rc = p->p.build_plan(opt, &plan);
+    if (rc) return rc;
+    if (n_strands) *n_strands = plan.n_di_strands;
+    if (n_tiles) *n_tiles = (uint32_t)plan.di_tiles.size();
+    if (lut_bytes) *lut_bytes = (uint64_t)plan.di_lut.size() * 4;
     return TFBS_OK;
 }
 

@@ -19,6 +19,9 @@ struct Pat {  // Pattern (types.rs:86-90)
     int32_t min_score = 0;
     uint32_t len = 0;
     std::vector<int32_t> w5;  // len x [A,C,G,T,N=0]
+    // TFBS_KIND_DIPWM: (len - 1) rows of 16 pair weights, index 4 a + b for the
+    // pair (base a, next base b); len counts bases; w5 stays empty
+    std::vector<int32_t> w16;
     std::string name;
 };
 
@@ -43,6 +46,14 @@ struct Plan {
     std::vector<int32_t> m_meta;     // per MFMA tile: kGMetaInts rescoring fields (tfbs_internal.hpp)
     uint32_t max_super_bytes = 0;
     uint32_t n_mfma_strands = 0;
+    // dinucleotide path (plan_dinuc.cpp, scan_dinuc.hip): DevUnit / DevTile as the LUT
+    // path's, lut_off / lut_begin / nblocks in k-mer blocks of kDiBlockBytes
+    std::vector<DevUnit> di_units;
+    std::vector<DevTile> di_tiles;
+    std::vector<int32_t> di_lut;     // blocks x 4^k codes x 4 strands (wrapping int32 partial sums)
+    std::vector<int32_t> di_w;       // per dinucleotide strand row: its 16 exact pair weights (windows containing N)
+    uint32_t max_di_tile_blocks = 0;
+    uint32_t n_di_strands = 0;
     bool zero_len_panics = false;
 };
 
@@ -79,6 +90,13 @@ struct SlotGroup {  // the strands of one pattern_id and its count slot
     std::vector<int> strands;
 };
 void build_fast_tiles(const Patterns &P, const std::vector<SlotGroup> &groups, uint32_t tile_blocks, Plan *plan);
+// Dinucleotide strands (TFBS_KIND_DIPWM) into k-mer lookup tiles; <0 when one
+// pattern_id group alone exceeds the tile's LDS budget.
+int build_dinuc_tiles(const Patterns &P, const std::vector<SlotGroup> &groups, Plan *plan);
+// The limits of a dinucleotide PWM of L bases (2 <= L <= kDiMaxLen), and of a set:
+// the strands of one pattern_id are all dinucleotide or all mononucleotide.
+int check_dipwm_length(uint32_t L, const std::string &name);
+int check_kinds(const Patterns &P);
 // Strands the int8 one-hot formulation scores exactly (L <= 32, every weight
 // splits as 64 a + b with a, b int8).
 bool mfma_eligible(const Pat &p);
@@ -90,6 +108,10 @@ int parse_weight(const std::string &s, int32_t *out);
 int parse_threshold_file(const std::string &path, float thr, int32_t *out);
 int parse_pwm_files(const std::string &pwm_file, const std::string &thr_dir, float thr,
                     const std::vector<std::string> &wanted, bool add_reverse, Patterns *out);
+// The same over a mononucleotide file (rows of 4) and then a dinucleotide file (rows
+// of 16, pattern ids continuing); either path may be null (skipped).
+int parse_pwm_files_di(const std::string *pwm_file, const std::string *dipwm_file, const std::string &thr_dir,
+                       float thr, const std::vector<std::string> &wanted, bool add_reverse, Patterns *out);
 const Patterns &patterns_of(const tfbs_patterns *p);
 
 }  // namespace tfbs

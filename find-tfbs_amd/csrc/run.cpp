@@ -516,8 +516,8 @@ extern "C" {
 
 int tfbs_run(const tfbs_run_args *a) {
     using namespace tfbs;
-    if (!a || !a->chromosome || !a->bcf || !a->bed_files || !a->reference || !a->pwm_file || !a->pwm_threshold_dir ||
-        !a->pwm_names || !a->output)
+    if (!a || !a->chromosome || !a->bcf || !a->bed_files || !a->reference || (!a->pwm_file && !a->dipwm_file) ||
+        !a->pwm_threshold_dir || !a->pwm_names || !a->output)
         return fail(TFBS_E_ARG, "missing required argument");
     RunSetup S;
     S.a = a;
@@ -534,8 +534,10 @@ int tfbs_run(const tfbs_run_args *a) {
     } warm_join{warm};
 
     // patterns (main.rs:237-250)
-    int rc = tfbs_patterns_from_files(a->pwm_file, a->pwm_threshold_dir, a->pwm_threshold, a->pwm_names,
-                                      a->forward_only ? 0 : 1, &S.pp);
+    int rc = a->dipwm_file ? tfbs_patterns_from_files_di(a->pwm_file, a->dipwm_file, a->pwm_threshold_dir,
+                                                         a->pwm_threshold, a->pwm_names, a->forward_only ? 0 : 1, &S.pp)
+                           : tfbs_patterns_from_files(a->pwm_file, a->pwm_threshold_dir, a->pwm_threshold, a->pwm_names,
+                                                      a->forward_only ? 0 : 1, &S.pp);
     if (rc) return rc;
     std::unique_ptr<tfbs_patterns, void (*)(tfbs_patterns *)> pguard(S.pp, tfbs_patterns_destroy);
 

@@ -1,4 +1,4 @@
-// Launch interface of the scan kernels (scan_kernels.hip), used by device.hip.
+// Launch interface of the scan kernels (scan_kernels.hip, scan_dinuc.hip, scan_mfma.hip), used by device.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,10 +13,12 @@ namespace tfbs {
 struct ScanArgs {
     const DevTile *tiles;
     uint32_t n_tiles;
-    const DevUnit *units;       // fast path: units; generic path: unused
+    const DevUnit *units;       // fast and dinucleotide paths: units; generic path: unused
     const DevPattern *gpats;    // generic path
-    const int32_t *lut;         // fast path: 4 KiB table blocks
-    const int32_t *wfull;       // fast path: [A,C,G,T] per column (windows containing N)
+    const int32_t *lut;         // fast path: 4 KiB table blocks; dinucleotide path: k-mer blocks
+    // fast path: [A,C,G,T] per column; dinucleotide path: 16 pair weights per row
+    // (windows containing N)
+    const int32_t *wfull;
     const int32_t *gw;          // generic path: 5 weights per column
     const DevHap *haps;
     uint32_t n_haps;
@@ -133,6 +135,10 @@ int launch_fast(const ScanArgs &a, const LaunchConfig &cfg, uint32_t n_haps, hip
 int launch_generic(const ScanArgs &a, uint32_t n_haps, hipStream_t stream);
 // Opts the fast kernel into more than 64 KiB of dynamic LDS.
 int fast_kernel_set_lds(const LaunchConfig &cfg);
+// Dinucleotide scan (scan_dinuc.hip) over the tiles of plan_dinuc.cpp: dense counts
+// like the fast kernel's; lds_bytes: the largest tile's blocks (dynamic LDS).
+int launch_dinuc(const ScanArgs &a, size_t lds_bytes, uint32_t n_haps, hipStream_t stream);
+int dinuc_kernel_set_lds(size_t lds_bytes);
 // The workgroups of one matrix-core launch: hap groups [g0, g0 + ng) x ns super
 // tiles, workgroup wg_base + (g - g0) ns + super; their hit lists are read back
 // per region by the key assembly (key_kernels.hip).

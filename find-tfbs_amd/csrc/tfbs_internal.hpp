@@ -38,12 +38,35 @@ constexpr int kMaxInnerPass = 8;   // inner ranges handled per pass (accumulator
 constexpr int kMaxTileSlots = 64;  // pattern_id slots per tile: one lane each
 constexpr uint32_t kMaxHapLen = 1u << 26;  // haplotype bases: window starts fit the window lists' 26-bit fields
 
+// Dinucleotide path (scan_dinuc.hip): a lookup block is indexed by the k-mer of bases
+// kDiStride b .. kDiStride b + k - 1 of the window (2 bits per base, first base in the low
+// bits) and returns four strands' partial sums over the k - 1 transitions inside it;
+// consecutive blocks overlap by one base.  k is a build-time choice (3 or 5; DESIGN.md,
+// "scan_dinuc_kernel").
+#ifndef TFBS_DINUC_K
+#define TFBS_DINUC_K 3
+#endif
+constexpr int kDiK = TFBS_DINUC_K;
+static_assert(kDiK == 3 || kDiK == 5, "TFBS_DINUC_K is 3 or 5");
+constexpr int kDiStride = kDiK - 1;             // transitions per lookup
+constexpr int kDiCodes = 1 << (2 * kDiK);
+constexpr int kDiBlockBytes = kDiCodes * 16;    // one ds_read_b128 per lookup
+constexpr int kDiBlockInts = kDiBlockBytes / 4;
+constexpr int kDiMaxLen = 32;                   // bases: the lane's 64-bit window image
+constexpr int kDiMaxBlocks = (kDiMaxLen - 1 + kDiStride - 1) / kDiStride;
+// LDS budget of one tile: at k = 3 two workgroups per CU (what the kernel's registers
+// allow) fit the CU's 160 KiB; one unit of 32-base strands at k = 5 is 8 blocks of
+// 16 KiB, so that build takes one workgroup per CU
+constexpr uint32_t kDiTileBytes = (kDiK == 3 ? 64u : 144u) * 1024u;
+
 enum UnitKind : uint32_t {
     // 8 strands, int16 partial sums biased to <= 0 per block, saturating packed adds:
     // hit iff sum > thr where thr = min_score - sum(block maxima) (exact, see plan)
     UNIT_OCTET16 = 0,
     // 4 strands, int32 partial sums (wrapping like the reference's i32)
     UNIT_QUAD32 = 1,
+    // dinucleotide strands: 4 per unit, int32 partial sums per k-mer block (scan_dinuc.hip)
+    UNIT_DINUC = 2,
 };
 
 // A unit of strands scored together: their 4-mer tables are interleaved so one

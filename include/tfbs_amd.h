@@ -62,6 +62,16 @@ const char *tfbs_version(void);
 /* ------------------------------------------------------------------ */
 #define TFBS_KIND_PWM 0   /* Pattern::PWM */
 #define TFBS_KIND_OTHER 1 /* Pattern::OtherPattern: length 0, never matches */
+/* A dinucleotide PWM (HOCOMOCO's H11DI models; the reference has no counterpart):
+ * L >= 2 bases, R = L - 1 rows of 16 milli-log-odds weights indexed 4 a + b for the
+ * pair (base a, next base b), A=0 C=1 G=2 T=3 (AA, AC, AG, AT, CA, ..., TT).  The
+ * window starting at base i scores sum_{j<R} W[j][4 s[i+j] + s[i+j+1]] (wrapping
+ * int32; a pair holding an N adds 0) and matches iff score > min_score, with the
+ * match range [pos[i], pos[i] + L - 1].  pattern_length is L (bases).  Limits, each
+ * TFBS_E_ARG: L < 2; L > 32; a pattern_id whose strands mix this kind and
+ * TFBS_KIND_PWM; the strands of one pattern_id needing more lookup tables than one
+ * kernel tile holds (64 KiB; four strands of 32 bases take 16 KiB, so 16 such strands). */
+#define TFBS_KIND_DIPWM 2
 #define TFBS_DIR_P 0      /* PWMDirection::P ("+") */
 #define TFBS_DIR_N 1      /* PWMDirection::N ("-") */
 
@@ -69,8 +79,9 @@ typedef struct tfbs_pattern_desc {
     uint16_t pattern_id;    /* shared by both strands of one PWM (pattern.rs:73-77) */
     uint8_t direction;      /* TFBS_DIR_* */
     uint8_t kind;           /* TFBS_KIND_* */
-    uint32_t length;        /* columns (pattern_length, types.rs:92-101) */
-    const int32_t *weights; /* length x 5 ints [A,C,G,T,N]; the N column is ignored (always 0) */
+    uint32_t length;        /* columns (pattern_length, types.rs:92-101); TFBS_KIND_DIPWM: bases L */
+    const int32_t *weights; /* length x 5 ints [A,C,G,T,N]; the N column is ignored (always 0);
+                               TFBS_KIND_DIPWM: (length - 1) x 16 ints */
     int32_t min_score;      /* a window matches iff score > min_score (pattern.rs:151) */
     const char *name;       /* pattern_id -> name (main.rs:239-250) */
 } tfbs_pattern_desc;
@@ -83,6 +94,22 @@ int tfbs_patterns_create(const tfbs_pattern_desc *descs, size_t n, tfbs_patterns
  * add_reverse = !--forward_only.  Fails with TFBS_E_NOPATTERN when nothing loads. */
 int tfbs_patterns_from_files(const char *pwm_file, const char *threshold_dir, float pwm_threshold,
                              const char *names_csv, int add_reverse, tfbs_patterns **out);
+/* The same over a mononucleotide file and a dinucleotide file; either may be NULL.
+ * The mono file's definitions take pattern ids 0..n-1 exactly as above (a
+ * definition named in names_csv takes an id whether or not its threshold loads,
+ * pattern.rs:66-81; one not named takes none); the dinucleotide file's continue
+ * from n under the same rule.  The dinucleotide file has the mono
+ * file's layout: a ">name" line, then one row per transition of 16
+ * whitespace-separated floats in the order AA AC AG AT CA CC ... TT (first base
+ * major), each read by parse_weight; a row whose field count is not 16 is skipped;
+ * a definition of R rows covers R + 1 bases; thresholds come from
+ * <threshold_dir>/<name>.thr as for a PWM.  (The column order and the R = L - 1 row
+ * count were written from memory of HOCOMOCO's dinucleotide files and of SARUS and
+ * have not been checked against a real file: compare with yours before relying on
+ * it.)  add_reverse adds the strand W'[i][4a + b] = W[R-1-i][4(3-b) + (3-a)], whose
+ * score on s is the forward strand's on the reverse complement of s. */
+int tfbs_patterns_from_files_di(const char *pwm_file, const char *dipwm_file, const char *threshold_dir,
+                                float pwm_threshold, const char *names_csv, int add_reverse, tfbs_patterns **out);
 size_t tfbs_patterns_count(const tfbs_patterns *p);
 /* Pointers in *out stay valid while p lives. */
 int tfbs_patterns_get(const tfbs_patterns *p, size_t i, tfbs_pattern_desc *out);
@@ -102,6 +129,9 @@ typedef struct tfbs_plan_stats {
     uint32_t n_mfma_strands, n_mfma_tiles, n_mfma_supers;
 } tfbs_plan_stats;
 int tfbs_patterns_plan_stats(const tfbs_patterns *p, uint32_t tile_blocks, int mfma, tfbs_plan_stats *out);
+/* The dinucleotide part of the plan (scored by its own kernel, never by the matrix
+ * cores): strands, tiles and the bytes of their lookup tables.  Any output may be NULL. */
+int tfbs_patterns_dinuc_stats(const tfbs_patterns *p, uint32_t *n_strands, uint32_t *n_tiles, uint64_t *lut_bytes);
 /* Host-only diagnostic of the matrix-core bound (mfma.cpp) for pattern i and
  * one window of pattern_length bases (0-3 = A,C,G,T, 4 = N): the window's
  * bound digit sum q8 = 8 Q, the strand's threshold t8, its scale and column
@@ -408,6 +438,8 @@ typedef struct tfbs_run_args {
     uint32_t regions_per_batch;    /* merged regions per GPU batch (0 = 512) */
     const char *devices;           /* comma list of HIP devices, one region shard each ("0,1,2,3";
                                       a device may repeat); NULL/"" = just `device` */
+    const char *dipwm_file;        /* --dipwm_file: dinucleotide PWMs (tfbs_patterns_from_files_di), NULL = none;
+                                      pwm_file may be NULL when it is set */
 } tfbs_run_args;
 /* Replaces run() (main.rs:234-393): writes <output>.part, renames it to output.
  * The merged regions go in batches of regions_per_batch (the reference's 50-peak
