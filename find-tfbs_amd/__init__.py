@@ -191,6 +191,18 @@ class PatternSet:
         check(lib().tfbs_patterns_dinuc_stats(self.h, C.byref(ns), C.byref(nt), C.byref(nb)))
         return {"n_strands": ns.value, "n_tiles": nt.value, "lut_bytes": nb.value}
 
+    def dinuc_lut_scores(self, i, windows):
+        """The scores the dinucleotide kernel's lookup loop gives pattern i on `windows`,
+        evaluated on the host from the plan's lookup tables (tfbs_patterns_dinuc_lut_scores).
+        A window is 32 base codes 0-3: the window's bases, then whatever follows them."""
+        n = len(windows)
+        if any(len(w) != 32 for w in windows):
+            raise ValueError("a dinucleotide window image has 32 base codes")
+        flat = (C.c_uint8 * max(1, 32 * n))(*[c for w in windows for c in w])
+        out = (C.c_int32 * max(1, n))()
+        check(lib().tfbs_patterns_dinuc_lut_scores(self.h, i, flat, n, out))
+        return list(out[:n])
+
 
 def parse_pwm_files(pwm_file, threshold_dir, pwm_threshold, wanted_pwms, add_reverse_patterns=True, dipwm_file=None):
     """pattern.rs:37-87.  Returns a PatternSet (index it or .to_list() for Pattern objects).

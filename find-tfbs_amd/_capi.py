@@ -70,6 +70,7 @@ SIGNATURES = [
     ("tfbs_patterns_destroy", None, [vp]),
     ("tfbs_patterns_plan_stats", C.c_int, [vp, C.c_uint32, C.c_int, C.POINTER(tfbs_plan_stats)]),
     ("tfbs_patterns_dinuc_stats", C.c_int, [vp, u32p, u32p, u64p]),
+    ("tfbs_patterns_dinuc_lut_scores", C.c_int, [vp, C.c_size_t, u8p, C.c_size_t, i32p]),
     ("tfbs_patterns_mfma_bound", C.c_int, [vp, C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(tfbs_mfma_bound)]),
     ("tfbs_parse_weight", C.c_int, [C.c_char_p, i32p]),
     ("tfbs_parse_threshold_file", C.c_int, [C.c_char_p, C.c_float, i32p]),

@@ -581,6 +581,18 @@ int tfbs_patterns_dinuc_stats(const tfbs_patterns *p, uint32_t *n_strands, uint3
     return TFBS_OK;
 }
 
+int tfbs_patterns_dinuc_lut_scores(const tfbs_patterns *p, size_t i, const uint8_t *images, size_t n_images,
+                                   int32_t *out_scores) {
+    if (!p || (n_images && (!images || !out_scores))) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (i >= p->p.pats.size() || p->p.pats[i].kind != TFBS_KIND_DIPWM)
+        return tfbs::fail(TFBS_E_ARG, "not the index of a dinucleotide strand");
+    tfbs::Plan plan;
+    tfbs::PlanOptions opt;
+    int rc = p->p.build_plan(opt, &plan);
+    if (rc) return rc;
+    return tfbs::dinuc_lut_scores(plan, (uint32_t)i, images, n_images, out_scores);
+}
+
 int tfbs_patterns_mfma_bound(const tfbs_patterns *p, size_t i, const uint8_t *bases, tfbs_mfma_bound *out) {
     if (!p || !out || (!bases && i < p->p.pats.size() && p->p.pats[i].len))
         return tfbs::fail(TFBS_E_ARG, "null argument");

@@ -93,6 +93,11 @@ void build_fast_tiles(const Patterns &P, const std::vector<SlotGroup> &groups, u
 // Dinucleotide strands (TFBS_KIND_DIPWM) into k-mer lookup tiles; <0 when one
 // pattern_id group alone exceeds the tile's LDS budget.
 int build_dinuc_tiles(const Patterns &P, const std::vector<SlotGroup> &groups, Plan *plan);
+// The scores the kernel's lookup loop gives strand pattern_index (creation order) on
+// n_images images of kDiMaxLen base codes 0-3, read from the plan's tiles, units and
+// tables alone; TFBS_E_ARG when the plan holds no such dinucleotide strand.
+int dinuc_lut_scores(const Plan &plan, uint32_t pattern_index, const uint8_t *images, size_t n_images,
+                     int32_t *out_scores);
 // The limits of a dinucleotide PWM of L bases (2 <= L <= kDiMaxLen), and of a set:
 // the strands of one pattern_id are all dinucleotide or all mononucleotide.
 int check_dipwm_length(uint32_t L, const std::string &name);

@@ -123,7 +123,12 @@ int build_dinuc_tiles(const Patterns &P, const std::vector<SlotGroup> &groups, P
         cur.clear();
         cur_slot.clear();
     };
-    for (const SlotGroup &g : groups) {
+    for (const SlotGroup &g0 : groups) {
+        // a pattern_id's strands longest first: its units then need the fewest blocks (strands of
+        // 4, 4, 7, 31 and 32 bases: 32 31 7 4 | 4, not 4 4 7 31 | 32 -- twice the blocks)
+        SlotGroup g = g0;
+        std::stable_sort(g.strands.begin(), g.strands.end(),
+                         [&](int a, int b) { return P.pats[a].len > P.pats[b].len; });
         if (di_need(P, g.strands) > tile_blocks)
             return fail(TFBS_E_ARG, "the dinucleotide strands of pattern_id " +
                                         std::to_string(P.pats[g.strands[0]].pattern_id) +
@@ -142,6 +147,38 @@ int build_dinuc_tiles(const Patterns &P, const std::vector<SlotGroup> &groups, P
     }
     close_tile();
     return TFBS_OK;
+}
+
+// scan_dinuc.hip's lookup loop (di_chunks) on the host, from the arrays the upload
+// copies: the 64-bit image with the first base in the low bits, per block the code
+// (img >> (2 kDiStride b)) & (kDiCodes - 1), the strand's lane of the 16-byte entry and
+// the wrapping sum over the unit's nblk blocks.  The rows (w16, di_w) are never read.
+int dinuc_lut_scores(const Plan &plan, uint32_t pattern_index, const uint8_t *images, size_t n_images,
+                     int32_t *out_scores) {
+    for (const DevTile &t : plan.di_tiles)
+        for (uint32_t ui = t.first; ui < t.last; ui++) {
+            const DevUnit &U = plan.di_units[ui];
+            for (uint32_t s = 0; s < U.nstrand; s++) {
+                if (U.orig_index[s] != pattern_index) continue;
+                const int32_t *base = plan.di_lut.data() + (size_t)(t.lut_begin + U.lut_off) * kDiBlockInts;
+                for (size_t n = 0; n < n_images; n++) {
+                    uint64_t img = 0;
+                    for (int j = 0; j < kDiMaxLen; j++) {
+                        const uint8_t c = images[(size_t)kDiMaxLen * n + j];
+                        if (c > 3) return fail(TFBS_E_ARG, "image base code above 3");
+                        img |= (uint64_t)c << (2 * j);
+                    }
+                    uint32_t sum = 0;
+                    for (uint32_t b = 0; b < U.nblk; b++) {
+                        const uint32_t code = (uint32_t)(img >> (2 * kDiStride * b)) & (uint32_t)(kDiCodes - 1);
+                        sum += (uint32_t)base[(size_t)b * kDiBlockInts + 4 * code + s];
+                    }
+                    out_scores[n] = (int32_t)sum;
+                }
+                return TFBS_OK;
+            }
+        }
+    return fail(TFBS_E_ARG, "pattern " + std::to_string(pattern_index) + " is not a dinucleotide strand of the plan");
 }
 
 }  // namespace tfbs

@@ -132,6 +132,16 @@ int tfbs_patterns_plan_stats(const tfbs_patterns *p, uint32_t tile_blocks, int m
 /* The dinucleotide part of the plan (scored by its own kernel, never by the matrix
  * cores): strands, tiles and the bytes of their lookup tables.  Any output may be NULL. */
 int tfbs_patterns_dinuc_stats(const tfbs_patterns *p, uint32_t *n_strands, uint32_t *n_tiles, uint64_t *lut_bytes);
+/* Host-only diagnostic of the dinucleotide lookup tables: the scores that the scan
+ * kernel's lookup loop gives pattern i (a TFBS_KIND_DIPWM strand) on n_images images,
+ * evaluated on the host from the plan's tiles, units and tables -- the arrays a device
+ * context uploads -- and never from the pattern's rows.  An image is 32 base codes
+ * (0-3 = A,C,G,T): the window's bases followed by whatever comes after them; the score
+ * of a strand of L bases does not depend on the codes past L.  The plan is built once
+ * per call.  TFBS_E_ARG for a pattern that is not a dinucleotide strand or a code
+ * above 3. */
+int tfbs_patterns_dinuc_lut_scores(const tfbs_patterns *p, size_t i, const uint8_t *images, size_t n_images,
+                                   int32_t *out_scores);
 /* Host-only diagnostic of the matrix-core bound (mfma.cpp) for pattern i and
  * one window of pattern_length bases (0-3 = A,C,G,T, 4 = N): the window's
  * bound digit sum q8 = 8 Q, the strand's threshold t8, its scale and column

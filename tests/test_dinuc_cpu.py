@@ -1,10 +1,12 @@
 """Dinucleotide PWMs (TFBS_KIND_DIPWM) on the host: the ABI round trip, the file
-parser, the limits, the plan part and the invariance of a mono set's plan."""
+parser, the limits, the plan part, the invariance of a mono set's plan, the plan's lookup
+tables against the reference, and the reference-only conditions of the GPU count cases."""
 import os
 import random
 
 import pytest
 
+import dinuc_cases as K
 import dinuc_ref as D
 from helpers import T, synth_patterns
 
@@ -158,3 +160,198 @@ def test_mono_plan_is_invariant_under_an_appended_dipwm(tmp_path, n_pwms, config
         assert plus.plan_stats(mfma=mfma) == mono.plan_stats(mfma=mfma)
     assert plus.to_list()[:len(ml)] == ml
     assert plus.dinuc_stats()["n_strands"] == 2 and mono.dinuc_stats()["n_strands"] == 0
+
+
+# ---------------------------------------------------------------------------------------
+# The plan's lookup tables, evaluated on the host the way the kernel's lookup loop reads
+# them (PatternSet.dinuc_lut_scores), against dinuc_ref.py.  Nothing here knows k.
+# ---------------------------------------------------------------------------------------
+def check_lut(pats, rnd, n_images):
+    """Every strand of the set on n_images random windows, each scored twice with different
+    bases after its L-th: both equal the reference's score of the window."""
+    ps = T.PatternSet.from_patterns(pats)
+    wrapped = 0
+    for i, p in enumerate(pats):
+        L = len(p)
+        wins = [[rnd.randrange(4) for _ in range(L)] for _ in range(n_images)]
+        a = [w + [rnd.randrange(4) for _ in range(32 - L)] for w in wins]
+        b = [w + [3 - c for c in x[L:]] for w, x in zip(wins, a)]  # every base past L differs
+        want = [D.score(p.weights, w, 0) for w in wins]
+        ga, gb = ps.dinuc_lut_scores(i, a), ps.dinuc_lut_scores(i, b)
+        assert ga == want, (i, L, p.pattern_id)
+        assert gb == want, (i, L, p.pattern_id)
+        wrapped += sum(1 for w in wins if not K.INT32_MIN <= K.exact_sum(p.weights, w, 0) <= K.INT32_MAX)
+    return ps, wrapped
+
+
+def test_lut_scores_every_length():
+    """Base lengths 2..32, both strands, in one set (neighbouring lengths share units) and
+    each length alone (a unit padded to two strands)."""
+    rnd = random.Random(11)
+    pats = []
+    for L in range(2, 33):
+        rows = rand_rows(rnd, L)
+        pats += [T.Pattern.DiPWM(rows, "d%d" % L, L, 0, T.DIR_P),
+                 T.Pattern.DiPWM(D.reverse_rows(rows), "d%d" % L, L, 0, T.DIR_N)]
+    check_lut(pats, rnd, 100)
+    for L in range(2, 33):
+        check_lut(pats[2 * (L - 2):2 * (L - 2) + 2], rnd, 10)
+
+
+def test_lut_scores_units_of_mixed_lengths_and_padded_units():
+    """Strands of one pattern_id with lengths (3, 32), (2, 17, 31) and (4, 4, 7, 31, 32): a
+    short strand's blocks past its length read 0 beside a long one's; sets of 1, 2, 3, 5 and
+    6 strands: units padded to 1, 2 or 3 real strands.  (With the five strands cut into units
+    in creation order, 4 4 7 31 | 32, the k = 5 build refused the set: two units of full depth
+    are more than its tile holds.  The planner now packs a pattern_id's strands longest first.)"""
+    rnd = random.Random(12)
+    calib = [rnd.randrange(4) for _ in range(100)]
+    pats = []
+    for pid, lengths in enumerate(((3, 32), (2, 17, 31), (4, 4, 7, 31, 32))):
+        pats += K.strands(rnd, pid, lengths, calib)
+    ps, _ = check_lut(pats, rnd, 60)
+    assert ps.dinuc_stats()["n_strands"] == 10
+    five, rest = pats[5:], sorted(pats[5:], key=len, reverse=True)
+    lut_bytes = lambda ps_: T.PatternSet.from_patterns(ps_).dinuc_stats()["lut_bytes"]
+    assert [len(p) for p in five] == [4, 4, 7, 31, 32]
+    assert lut_bytes(five) == lut_bytes(rest[:4]) + lut_bytes(rest[4:])  # packed as 32 31 7 4 | 4
+    lens = (9, 2, 32, 5, 17, 3)
+    for total in (1, 2, 3, 5, 6):
+        some = [T.Pattern.DiPWM(rand_rows(rnd, lens[k]), "s%d" % k, k // 2, 0, k & 1) for k in range(total)]
+        check_lut(some, rnd, 40)
+
+
+def test_lut_scores_across_tiles_and_the_slot_cap():
+    """70 ids of 2-3 bases (one and two strands) beside 9 two-strand ids of 32: more than the
+    64 slots of a tile."""
+    rnd = random.Random(13)
+    calib = [rnd.randrange(4) for _ in range(100)]
+    pats = []
+    for k in range(70):
+        pats += K.strands(rnd, 100 + k, [(2,), (3, 2), (3,), (2, 2)][k % 4], calib)
+    for k in range(9):
+        pats += K.both_strands(rnd, k, 32, calib)
+    ps, _ = check_lut(pats, rnd, 30)
+    assert ps.dinuc_stats()["n_tiles"] >= 2
+
+
+def test_lut_scores_wrap():
+    """Weights of +-2^30, +-(2^31 - 1) and -2^31 among small ones: the tables' partial sums
+    and the sum over blocks wrap as the specification's int32 sum does."""
+    rnd = random.Random(14)
+    pats = [T.Pattern.DiPWM(K.wrap_rows(rnd, L), "w%d" % k, k, 0) for k, L in enumerate((2, 3, 4, 5, 6, 9, 13, 17, 32))]
+    _, wrapped = check_lut(pats, rnd, 100)
+    assert wrapped >= 100  # windows whose exact sum lies outside int32
+
+
+def test_lut_scores_argument_errors():
+    rnd = random.Random(15)
+    ps = T.PatternSet.from_patterns([T.Pattern.PWM([T.Weight(1, 2, 3, 4)] * 5, "m", 0, 0),
+                                     T.Pattern.DiPWM(rand_rows(rnd, 4), "d", 1, 0)])
+    assert len(ps.dinuc_lut_scores(1, [[0] * 32])) == 1 and ps.dinuc_lut_scores(1, []) == []
+    for i, img in ((0, [0] * 32), (2, [0] * 32), (1, [0] * 31 + [4])):
+        with pytest.raises(T.TfbsError) as e:
+            ps.dinuc_lut_scores(i, [img])
+        assert e.value.code == TFBS_E_ARG
+
+
+# ---------------------------------------------------------------------------------------
+# The cases of test_gpu_dinuc_counts.py (dinuc_cases.py): what makes them bite, checked on
+# the reference alone.
+# ---------------------------------------------------------------------------------------
+def attains_thresholds(case):
+    """Every threshold but INT32_MIN / INT32_MAX is a score of a window of the first region's
+    reference haplotype (the calibration sequence): equality is scanned, and is no hit."""
+    return all(p.min_score in D.scores(p.weights, case["calib"]) for p in case["pats"]
+               if K.INT32_MIN < p.min_score < K.INT32_MAX)
+
+
+def test_cases_every_pattern_id_counts():
+    for case in (K.case_tiles(), K.case_geometry(), K.case_many_haplotypes(), K.case_n_and_indels(),
+                 K.case_reduction(), K.case_all_kernels()):
+        assert K.ids_with_a_key(case["want"]) == {p.pattern_id for p in case["pats"]}
+        assert K.total_hits(case["want"]) >= 100
+        assert attains_thresholds(case)
+    # the wrap case: an id whose threshold is INT32_MAX can have no key; every other id has one
+    case = K.case_wrap()
+    never = {p.pattern_id for p in case["pats"] if p.min_score == K.INT32_MAX}
+    assert len(never) == 5
+    assert K.ids_with_a_key(case["want"]) == {p.pattern_id for p in case["pats"]} - never
+    assert K.total_hits(case["want"]) >= 100
+    for p in case["pats"]:  # attained, or (the fourth threshold of each strand) an attained score minus 1
+        if K.INT32_MIN < p.min_score < K.INT32_MAX:
+            sc = D.scores(p.weights, case["calib"])
+            assert p.min_score in sc or p.min_score + 1 in sc
+
+
+def test_case_tiles_plan():
+    case = K.case_tiles()
+    ps = T.PatternSet.from_patterns(case["pats"])
+    assert ps.dinuc_stats()["n_tiles"] >= 3 and ps.dinuc_stats()["n_strands"] == 122
+    assert all(len(T.select_inner_peaks(r["merged"], case["beds"])) == 3 for r in case["regions"])
+
+
+def test_case_geometry_shapes():
+    case = K.case_geometry()
+    assert tuple(len(r["ref"]) - 2 + 1 for r in case["regions"]) == K.GEOMETRY_WINDOWS
+    assert all(len(set(sq)) >= 3 for sq in case["seqs"])  # several distinct haplotypes in every region
+    assert sum(len(set(sq)) for sq in case["seqs"]) > 128
+    assert len(set(K.case_many_haplotypes()["seqs"][0])) > 128
+
+
+def test_case_n_and_indels_conditions():
+    case = K.case_n_and_indels()
+    st = case["stats"]
+    assert st["with_n"] >= 5 and st["after_indel"] >= 5
+    assert st["n_first"] >= 5 and st["n_last"] >= 5  # N as a hit window's first and as its last base
+    assert st["n_in_indel_haplotype"] >= 5  # N and positions in one haplotype
+    refs = [r["ref"] for r in case["regions"]]
+    assert refs[0][0] == "N" and refs[0][-1] == "N" and "NNN" in refs[0]
+    r1 = case["regions"][1]
+    assert any(len(ref) == 6 and len(alt) == 1 and pos + 5 == r1["ee"] for _, pos, ref, alt, _ in r1["records"])
+    kinds = {(len(ref), len(alt)) for r in case["regions"] for _, _, ref, alt, _ in r["records"]}
+    assert kinds == {(1, 1), (1, 4), (6, 1)}  # SNVs, insertions of 3, deletions of 5
+
+
+def test_case_reduction_shapes_and_row_reconstruction():
+    """Region 0 has 40 inner ranges (more than 32), region 1's doubled range doubles its counts;
+    rebuild_rows reproduces the oracle's own rows from the oracle's keys on the mono set."""
+    case = K.case_reduction()
+    inner = [T.select_inner_peaks(r["merged"], case["beds"]) for r in case["regions"]]
+    assert len(inner[0]) == 41 and len({i[1] for i in inner[0]}) == 1
+    assert len(inner[1]) == 3 and inner[1][0] == inner[1][1]
+    s1, e1 = case["regions"][1]["merged"]
+    once = K.expected_keys(case["pats"], case["n"], [("a.bed", [(s1, e1)])], case["regions"][1], case["seqs"][1])
+    assert once and all(case["want"][1][k] == ([2 * x for x in l], [2 * x for x in r]) for k, (l, r) in once.items())
+    names = {p.pattern_id: p.name for p in case["mono"]}
+    assert case["mono_rows"].count("\n") >= 10
+    assert K.rebuild_rows(case["mono_keys"], case["beds"], names.get) == case["mono_rows"]
+    f = K.case_all_kernels()
+    names = {p.pattern_id: p.name for p in f["mono"]}
+    assert K.rebuild_rows(f["mono_keys"], f["beds"], names.get) == f["mono_rows"]
+
+
+def test_case_wrap_really_wraps():
+    case = K.case_wrap()
+    outside = hit_min = equal = 0
+    for codes, _ in set(case["seqs"][0]):
+        for p in case["pats"]:
+            for i, v in enumerate(D.scores(p.weights, codes)):
+                outside += not K.INT32_MIN <= K.exact_sum(p.weights, codes, i) <= K.INT32_MAX
+                hit_min += p.min_score == K.INT32_MIN and v == K.INT32_MIN  # the one score INT32_MIN rejects
+                equal += v == p.min_score
+    assert outside >= 100 and hit_min >= 1 and equal >= 10
+    assert {p.min_score for p in case["pats"]} >= {K.INT32_MIN, K.INT32_MAX}
+    assert len(case["pats"]) % 4 == 1  # the last unit holds one real strand and three padding strands
+
+
+def test_case_all_kernels_plan():
+    f = K.case_all_kernels()
+    mixed = T.PatternSet.from_patterns(sorted(f["mono"] + f["pats"], key=lambda p: p.pattern_id))
+    st = mixed.plan_stats(mfma=True)
+    assert st["n_mfma_strands"] > 0 and st["n_quad_strands"] > 0 and st["n_generic_strands"] > 0
+    assert mixed.plan_stats(mfma=False)["n_octet_strands"] > 0 and mixed.dinuc_stats()["n_strands"] == 14
+    di, mono = {p.pattern_id for p in f["pats"]}, {p.pattern_id for p in f["mono"]}
+    assert min(di) < min(mono) and any(min(mono) < d < max(mono) for d in di) and max(di) > max(mono)
+    assert sum(sum(l) + sum(r) for k in f["mono_keys"] for l, r in k.values()) >= 100
+    assert {k[2] for ks in f["mono_keys"] for k in ks} == mono
