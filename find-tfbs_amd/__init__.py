@@ -31,6 +31,12 @@ KIND_PWM, KIND_OTHER, KIND_DIPWM = 0, 1, 2
 DIR_P, DIR_N = 0, 1
 NUCLEOTIDES = "ACGTN"  # types.rs:5-8, the weight index order
 
+# tfbs_hit as a numpy dtype (RegionBatch.hits), the hit list TSV's modes and header line
+HIT_DTYPE = [("region", "<u4"), ("haplotype", "<u4"), ("pattern", "<u4"), ("window", "<u4"), ("start", "<u8"),
+             ("end", "<u8"), ("score", "<i4"), ("reserved", "<u4")]
+HITS_MODES = {"all": 0, "diff": 1}
+HITS_HEADER = "#chrom\tregion\thaplotype\tcarriers\tkind\tname\tpattern_id\tstrand\tstart\tend\tscore\tcarrier_ids\n"
+
 Range = namedtuple("Range", "start end")  # range.rs:4-8, inclusive
 NucleotidePos = namedtuple("NucleotidePos", "nuc pos")  # types.rs:23-27 (nuc as 'A'..'N')
 Diff = namedtuple("Diff", "pos reference alternative")  # types.rs:39-44 (strings)
@@ -576,6 +582,69 @@ class RegionBatch:
                 tmp.close()
         return out, fp.value, nr.value, nb.value
 
+    def upload(self, scanner):
+        """tfbs_batch_upload: the packed batch resident on the scanner (what hits() needs)."""
+        check(lib().tfbs_batch_upload(scanner.h, self.h))
+
+    def hits(self, scanner, r0=0, r1=None):
+        """tfbs_batch_hits: find_all_matches (main.rs:94-154) for regions [r0, r1) of this batch,
+        resident on the scanner (after an upload; no scan needed): a numpy structured array
+        (HIT_DTYPE: region, haplotype, pattern, window, start, end, score) sorted by (region,
+        haplotype, pattern, window)."""
+        import numpy as np
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_hits(scanner.h, self.h, r0, self.num_regions if r1 is None else r1, C.byref(p),
+                                    C.byref(n)))
+        try:
+            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_hit)), dtype=HIT_DTYPE).copy()
+        finally:
+            lib().tfbs_free(p)
+        return out
+
+    def hits_count(self, scanner, r0=0, r1=None):
+        """tfbs_batch_hits_count: the hits of each region of [r0, r1) (numpy uint64), count pass only."""
+        import numpy as np
+        r1 = self.num_regions if r1 is None else r1
+        out = np.zeros(max(1, r1 - r0), dtype=np.uint64)
+        check(lib().tfbs_batch_hits_count(scanner.h, self.h, r0, r1, out.ctypes.data_as(_capi.u64p)))
+        return out[:r1 - r0]
+
+    def haplotype(self, region, h):
+        """tfbs_batch_region_haplotype: (codes 0-4, positions, carrier ids' number) of distinct
+        haplotype h of a region, as load_haplotypes made it."""
+        n, car = C.c_size_t(), C.c_uint32()
+        rc = lib().tfbs_batch_region_haplotype(self.h, region, h, None, None, 0, C.byref(n), C.byref(car))
+        if rc != 0 and n.value == 0:
+            check(rc)
+        cap = n.value
+        nucs = (C.c_uint8 * max(1, cap))()
+        pos = (C.c_uint64 * max(1, cap))()
+        check(lib().tfbs_batch_region_haplotype(self.h, region, h, nucs, pos, cap, C.byref(n), C.byref(car)))
+        return tuple(nucs[:cap]), tuple(pos[:cap]), car.value
+
+    def membership(self, region):
+        """tfbs_batch_region_membership: list, [haplotype id 2 * sample + side] -> distinct index."""
+        out = (C.c_uint32 * max(1, 2 * self.n_samples))()
+        check(lib().tfbs_batch_region_membership(self.h, region, out))
+        return list(out[:2 * self.n_samples])
+
+    def hits_tsv(self, hits, chromosome, mode="diff", header=False):
+        """tfbs_batch_hits_tsv: the TSV of a hits() result over whole regions; mode "all" (one
+        `hit` line per hit) or "diff" (every region of the batch: `hap` lines, the baseline's
+        `base` lines, the others' `gain` / `loss` lines); header: HITS_HEADER first."""
+        import numpy as np
+        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_hits_tsv(self.h, hits.ctypes.data_as(C.c_void_p), len(hits), _u(chromosome),
+                                        HITS_MODES[mode], C.byref(p), C.byref(n)))
+        try:
+            text = C.string_at(p, n.value).decode()
+        finally:
+            lib().tfbs_free(p)
+        return (HITS_HEADER if header else "") + text
+
     def rows(self, chromosome, min_maf=0, fake_position=1):
         """Rows for every region (main.rs:415-429); returns (text, next fake_position)."""
         fp = C.c_uint32(fake_position)
@@ -643,10 +712,13 @@ def select_inner_peaks(merged, beds):
 
 def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_file, pwm_threshold_directory,
         pwm_threshold, wanted_pwms, output_file, forward_only=False, run_tabix=False, min_maf=0, threads=1,
-        after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None):
+        after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None,
+        hits_output=None, hits_mode="diff"):
     """main.rs:234-393 `run` with the reference's argument order; writes the BGZF VCF.
     devices: list of HIP devices; batch g of merged regions runs on devices[g % n] (same
-    text for any list; a device may repeat)."""
+    text for any list; a device may repeat).  hits_output: also write every region's hit
+    list there as BGZF TSV (HITS_HEADER, then RegionBatch.hits_tsv's lines in hits_mode "all"
+    or "diff"); the main output does not change."""
     a = _capi.tfbs_run_args()
     keep = [_u(x) if x is not None else None for x in (chromosome, bcf, ",".join(bed_files), reference_genome_file,
                                                         wanted_samples, pwm_file, pwm_threshold_directory,
@@ -666,6 +738,9 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     a.devices = dev
     di = _u(dipwm_file) if dipwm_file is not None else None
     a.dipwm_file = di
+    ho = _u(hits_output) if hits_output is not None else None
+    a.hits_output = ho
+    a.hits_mode = HITS_MODES[hits_mode]
     check(lib().tfbs_run(C.byref(a)))
 
 

@@ -50,8 +50,13 @@ class tfbs_run_args(C.Structure):
         ("pwm_names", C.c_char_p), ("output", C.c_char_p), ("pwm_threshold", C.c_float), ("forward_only", C.c_int),
         ("min_maf", C.c_uint32), ("threads", C.c_uint32), ("after_position", C.c_uint64), ("tabix", C.c_int),
         ("verbose", C.c_int), ("device", C.c_int), ("regions_per_batch", C.c_uint32), ("devices", C.c_char_p),
-        ("dipwm_file", C.c_char_p),
+        ("dipwm_file", C.c_char_p), ("hits_output", C.c_char_p), ("hits_mode", C.c_int),
     ]
+
+
+class tfbs_hit(C.Structure):
+    _fields_ = [("region", C.c_uint32), ("haplotype", C.c_uint32), ("pattern", C.c_uint32), ("window", C.c_uint32),
+                ("start", C.c_uint64), ("end", C.c_uint64), ("score", C.c_int32), ("reserved", C.c_uint32)]
 
 
 # (name, restype, argtypes) for every symbol in include/tfbs_amd.h
@@ -135,6 +140,14 @@ SIGNATURES = [
     ("tfbs_batch_format_rows", C.c_int, [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, u64p,
                                          u64p]),
     ("tfbs_batch_prep_seconds", C.c_int, [vp, C.POINTER(C.c_double)]),
+    ("tfbs_batch_hits", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    ("tfbs_batch_hits_count", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, u64p]),
+    ("tfbs_ctx_last_hits_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
+    ("tfbs_batch_region_haplotype", C.c_int, [vp, C.c_size_t, C.c_uint32, u8p, u64p, C.c_size_t,
+                                              C.POINTER(C.c_size_t), u32p]),
+    ("tfbs_batch_region_membership", C.c_int, [vp, C.c_size_t, u32p]),
+    ("tfbs_batch_hits_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_size_t)]),
     ("tfbs_free", None, [C.c_void_p]),
     ("tfbs_counts_as_genotypes", C.c_int, [u32p, u32p, C.c_size_t, u32p, C.c_char_p, C.c_size_t, C.c_char_p,
                                            C.c_size_t]),

@@ -13,19 +13,24 @@ static void usage() {
             "find-tfbs-amd 1.0.1 (MI355X)\nFind patterns in a VCF file\n\n"
             "USAGE: find-tfbs-amd --chromosome CHROM --input IN --output OUT --reference REF --bed BED[,BED..]\n"
             "       --pwm_names N1[,N2..] --pwm_file PWM --pwm_threshold_directory DIR --pwm_threshold T\n"
-            "       [--dipwm_file DIPWM]\n"
+            "       [--dipwm_file DIPWM] [--hits_output FILE [--hits_mode all|diff]]\n"
             "       [--forward_only] [--threads N] [--min_maf N] [--after_position P] [--samples FILE]\n"
             "       [--tabix] [--verbose] [--device D | --devices D1,D2,.. | --gpus N] [--regions_per_batch N]\n"
             "  --devices: one contiguous block of merged regions per listed HIP device (a device may repeat);\n"
             "  --gpus N: devices 0..N-1.  The output is the same for any device list.\n"
             "  --dipwm_file: dinucleotide PWMs (rows of 16 weights, AA AC .. TT); --pwm_file is then optional\n"
-            "  and --pwm_names selects from both files.\n");
+            "  and --pwm_names selects from both files.\n"
+            "  --hits_output FILE: also write where the sites are, as BGZF TSV: per merged region and distinct\n"
+            "  haplotype its matches (pattern, strand, range, score).  --hits_mode all: one `hit` line per match;\n"
+            "  diff (default): per haplotype a `hap` line with its carrier ids, the most carried haplotype's\n"
+            "  matches as `base` lines, the others' `gain` and `loss` lines against it.  --output is unchanged.\n");
 }
 
 int main(int argc, char **argv) {
     tfbs_run_args a;
     memset(&a, 0, sizeof a);
     a.threads = 1;
+    a.hits_mode = TFBS_HITS_DIFF;
     bool have_thr = false;
     std::string gpus;
     for (int i = 1; i < argc; i++) {
@@ -45,6 +50,15 @@ int main(int argc, char **argv) {
         else if (k == "--pwm_names" || k == "-n") a.pwm_names = val("--pwm_names");
         else if (k == "--pwm_file" || k == "-p") a.pwm_file = val("--pwm_file");
         else if (k == "--dipwm_file") a.dipwm_file = val("--dipwm_file");
+        else if (k == "--hits_output") a.hits_output = val("--hits_output");
+        else if (k == "--hits_mode") {
+            const std::string m = val("--hits_mode");
+            if (m != "all" && m != "diff") {
+                fprintf(stderr, "error: --hits_mode is all or diff\n");
+                return 2;
+            }
+            a.hits_mode = m == "all" ? TFBS_HITS_ALL : TFBS_HITS_DIFF;
+        }
         else if (k == "--pwm_threshold_directory") a.pwm_threshold_dir = val(k.c_str());
         else if (k == "--pwm_threshold" || k == "-t") {
             a.pwm_threshold = strtof(val(k.c_str()), nullptr);

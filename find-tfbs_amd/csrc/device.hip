@@ -23,6 +23,7 @@
 
 #include "batch.hpp"
 #include "bgzf_gpu.hpp"
+#include "hits.hpp"
 #include "patterns.hpp"
 #include "keys.hpp"
 #include "rows.hpp"
@@ -280,6 +281,8 @@ struct tfbs_ctx {
     // fused post-scan (ScanArgs::post_done): tfbs_step allows it for its lean steps
     // (TFBS_POST_FUSE=0: never); post_fused: the last scan did it (its assembly skips the launch)
     bool post_fuse_env = true, post_fuse_ok = false, post_fused = false;
+    // hit lists (tfbs_batch_hits): tables, scratch and timers, made by the first hits call
+    tfbs::HitsState *hits_state = nullptr;
 };
 
 namespace tfbs {
@@ -808,6 +811,8 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     ctx->di_units.release(); ctx->di_tiles.release(); ctx->di_lut.release(); ctx->di_w.release();
     ctx->m_image.release(); ctx->m_weights.release(); ctx->m_meta.release(); ctx->m_supers.release();
     ctx->cands.release(); ctx->hitl.release(); ctx->hitn.release(); ctx->candn.release(); ctx->cand_over.release(); ctx->ref_hits.release();
+    tfbs::hits_state_destroy(ctx->hits_state);
+    ctx->hits_state = nullptr;
     ctx->ref_count.release(); ctx->spill.release(); ctx->over.release(); ctx->spill_sorted.release();
     ctx->spill_bcnt.release(); ctx->spill_boff.release(); ctx->srcs.release();
     if (ctx->over_host) (void)hipHostFree(ctx->over_host);
@@ -2353,6 +2358,41 @@ int tfbs_matches(tfbs_ctx *ctx, const uint8_t *nucs, const uint64_t *pos, size_t
     }
     *n_total = total;
     if (total > cap) return tfbs::fail(TFBS_E_ARG, "output capacity too small");
+    return TFBS_OK;
+}
+
+// Hit lists (scan_hits.hip): the resident image, the ctx's stream, buffers of their own.
+static int hits_call(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, std::vector<tfbs_hit> *out,
+                     uint64_t *per_region) {
+    if (!ctx || !b) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (ctx->resident != b) return tfbs::fail(TFBS_E_STATE, "batch not resident on this ctx (tfbs_batch_upload)");
+    const Batch &B = b->b;
+    if (r0 > r1 || r1 > B.rh.size()) return tfbs::fail(TFBS_E_ARG, "bad region range");
+    if (B.haps.size() != ctx->haps.n) return tfbs::fail(TFBS_E_STATE, "regions added since the upload");
+    const HitsImage img{ctx->haps.p, ctx->words.p, ctx->nmask.p};
+    return hits_run(&ctx->hits_state, ctx->device, ctx->stream, *ctx->pats, img, B, r0, r1, out, per_region);
+}
+
+int tfbs_batch_hits(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_hit **out, size_t *n) {
+    if (!out || !n) return tfbs::fail(TFBS_E_ARG, "null argument");
+    std::vector<tfbs_hit> v;
+    if (int rc = hits_call(ctx, b, r0, r1, &v, nullptr)) return rc;
+    tfbs_hit *p = static_cast<tfbs_hit *>(malloc(std::max<size_t>(1, v.size()) * sizeof(tfbs_hit)));
+    if (!p) return tfbs::fail(TFBS_E_NOMEM, "malloc");
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(tfbs_hit));
+    *out = p;
+    *n = v.size();
+    return TFBS_OK;
+}
+
+int tfbs_batch_hits_count(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, uint64_t *per_region) {
+    if (!per_region && r1 > r0) return tfbs::fail(TFBS_E_ARG, "null argument");
+    return hits_call(ctx, b, r0, r1, nullptr, per_region);
+}
+
+int tfbs_ctx_last_hits_ms(const tfbs_ctx *ctx, double out[4]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    hits_last_ms(ctx->hits_state, out);
     return TFBS_OK;
 }
 

@@ -1,0 +1,66 @@
+// Hit lists (tfbs_batch_hits): the interface of scan_hits.hip to device.hip, and the
+// host-only helpers of hits.cpp.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "batch.hpp"
+#include "patterns.hpp"
+#include "tfbs_internal.hpp"
+
+namespace tfbs {
+
+// One strand of the pattern set in creation order.  w_off: its exact int32 weights in
+// HitTables::weights -- [column][A,C,G,T] for a mono PWM, [row][16] for a dinucleotide
+// PWM (a multiple of 4 ints: 16-byte rows).  len 0: never matches (TFBS_KIND_OTHER).
+struct DevHitStrand {
+    uint32_t kind;
+    uint32_t len;
+    int32_t min_score;
+    uint32_t w_off;
+};
+
+// Built from Patterns alone (never from the Plan).
+struct HitTables {
+    std::vector<DevHitStrand> strands;
+    std::vector<int32_t> weights;
+};
+void build_hit_tables(const Patterns &P, HitTables *out);
+
+// One hit as the fill pass writes it: batch haplotype index, pattern index (creation
+// order), window, score.
+struct DevHitRec {
+    uint32_t hap, pattern, window;
+    int32_t score;
+};
+
+// A ctx's hit-list state (scan_hits.hip): the tables on the device, the scratch and the
+// timers; made by the ctx's first hits call.
+struct HitsState;
+void hits_state_destroy(HitsState *s);
+// The resident batch image as the scan reads it (device pointers).
+struct HitsImage {
+    const DevHap *haps;
+    const uint32_t *words;
+    const uint32_t *nmask;
+};
+// The hit list of regions [r0, r1) of B (resident as img on `device`): appended to *out
+// (sorted as specified), or -- out null -- the count pass alone into per_region[r - r0].
+// *state is made on the first call.  Synchronises `stream` (a hipStream_t; this header
+// is also the host sources', which include no HIP header).
+int hits_run(HitsState **state, int device, void *stream, const Patterns &P, const HitsImage &img,
+             const Batch &B, size_t r0, size_t r1, std::vector<tfbs_hit> *out, uint64_t *per_region);
+// The last hits_run's times (ms): count pass, scan, fill pass (HIP events, summed over
+// the chunks), copy-back + host part (wall).
+void hits_last_ms(const HitsState *s, double out[4]);
+
+// Distinct haplotype h (region-local) of region R as load_haplotypes made it: base codes
+// 0-4 and positions, unpacked from the batch image.
+void region_haplotype(const Batch &B, const RegionH &R, uint32_t h, std::vector<uint8_t> &nucs,
+                      std::vector<uint64_t> &pos);
+// tfbs_batch_hits_tsv's text appended to out (no header line).
+int hits_tsv(const Batch &B, const tfbs_hit *hits, size_t n, const std::string &chrom, int mode, std::string &out);
+
+}  // namespace tfbs

@@ -397,7 +397,7 @@ struct tfbs_patterns {
 
 const char *tfbs_last_error(void) { return tfbs::g_last_error.c_str(); }
 
-const char *tfbs_version(void) { return "find-tfbs_amd 0.1 (gfx950)"; }
+const char *tfbs_version(void) { return "find-tfbs_amd 0.2 (gfx950)"; }
 
 const char *tfbs_strerror(int code) {
     switch (code) {

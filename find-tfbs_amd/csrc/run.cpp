@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "batch.hpp"
+#include "hits.hpp"
 #include "io.hpp"
 #include "patterns.hpp"
 #include "rows.hpp"
@@ -95,8 +96,27 @@ struct Shard {
     double t_setup = 0, t_boot = 0, t_end = 0;  // readers + ctx + grouper; the first batches' stages; flush + ctx release
 };
 
+// --hits_output: the batches' hit list texts (tfbs_batch_hits_tsv) written in batch
+// order by the host BGZF writer, whichever shard hands them in first.
+struct HitsOut {
+    std::mutex mu;
+    tfbs::BgzfWriter w;
+    std::map<size_t, std::string> pending;  // batches past `next`, waiting for their turn
+    size_t next = 0;
+    int rc = TFBS_OK;
+    std::string err;
+    int submit(size_t g, std::string &&text) {
+        std::lock_guard<std::mutex> l(mu);
+        pending[g] = std::move(text);
+        for (auto it = pending.begin(); !rc && it != pending.end() && it->first == next; it = pending.erase(it), next++)
+            if ((rc = w.write(it->second.data(), it->second.size()))) err = tfbs_last_error();
+        return rc ? tfbs::fail(rc, err) : TFBS_OK;
+    }
+};
+
 struct RunSetup {
     const tfbs_run_args *a;
+    HitsOut *hits = nullptr;  // null without --hits_output: the run does nothing more
     std::string chrom;
     tfbs_patterns *pp;
     std::vector<std::pair<std::string, std::vector<std::pair<uint64_t, uint64_t>>>> beds;
@@ -330,6 +350,16 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
         sh.regions += B.rh.size();
         if ((rc = out(g, ctx, bb))) return rc;
         sh.t_rows += now() - t1;
+        if (S.hits) {  // the batch's hit list (its image is still resident), as text, in batch order
+            tfbs_hit *hits = nullptr;
+            size_t nh = 0;
+            if ((rc = tfbs_batch_hits(ctx, bb, 0, B.rh.size(), &hits, &nh))) return rc;
+            std::unique_ptr<tfbs_hit, void (*)(void *)> hguard(hits, free);
+            std::string text;
+            if ((rc = hits_tsv(B, hits, nh, strip_chr(S.chrom), a->hits_mode, text)) ||
+                (rc = S.hits->submit(g, std::move(text))))
+                return rc;
+        }
         if (a->verbose) {
             for (size_t r = 0; r < B.rh.size(); r++)
                 fprintf(stdout, "Peak %zu/%zu\t%llu\t%llu\t%u haplotypes\t%u variants\n", g * S.per_batch + r + 1,
@@ -611,6 +641,16 @@ int tfbs_run(const tfbs_run_args *a) {
     header += "\n";
     rc = w.write(header.data(), header.size());
     if (rc) return rc;
+    HitsOut hits_out;
+    const std::string hits_path = a->hits_output ? a->hits_output : "";
+    if (a->hits_output) {
+        if (a->hits_mode != TFBS_HITS_ALL && a->hits_mode != TFBS_HITS_DIFF)
+            return fail(TFBS_E_ARG, "hits_mode is TFBS_HITS_ALL or TFBS_HITS_DIFF");
+        if ((rc = hits_out.w.open(hits_path + ".part", threads)) ||
+            (rc = hits_out.w.write(TFBS_HITS_HEADER, strlen(TFBS_HITS_HEADER))))
+            return rc;
+        S.hits = &hits_out;
+    }
 
     // shards: batch g of merged regions on device g % n (one device:
     // every batch); rows in merged-peak order, POS counted across the devices
@@ -767,6 +807,11 @@ int tfbs_run(const tfbs_run_args *a) {
     // the reference flushes twice before drop (main.rs:271, 275): two empty blocks
     double t0 = now();
     if ((rc = w.flush()) || (rc = w.flush()) || (rc = w.close())) return rc;
+    if (S.hits) {
+        if ((rc = hits_out.w.close())) return rc;
+        if (rename((hits_path + ".part").c_str(), hits_path.c_str()) != 0)
+            return fail(TFBS_E_IO, "Could not rename " + hits_path + ".part into " + hits_path);
+    }
     const double t_close = now() - t0;
     if (timing)
         for (size_t k = 0; k < n_sh; k++)

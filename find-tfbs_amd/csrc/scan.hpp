@@ -204,6 +204,9 @@ struct ClassTab {
     uint32_t w[33], c[33];
 };
 size_t scan_tmp_words(size_t n);
+// In-place exclusive scan of n u64 values on `stream` (the window lists' offsets, the hit
+// lists' record offsets); tmp: scan_tmp_words(n) words.
+int exclusive_scan(uint64_t *x, uint64_t n, uint64_t *tmp, hipStream_t stream);
 // Per haplotype group of hpb (n_groups): the window tiles of its lists, cost[g] =
 // pairs of class 2 x w[0] + pairs of class 4 x w[1] (w: the per-pair work of each
 // depth class's super tiles), for the scan's workgroup order.

@@ -1,0 +1,466 @@
+// MI355X (gfx950) hit-list kernel: find_all_matches (main.rs:94-154) kept, not counted.
+//
+// For every distinct haplotype h of the asked regions, every strand p of the pattern set
+// (creation order) and every window i with i + L <= len(h), the exact score -- a mono
+// PWM's wrapping int32 column sum, a dinucleotide PWM's wrapping int32 pair sum, an N
+// adding 0 -- is computed from the pattern set's own weights and compared with
+// min_score.  Nothing of the count path is used: no plan, no lookup tables, no window
+// lists, no diff runs, no reuse between haplotypes.  Brute force is the point: the list
+// is a second opinion on the count path at any size.
+//
+//  * A wave owns one (haplotype, strand) pair; its lanes are 64 consecutive windows and
+//    it walks the 64-window chunks in ascending order.  The strand is wave-uniform: a
+//    mono column's four weights come through one scalar load and three selects, a
+//    dinucleotide strand's rows (at most 31 x 16 ints) sit in the wave's LDS slice,
+//    where the 16 entries of a row lie on 16 banks (lanes on one entry broadcast).
+//  * A lane takes the bases of its window 16 at a time: two packed words and two N-mask
+//    words funnel-shifted to the window's phase.  It has up to four chunks' windows in
+//    flight: their words are loaded together and a column's weights are fetched once.
+//  * Two passes run the same scoring code.  The count pass stores each pair's hits; an
+//    exclusive u64 scan over the pairs, haplotype-major, turns them into offsets; the
+//    fill pass places each chunk's hits behind the pair's offset with a ballot and a
+//    popcount prefix.  The order (haplotype, pattern, window) comes out of the offsets:
+//    no atomics, no fixed-capacity list, no sort.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "hits.hpp"
+#include "scan.hpp"
+
+namespace tfbs {
+namespace {
+
+constexpr uint32_t kHitWaves = 4;                       // waves (pairs) per workgroup
+constexpr uint32_t kHitBlock = 64 * kHitWaves;
+constexpr int kHitChunks = 4;                           // 64-window chunks a lane has in flight
+constexpr uint32_t kHitDiInts = (kDiMaxLen - 1) * 16;   // a dinucleotide strand's rows
+constexpr uint64_t kHitsMaxPairs = 1ull << 30;          // pairs per launch: the grid stays below 2^31
+
+typedef const __attribute__((address_space(4))) DevHitStrand CStrand;  // wave-uniform: scalar loads
+struct alignas(16) Col4 {  // one mono column: [A,C,G,T]
+    int32_t x, y, z, w;
+};
+typedef const __attribute__((address_space(4))) Col4 CInt4;
+
+struct HitsArgs {
+    const DevHitStrand *strands;
+    const int32_t *weights;
+    uint32_t n_strands;
+    const DevHap *haps;
+    const uint32_t *words;
+    const uint32_t *nmask;
+    const uint32_t *hap_ids;  // the chunk's haplotypes (batch indices)
+    // pair p = chunk haplotype k * n_strands + strand.  The count pass stores the pair's
+    // hits at off[p]; after the exclusive scan over the chunk's pairs + 1 values, off[p]
+    // is the pair's first record and the last value the chunk's total
+    uint64_t *off;
+    uint32_t k0, k1;      // the haplotypes of the chunk this launch takes
+    uint32_t n_chunk;     // haplotypes in the chunk (count pass: the total's slot is zeroed)
+    // fill pass: record off[p] - rec_base of recs (rec_cap entries)
+    uint64_t rec_base, rec_cap;
+    DevHitRec *recs;
+};
+
+// The 16 bases from base q of a haplotype (2 bits each, base q lowest) and their N bits.
+__device__ __forceinline__ void bases16(const uint32_t *W, const uint32_t *M, uint32_t q, uint32_t &bits,
+                                        uint32_t &nm) {
+    const uint32_t wi = q >> 4;
+    bits = __builtin_amdgcn_alignbit(W[wi + 1], W[wi], 2 * (q & 15));
+    nm = M ? __builtin_amdgcn_alignbit(M[(q >> 5) + 1], M[q >> 5], q & 31) : 0u;
+}
+
+// Wrapping column sums of the windows at bases i[0 .. NCH) (one per 64-window chunk in
+// flight: their words are loaded together, a column's weights once); an N column adds 0.
+template <int NCH>
+__device__ __forceinline__ void score_mono(const uint32_t *W, const uint32_t *M, const uint32_t (&i)[NCH], uint32_t L,
+                                           CInt4 *wq, uint32_t (&s)[NCH]) {
+#pragma unroll
+    for (int c = 0; c < NCH; c++) s[c] = 0;
+    for (uint32_t g = 0; g < L; g += 16) {  // (wave-uniform trip counts)
+        uint32_t bits[NCH], nm[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; c++) bases16(W, M, i[c] + g, bits[c], nm[c]);
+        const uint32_t cnt = min(16u, L - g);
+        for (uint32_t t = 0; t < cnt; t++) {
+            CInt4 &w = wq[g + t];
+            const int32_t wa = w.x, wc = w.y, wg = w.z, wt = w.w;
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                const uint32_t b = bits[c] & 3u;
+                const int32_t v = b == 0 ? wa : b == 1 ? wc : b == 2 ? wg : wt;
+                s[c] += (nm[c] & 1u) ? 0u : (uint32_t)v;
+                bits[c] >>= 2;
+                nm[c] >>= 1;
+            }
+        }
+    }
+}
+
+// Wrapping pair sums of the windows at bases i[0 .. NCH) (L <= 32 bases); a pair holding an
+// N adds 0.
+template <int NCH>
+__device__ __forceinline__ void score_dinuc(const uint32_t *W, const uint32_t *M, const uint32_t (&i)[NCH],
+                                            uint32_t L, const int32_t *rows, uint32_t (&s)[NCH]) {
+    uint32_t prev[NCH], prevn[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) s[c] = 0, prev[c] = 0, prevn[c] = 1;  // (no pair ends on the first base)
+    for (uint32_t g = 0; g < L; g += 16) {
+        uint32_t bits[NCH], nm[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; c++) bases16(W, M, i[c] + g, bits[c], nm[c]);
+        const uint32_t cnt = min(16u, L - g);
+        for (uint32_t t = 0; t < cnt; t++) {
+            const uint32_t j = g + t;  // the pair (base j - 1, base j) is row j - 1
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                const uint32_t b = bits[c] & 3u, n = nm[c] & 1u;
+                const int32_t v = j ? rows[16 * (j - 1) + 4 * prev[c] + b] : 0;
+                s[c] += (n | prevn[c]) ? 0u : (uint32_t)v;
+                prev[c] = b;
+                prevn[c] = n;
+                bits[c] >>= 2;
+                nm[c] >>= 1;
+            }
+        }
+    }
+}
+
+struct HitsPair {  // what a wave knows of its pair (wave-uniform)
+    const uint32_t *W, *M;
+    CInt4 *wq;
+    const int32_t *rows;
+    uint32_t L, nwin, hid, sidx;
+    int32_t min_score;
+    bool di;
+};
+
+// NCH 64-window chunks from window c0, in ascending order: scored together, counted or
+// placed chunk by chunk.
+template <bool FILL, int NCH>
+__device__ __forceinline__ void hits_chunks(const HitsArgs &A, const HitsPair &P, uint32_t c0, uint32_t lane,
+                                            uint64_t &at) {
+    uint32_t ii[NCH], s[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const uint32_t i = c0 + 64 * c + lane;
+        ii[c] = i < P.nwin ? i : 0;  // (window 0 exists: reads stay inside the haplotype's pads)
+    }
+    if (P.di) score_dinuc<NCH>(P.W, P.M, ii, P.L, P.rows, s);
+    else score_mono<NCH>(P.W, P.M, ii, P.L, P.wq, s);
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const uint32_t i = c0 + 64 * c + lane;
+        const bool hit = i < P.nwin && (int32_t)s[c] > P.min_score;
+        const uint64_t mask = __ballot(hit);
+        if (FILL && hit) {
+            const uint32_t rank =
+                __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+            const uint64_t r = at + rank;
+            if (r < A.rec_cap) A.recs[r] = DevHitRec{P.hid, P.sidx, i, (int32_t)s[c]};
+        }
+        at += (uint32_t)__popcll(mask);
+    }
+}
+
+// Grid: ceil((k1 - k0) * n_strands / kHitWaves) workgroups of kHitBlock threads.
+template <bool FILL>
+__global__ __launch_bounds__(kHitBlock) void scan_hits_kernel(HitsArgs A) {
+    __shared__ int32_t s_rows[kHitWaves][kHitDiInts];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t n_pairs = (uint64_t)(A.k1 - A.k0) * A.n_strands;
+    const uint64_t pl = (uint64_t)blockIdx.x * kHitWaves + wave;
+    const bool active = pl < n_pairs;
+    const uint64_t p = (uint64_t)A.k0 * A.n_strands + (active ? pl : n_pairs - 1);
+    const uint32_t k = (uint32_t)(p / A.n_strands);
+    const uint32_t sidx = (uint32_t)(p - (uint64_t)k * A.n_strands);
+    CStrand &S = ((CStrand *)A.strands)[sidx];
+    const uint32_t kind = S.kind, L = S.len, w_off = S.w_off;
+    const int32_t min_score = S.min_score;
+    const bool di = kind == TFBS_KIND_DIPWM;
+    if (di) {  // (L <= kDiMaxLen: check_dipwm_length)
+        const uint32_t n = min((L - 1) * 16, kHitDiInts);
+        for (uint32_t x = lane; x < n; x += 64) s_rows[wave][x] = A.weights[w_off + x];
+    }
+    __syncthreads();
+    if (!active) return;
+    if (!FILL && pl == 0 && lane == 0) A.off[(uint64_t)A.n_chunk * A.n_strands] = 0;  // the total's slot
+    if (FILL && A.off[p + 1] == A.off[p]) return;  // the count pass found no hit: nothing to place
+    const uint32_t hid = A.hap_ids[k];
+    const DevHap hm = A.haps[hid];
+    const bool scored = L != 0 && hm.len >= L && (kind == TFBS_KIND_PWM || di);
+    const uint32_t nwin = scored ? hm.len - L + 1 : 0;
+    const uint32_t *W = A.words + hm.word_off;
+    const uint32_t *M = (hm.flags & HAP_HAS_N) ? A.nmask + hm.nmask_off : nullptr;
+    CInt4 *wq = (CInt4 *)(A.weights + w_off);
+    const HitsPair P{W, M, wq, s_rows[wave], L, nwin, hid, sidx, min_score, di};
+    uint64_t at = FILL ? A.off[p] - A.rec_base : 0;  // records of the pair so far (fill: their place)
+    for (uint32_t c0 = 0; c0 < nwin; c0 += 64 * kHitChunks) {
+        const uint32_t nch = (nwin - c0 + 63) / 64;
+        if (nch >= 3) hits_chunks<FILL, kHitChunks>(A, P, c0, lane, at);  // (a 3-chunk tail scores one chunk of window 0)
+        else if (nch == 2) hits_chunks<FILL, 2>(A, P, c0, lane, at);
+        else hits_chunks<FILL, 1>(A, P, c0, lane, at);
+    }
+    if (!FILL && lane == 0) A.off[p] = at;
+}
+
+// hap_off[k] = off[k * n_strands], k = 0 .. n_haps: the records before chunk haplotype k.
+__global__ __launch_bounds__(256) void hits_hap_offsets_kernel(const uint64_t *__restrict__ off, uint32_t n_haps,
+                                                                uint32_t n_strands, uint64_t *__restrict__ hap_off) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k <= n_haps) hap_off[k] = off[(uint64_t)k * n_strands];
+}
+
+template <typename T>
+struct Buf {  // a device buffer that only grows
+    T *p = nullptr;
+    size_t cap = 0;
+    int ensure(size_t n) {
+        if (n <= cap) return TFBS_OK;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(TFBS_E_HIP, std::string("hipMalloc (hit lists): ") + hipGetErrorString(e));
+        }
+        cap = n;
+        return TFBS_OK;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+#define HITS_TRY(expr)                                                                       \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess) return fail(TFBS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+}  // namespace
+
+void build_hit_tables(const Patterns &P, HitTables *out) {
+    out->strands.clear();
+    out->weights.clear();
+    for (const Pat &p : P.pats) {
+        DevHitStrand s{};
+        s.kind = (uint32_t)p.kind;
+        s.min_score = p.min_score;
+        s.w_off = (uint32_t)out->weights.size();
+        if (p.kind == TFBS_KIND_PWM) {
+            s.len = p.len;
+            for (uint32_t j = 0; j < p.len; j++)
+                for (int c = 0; c < 4; c++) out->weights.push_back(p.w5[5 * (size_t)j + c]);
+        } else if (p.kind == TFBS_KIND_DIPWM) {
+            s.len = p.len;
+            out->weights.insert(out->weights.end(), p.w16.begin(), p.w16.end());
+        } else {
+            s.len = 0;  // TFBS_KIND_OTHER never matches
+        }
+        out->strands.push_back(s);
+    }
+}
+
+struct HitsState {
+    Buf<DevHitStrand> strands;
+    Buf<int32_t> weights;
+    uint32_t n_strands = 0;
+    Buf<uint32_t> hap_ids;
+    Buf<uint64_t> off, tmp, hap_off;
+    Buf<DevHitRec> recs;
+    PinnedBytes host;  // hap_off, then the records, copied back
+    hipEvent_t ev[3] = {};
+    double ms[4] = {0, 0, 0, 0};
+};
+
+void hits_state_destroy(HitsState *s) {
+    if (!s) return;
+    s->strands.release(); s->weights.release(); s->hap_ids.release(); s->off.release(); s->tmp.release();
+    s->hap_off.release(); s->recs.release();
+    for (hipEvent_t e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete s;
+}
+
+void hits_last_ms(const HitsState *s, double out[4]) {
+    for (int k = 0; k < 4; k++) out[k] = s ? s->ms[k] : 0.0;
+}
+
+namespace {
+
+// Scratch of a chunk of nh haplotypes besides its records: the pairs' counters / offsets
+// (u64: the scan works in place), the scan's tile sums, the haplotype list and offsets.
+uint64_t chunk_fixed_bytes(uint64_t nh, uint64_t ns) {
+    const uint64_t np = nh * ns + 1;
+    return 8 * np + 8 * scan_tmp_words(np) + 4 * nh + 8 * (nh + 1);
+}
+
+int first_use(HitsState **state, const Patterns &P, hipStream_t stream) {
+    if (*state) return TFBS_OK;
+    HitsState *s = new HitsState();
+    HitTables T;
+    build_hit_tables(P, &T);
+    s->n_strands = (uint32_t)T.strands.size();
+    int rc;
+    if ((rc = s->strands.ensure(T.strands.size())) || (rc = s->weights.ensure(T.weights.size() + 4))) {
+        hits_state_destroy(s);
+        return rc;
+    }
+    hipError_t e = hipSuccess;
+    if (!T.strands.empty())
+        e = hipMemcpyAsync(s->strands.p, T.strands.data(), T.strands.size() * sizeof(DevHitStrand),
+                           hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && !T.weights.empty())
+        e = hipMemcpyAsync(s->weights.p, T.weights.data(), T.weights.size() * 4, hipMemcpyHostToDevice, stream);
+    for (hipEvent_t &ev : s->ev)
+        if (e == hipSuccess) e = hipEventCreate(&ev);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // (T goes out of scope)
+    if (e != hipSuccess) {
+        hits_state_destroy(s);
+        return fail(TFBS_E_HIP, std::string("hit tables: ") + hipGetErrorString(e));
+    }
+    *state = s;
+    return TFBS_OK;
+}
+
+}  // namespace
+
+int hits_run(HitsState **state, int device, void *stream_, const Patterns &P, const HitsImage &img,
+             const Batch &B, size_t r0, size_t r1, std::vector<tfbs_hit> *out, uint64_t *per_region) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    HITS_TRY(hipSetDevice(device));
+    if (int rc = first_use(state, P, stream)) return rc;
+    HitsState &S = **state;
+    for (double &m : S.ms) m = 0;
+    if (per_region) std::fill(per_region, per_region + (r1 - r0), 0ull);
+    const uint64_t ns = S.n_strands;
+    // the distinct haplotypes of [r0, r1) in order (helper reference copies left out)
+    std::vector<uint32_t> ids;
+    for (size_t r = r0; r < r1; r++)
+        for (uint32_t h = 0; h < B.rh[r].hap_count; h++) ids.push_back(B.rh[r].hap_begin + h);
+    if (ids.empty() || ns == 0) return TFBS_OK;
+    if (ns > kHitsMaxPairs) return fail(TFBS_E_ARG, "too many strands for the hit list kernel");
+    const char *env = getenv("TFBS_HITS_SCRATCH_MB");  // read at the call
+    const double mb = env && *env ? strtod(env, nullptr) : 256.0;  // (fractions of a MiB too)
+    const uint64_t budget = mb > 0 ? (uint64_t)std::min(mb * 1048576.0, 9.0e18) : 0;
+
+    HitsArgs A{};
+    A.strands = S.strands.p;
+    A.weights = S.weights.p;
+    A.n_strands = (uint32_t)ns;
+    A.haps = img.haps;
+    A.words = img.words;
+    A.nmask = img.nmask;
+    int rc;
+    for (size_t start = 0; start < ids.size();) {
+        // the chunk: as many haplotypes as the budget's counters allow, one at least
+        uint64_t nh = std::min<uint64_t>(ids.size() - start, std::max<uint64_t>(1, kHitsMaxPairs / ns));
+        nh = std::min(nh, std::max<uint64_t>(1, budget / (8 * ns + 12)));
+        while (nh > 1 && chunk_fixed_bytes(nh, ns) > budget) nh -= std::max<uint64_t>(1, nh / 1024);
+        const uint64_t fixed = chunk_fixed_bytes(nh, ns);
+        const uint64_t np = nh * ns + 1;
+        if ((rc = S.hap_ids.ensure(nh)) || (rc = S.off.ensure(np)) || (rc = S.tmp.ensure(scan_tmp_words(np))) ||
+            (rc = S.hap_off.ensure(nh + 1)) || (rc = S.host.reserve(8 * (nh + 1))))
+            return rc;
+        HITS_TRY(hipMemcpyAsync(S.hap_ids.p, ids.data() + start, 4 * nh, hipMemcpyHostToDevice, stream));
+        A.hap_ids = S.hap_ids.p;
+        A.off = S.off.p;
+        A.k0 = 0;
+        A.k1 = A.n_chunk = (uint32_t)nh;
+        HITS_TRY(hipEventRecord(S.ev[0], stream));
+        hipLaunchKernelGGL(scan_hits_kernel<false>, dim3((uint32_t)((np - 1 + kHitWaves - 1) / kHitWaves)),
+                           dim3(kHitBlock), 0, stream, A);
+        HITS_TRY(hipGetLastError());
+        HITS_TRY(hipEventRecord(S.ev[1], stream));
+        if ((rc = exclusive_scan(S.off.p, np, S.tmp.p, stream))) return rc;
+        hipLaunchKernelGGL(hits_hap_offsets_kernel, dim3((uint32_t)(nh / 256 + 1)), dim3(256), 0, stream, S.off.p,
+                           (uint32_t)nh, (uint32_t)ns, S.hap_off.p);
+        HITS_TRY(hipGetLastError());
+        HITS_TRY(hipEventRecord(S.ev[2], stream));
+        HITS_TRY(hipEventSynchronize(S.ev[2]));  // (the host part's clock starts when the kernels are done)
+        double t0 = now_ms();
+        HITS_TRY(hipMemcpyAsync(S.host.p, S.hap_off.p, 8 * (nh + 1), hipMemcpyDeviceToHost, stream));
+        HITS_TRY(hipStreamSynchronize(stream));
+        float ms = 0;
+        HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+        S.ms[0] += ms;
+        HITS_TRY(hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
+        S.ms[1] += ms;
+        std::vector<uint64_t> hap_off(nh + 1);
+        memcpy(hap_off.data(), S.host.p, 8 * (nh + 1));
+        if (per_region) {
+            for (uint64_t k = 0; k < nh; k++)
+                per_region[B.haps[ids[start + k]].region - r0] += hap_off[k + 1] - hap_off[k];
+            S.ms[3] += now_ms() - t0;
+            start += nh;
+            continue;
+        }
+        // the records, in runs of whole haplotypes that fit what the counters leave (one at least)
+        const uint64_t room = budget > fixed ? (budget - fixed) / sizeof(DevHitRec) : 0;
+        for (uint64_t k0 = 0; k0 < nh;) {
+            uint64_t k1 = k0 + 1;
+            while (k1 < nh && hap_off[k1 + 1] - hap_off[k0] <= room) k1++;
+            const uint64_t nrec = hap_off[k1] - hap_off[k0];
+            S.ms[3] += now_ms() - t0;
+            if (nrec) {
+                if ((rc = S.recs.ensure(nrec)) || (rc = S.host.reserve(nrec * sizeof(DevHitRec)))) return rc;
+                A.k0 = (uint32_t)k0;
+                A.k1 = (uint32_t)k1;
+                A.rec_base = hap_off[k0];
+                A.rec_cap = nrec;
+                A.recs = S.recs.p;
+                HITS_TRY(hipEventRecord(S.ev[0], stream));
+                hipLaunchKernelGGL(scan_hits_kernel<true>,
+                                   dim3((uint32_t)(((k1 - k0) * ns + kHitWaves - 1) / kHitWaves)), dim3(kHitBlock), 0,
+                                   stream, A);
+                HITS_TRY(hipGetLastError());
+                HITS_TRY(hipEventRecord(S.ev[1], stream));
+                HITS_TRY(hipEventSynchronize(S.ev[1]));
+                t0 = now_ms();
+                HITS_TRY(hipMemcpyAsync(S.host.p, S.recs.p, nrec * sizeof(DevHitRec), hipMemcpyDeviceToHost, stream));
+                HITS_TRY(hipStreamSynchronize(stream));
+                HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+                S.ms[2] += ms;
+                const DevHitRec *rec = reinterpret_cast<const DevHitRec *>(S.host.p);
+                const size_t base = out->size();
+                out->resize(base + nrec);
+                for (uint64_t x = 0; x < nrec; x++) {
+                    const DevHitRec &q = rec[x];
+                    const DevHap &hm = B.haps[q.hap];
+                    const RegionH &R = B.rh[hm.region];
+                    tfbs_hit &o = (*out)[base + x];
+                    o.region = hm.region;
+                    o.haplotype = q.hap - R.hap_begin;
+                    o.pattern = q.pattern;
+                    o.window = q.window;
+                    const int64_t rel = (hm.flags & HAP_HAS_POS) ? B.posrel[hm.pos_off + q.window] : (int64_t)q.window;
+                    o.start = R.es + (uint64_t)rel;
+                    o.end = o.start + P.pats[q.pattern].len - 1;
+                    o.score = q.score;
+                    o.reserved = 0;
+                }
+            } else {
+                t0 = now_ms();
+            }
+            k0 = k1;
+        }
+        S.ms[3] += now_ms() - t0;
+        start += nh;
+    }
+    return TFBS_OK;
+}
+
+}  // namespace tfbs

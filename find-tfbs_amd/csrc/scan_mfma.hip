@@ -1351,6 +1351,8 @@ __global__ __launch_bounds__(256) void scan_add_kernel(uint64_t *__restrict__ x,
     }
 }
 
+}  // namespace
+
 int exclusive_scan(uint64_t *x, uint64_t n, uint64_t *tmp, hipStream_t stream) {
     const uint64_t nt = (n + kScanTile - 1) / kScanTile;
     if (nt == 0) return TFBS_OK;
@@ -1363,6 +1365,8 @@ int exclusive_scan(uint64_t *x, uint64_t n, uint64_t *tmp, hipStream_t stream) {
     if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("scan kernels: ") + hipGetErrorString(e));
     return TFBS_OK;
 }
+
+namespace {
 
 typedef void (*MfmaKernel)(ScanArgs);
 template <int NK> MfmaKernel mfma_nk(bool staged) {

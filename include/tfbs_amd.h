@@ -417,6 +417,72 @@ int tfbs_batch_format_rows(const tfbs_batch *b, const char *chromosome, uint32_t
  * (wall: the prep a BCF reader's records go through) and the whole fill (wall,
  * generation included). */
 int tfbs_batch_prep_seconds(const tfbs_batch *b, double *out);
+/* ------------------------------------------------------------------ */
+/* Hit lists: find_all_matches (main.rs:94-154) kept, not counted        */
+/* ------------------------------------------------------------------ */
+/* One matching site.  For a region of a batch the hit list is every (distinct
+ * haplotype h, pattern strand p, window i) with: h one of the region's n_haplotypes
+ * distinct haplotypes (helper reference copies are not included); p a TFBS_KIND_PWM or
+ * TFBS_KIND_DIPWM strand of L bases (TFBS_KIND_OTHER never matches); i + L <= len(h);
+ * score > min_score.  score is the count path's: the wrapping int32 sum of the columns'
+ * weights (an N column adds 0; any L) or of the pair weights (a pair holding an N adds
+ * 0).  The match range is [pos[i], pos[i] + L - 1] (pattern.rs:157-160); inner ranges
+ * play no part.  Hits are sorted by (region, haplotype, pattern, window). */
+typedef struct tfbs_hit {
+    uint32_t region, haplotype, pattern, window; /* batch region, distinct haplotype of the region,
+                                                    pattern index in creation order, window start (base index) */
+    uint64_t start, end;
+    int32_t score;
+    uint32_t reserved;
+} tfbs_hit;
+
+/* find_all_matches (main.rs:94-154) for regions [r0, r1) of the batch resident on ctx
+ * (after tfbs_batch_upload; needs no scan; leaves every scan / reduce / encode result
+ * and later step untouched).  *out is malloc'd (tfbs_free), sorted as specified.  Its
+ * own kernel (scan_hits.hip) scores every window of every distinct haplotype from the
+ * pattern set alone; the device scratch (counters, offsets and records) of one pass is
+ * bounded by TFBS_HITS_SCRATCH_MB (default 256; at least one haplotype; read at the
+ * call) and the result does not depend on it.  TFBS_E_STATE for a batch not resident. */
+int tfbs_batch_hits(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_hit **out, size_t *n);
+/* The count pass alone: per_region[r - r0]. */
+int tfbs_batch_hits_count(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, uint64_t *per_region);
+/* Device time (ms, HIP events on the ctx stream, summed over the scratch chunks) of the
+ * last tfbs_batch_hits / tfbs_batch_hits_count: out[0] the count pass, out[1] the offset
+ * scan, out[2] the fill pass; out[3] the copy-back and host part (wall ms). */
+int tfbs_ctx_last_hits_ms(const tfbs_ctx *ctx, double out[4]);
+/* Host only.  Distinct haplotype h of a region as load_haplotypes made it
+ * (codes 0-4, NucleotidePos.pos) and its number of carrier ids.
+ * TFBS_E_ARG with *n = the need when cap is short. */
+int tfbs_batch_region_haplotype(const tfbs_batch *b, size_t region, uint32_t h, uint8_t *nucs, uint64_t *pos,
+                                size_t cap, size_t *n, uint32_t *carriers);
+/* Host only.  out[id] = distinct index of haplotype id 2*sample+side (2 * n_samples entries).
+ * Fetches a device-grouped row through region_membership.
+ * TFBS_E_STATE without keep_membership. */
+int tfbs_batch_region_membership(const tfbs_batch *b, size_t region, uint32_t *out);
+/* Host only.  Formats hits (a tfbs_batch_hits result for whole regions) as TSV, one
+ * line per record, tab-separated, under the header
+ *   #chrom region haplotype carriers kind name pattern_id strand start end score carrier_ids
+ * chrom = `chromosome` as given, region = <merged_start>-<merged_end>, haplotype = the
+ * distinct index, carriers = its number of carrier ids, strand + or -.
+ * TFBS_HITS_ALL: one `hit` line per hit in list order, carrier_ids ".".
+ * TFBS_HITS_DIFF (every region of the batch, one without hits included: pass the hits of all of
+ * them): per region the baseline is the distinct haplotype with the most
+ * carrier ids (ties: the one holding the lowest haplotype id).  Each distinct haplotype
+ * in index order writes one `hap` line (pattern fields ".", carrier_ids its ascending
+ * haplotype ids comma-joined, "*" for the baseline, "." without membership), then -- the
+ * baseline -- its hits as `base` lines, or -- any other -- its `gain` lines in (pattern,
+ * window) order and its `loss` lines in (pattern, baseline window) order, a loss carrying
+ * the baseline hit's range and score.  Hits compare as a multiset on (pattern, start,
+ * end): of n_h hits of the haplotype and n_b of the baseline under one key the last
+ * n_h - n_b of the haplotype's in window order are gains, or the last n_b - n_h of the
+ * baseline's are losses; a hit present in both with another score is neither.
+ * The header line is not part of *text (malloc'd, tfbs_free). */
+#define TFBS_HITS_ALL 0
+#define TFBS_HITS_DIFF 1
+#define TFBS_HITS_HEADER "#chrom\tregion\thaplotype\tcarriers\tkind\tname\tpattern_id\tstrand\tstart\tend\tscore\tcarrier_ids\n"
+int tfbs_batch_hits_tsv(const tfbs_batch *b, const tfbs_hit *hits, size_t n, const char *chromosome, int mode,
+                        char **text, size_t *len);
+
 void tfbs_free(void *p);
 
 /* counts_as_genotypes alone (main.rs:439-498): 1 = row (strings written), 0 = no variation. */
@@ -450,6 +516,9 @@ typedef struct tfbs_run_args {
                                       a device may repeat); NULL/"" = just `device` */
     const char *dipwm_file;        /* --dipwm_file: dinucleotide PWMs (tfbs_patterns_from_files_di), NULL = none;
                                       pwm_file may be NULL when it is set */
+    const char *hits_output;       /* --hits_output: the batches' hit lists as BGZF TSV (tfbs_batch_hits_tsv under
+                                      TFBS_HITS_HEADER), NULL = none: the run does nothing more than without it */
+    int hits_mode;                 /* --hits_mode: TFBS_HITS_ALL / TFBS_HITS_DIFF */
 } tfbs_run_args;
 /* Replaces run() (main.rs:234-393): writes <output>.part, renames it to output.
  * The merged regions go in batches of regions_per_batch (the reference's 50-peak
