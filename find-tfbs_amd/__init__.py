@@ -36,6 +36,12 @@ HIT_DTYPE = [("region", "<u4"), ("haplotype", "<u4"), ("pattern", "<u4"), ("wind
              ("end", "<u8"), ("score", "<i4"), ("reserved", "<u4")]
 HITS_MODES = {"all": 0, "diff": 1}
 HITS_HEADER = "#chrom\tregion\thaplotype\tcarriers\tkind\tname\tpattern_id\tstrand\tstart\tend\tscore\tcarrier_ids\n"
+# tfbs_best as a numpy dtype (RegionBatch.best), the best-site TSV's modes and header line
+BEST_DTYPE = [("region", "<u4"), ("haplotype", "<u4"), ("pattern", "<u4"), ("range", "<u4"), ("window", "<u4"),
+              ("n_windows", "<u4"), ("score", "<i4"), ("reserved", "<u4"), ("start", "<u8"), ("end", "<u8")]
+BEST_MODES = {"all": 0, "diff": 1}
+BEST_HEADER = ("#chrom\tregion\tbed\tinner_start\tinner_end\tname\tpattern_id\thaplotype\tcarriers\tkind\tstrand\t"
+               "start\tend\tscore\tdelta\tcarrier_ids\n")
 
 Range = namedtuple("Range", "start end")  # range.rs:4-8, inclusive
 NucleotidePos = namedtuple("NucleotidePos", "nuc pos")  # types.rs:23-27 (nuc as 'A'..'N')
@@ -320,6 +326,12 @@ class Scanner:
 
     def last_scan_ms(self):
         return lib().tfbs_ctx_last_scan_ms(self.h)
+
+    def last_best_ms(self):
+        """tfbs_ctx_last_best_ms: (kernel ms from HIP events, copy-back + host ms) of the last best()."""
+        out = (C.c_double * 2)()
+        check(lib().tfbs_ctx_last_best_ms(self.h, out))
+        return out[0], out[1]
 
 
 def matches(pattern, haplotype, haplotype_ids=(), verbose=False):
@@ -645,6 +657,65 @@ class RegionBatch:
             lib().tfbs_free(p)
         return (HITS_HEADER if header else "") + text
 
+    def best(self, scanner, r0=None, r1=None):
+        """tfbs_batch_best: the best-scoring site per (distinct haplotype, pattern strand, inner
+        range) of regions [r0, r1) of this batch, resident on the scanner (after an upload; no
+        scan needed): a dense numpy structured array (BEST_DTYPE) sorted by (region, haplotype,
+        pattern, range); a region's block reshapes to [n_haplotypes][n_patterns][n_ranges]."""
+        import numpy as np
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_best(scanner.h, self.h, 0 if r0 is None else r0,
+                                    self.num_regions if r1 is None else r1, C.byref(p), C.byref(n)))
+        try:
+            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_best)), dtype=BEST_DTYPE).copy()
+        finally:
+            lib().tfbs_free(p)
+        return out
+
+    def ranges(self, region):
+        """The region's distinct non-empty inner ranges [(start, end)] in ascending order: what
+        a best record's `range` indexes."""
+        n = C.c_size_t()
+        check(lib().tfbs_batch_region_num_ranges(self.h, region, C.byref(n)))
+        out = []
+        for k in range(n.value):
+            s, e = C.c_uint64(), C.c_uint64()
+            check(lib().tfbs_batch_region_range(self.h, region, k, C.byref(s), C.byref(e)))
+            out.append((s.value, e.value))
+        return out
+
+    def best_tsv(self, best, chromosome, mode="diff", header=False):
+        """tfbs_batch_best_tsv: the TSV of a best() result over whole regions; mode "all" (one
+        `best` line per (key, pattern_id, haplotype)) or "diff" (`hap` lines, then `base` and
+        `alt` lines where a haplotype's best differs from the baseline's); header: BEST_HEADER first."""
+        import numpy as np
+        best = np.ascontiguousarray(best, dtype=BEST_DTYPE)
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_best_tsv(self.h, best.ctypes.data_as(C.c_void_p), len(best), _u(chromosome),
+                                        BEST_MODES[mode], C.byref(p), C.byref(n)))
+        try:
+            text = C.string_at(p, n.value).decode()
+        finally:
+            lib().tfbs_free(p)
+        return (BEST_HEADER if header else "") + text
+
+    def best_by_sample(self, best, region):
+        """(scores, n_windows): int32 / uint32 arrays [2 * n_samples][n_patterns][n_ranges] of one
+        region, row id = the records of the distinct haplotype that haplotype id 2 * sample + side
+        carries (membership); `best` must hold that region in full."""
+        import numpy as np
+        mine = best[best["region"] == region]
+        nh, nr = self.region_stats(region)[0], len(self.ranges(region))
+        npat = len(mine) // (nh * nr) if nh * nr else 0
+        if npat * nh * nr != len(mine) or (nh * nr and npat != len(self.patterns)):
+            raise ValueError("best does not hold region %d in full" % region)
+        memb = np.asarray(self.membership(region), dtype=np.int64)
+        scores = mine["score"].reshape(nh, npat, nr)
+        counts = mine["n_windows"].reshape(nh, npat, nr)
+        return scores[memb], counts[memb]
+
     def rows(self, chromosome, min_maf=0, fake_position=1):
         """Rows for every region (main.rs:415-429); returns (text, next fake_position)."""
         fp = C.c_uint32(fake_position)
@@ -713,12 +784,13 @@ def select_inner_peaks(merged, beds):
 def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_file, pwm_threshold_directory,
         pwm_threshold, wanted_pwms, output_file, forward_only=False, run_tabix=False, min_maf=0, threads=1,
         after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None,
-        hits_output=None, hits_mode="diff"):
+        hits_output=None, hits_mode="diff", best_output=None, best_mode="diff"):
     """main.rs:234-393 `run` with the reference's argument order; writes the BGZF VCF.
     devices: list of HIP devices; batch g of merged regions runs on devices[g % n] (same
     text for any list; a device may repeat).  hits_output: also write every region's hit
     list there as BGZF TSV (HITS_HEADER, then RegionBatch.hits_tsv's lines in hits_mode "all"
-    or "diff"); the main output does not change."""
+    or "diff"); best_output: the same for every region's best sites (BEST_HEADER, then
+    RegionBatch.best_tsv's lines in best_mode); the main output does not change."""
     a = _capi.tfbs_run_args()
     keep = [_u(x) if x is not None else None for x in (chromosome, bcf, ",".join(bed_files), reference_genome_file,
                                                         wanted_samples, pwm_file, pwm_threshold_directory,
@@ -741,6 +813,9 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     ho = _u(hits_output) if hits_output is not None else None
     a.hits_output = ho
     a.hits_mode = HITS_MODES[hits_mode]
+    bo = _u(best_output) if best_output is not None else None
+    a.best_output = bo
+    a.best_mode = BEST_MODES[best_mode]
     check(lib().tfbs_run(C.byref(a)))
 
 

@@ -51,12 +51,19 @@ class tfbs_run_args(C.Structure):
         ("min_maf", C.c_uint32), ("threads", C.c_uint32), ("after_position", C.c_uint64), ("tabix", C.c_int),
         ("verbose", C.c_int), ("device", C.c_int), ("regions_per_batch", C.c_uint32), ("devices", C.c_char_p),
         ("dipwm_file", C.c_char_p), ("hits_output", C.c_char_p), ("hits_mode", C.c_int),
+        ("best_output", C.c_char_p), ("best_mode", C.c_int),
     ]
 
 
 class tfbs_hit(C.Structure):
     _fields_ = [("region", C.c_uint32), ("haplotype", C.c_uint32), ("pattern", C.c_uint32), ("window", C.c_uint32),
                 ("start", C.c_uint64), ("end", C.c_uint64), ("score", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class tfbs_best(C.Structure):
+    _fields_ = [("region", C.c_uint32), ("haplotype", C.c_uint32), ("pattern", C.c_uint32), ("range", C.c_uint32),
+                ("window", C.c_uint32), ("n_windows", C.c_uint32), ("score", C.c_int32), ("reserved", C.c_uint32),
+                ("start", C.c_uint64), ("end", C.c_uint64)]
 
 
 # (name, restype, argtypes) for every symbol in include/tfbs_amd.h
@@ -147,6 +154,12 @@ SIGNATURES = [
                                               C.POINTER(C.c_size_t), u32p]),
     ("tfbs_batch_region_membership", C.c_int, [vp, C.c_size_t, u32p]),
     ("tfbs_batch_hits_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.POINTER(C.c_void_p),
+                                      C.POINTER(C.c_size_t)]),
+    ("tfbs_batch_best", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    ("tfbs_batch_region_num_ranges", C.c_int, [vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("tfbs_batch_region_range", C.c_int, [vp, C.c_size_t, C.c_size_t, u64p, u64p]),
+    ("tfbs_ctx_last_best_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
+    ("tfbs_batch_best_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_size_t)]),
     ("tfbs_free", None, [C.c_void_p]),
     ("tfbs_counts_as_genotypes", C.c_int, [u32p, u32p, C.c_size_t, u32p, C.c_char_p, C.c_size_t, C.c_char_p,

@@ -14,6 +14,7 @@ static void usage() {
             "USAGE: find-tfbs-amd --chromosome CHROM --input IN --output OUT --reference REF --bed BED[,BED..]\n"
             "       --pwm_names N1[,N2..] --pwm_file PWM --pwm_threshold_directory DIR --pwm_threshold T\n"
             "       [--dipwm_file DIPWM] [--hits_output FILE [--hits_mode all|diff]]\n"
+            "       [--best_output FILE [--best_mode all|diff]]\n"
             "       [--forward_only] [--threads N] [--min_maf N] [--after_position P] [--samples FILE]\n"
             "       [--tabix] [--verbose] [--device D | --devices D1,D2,.. | --gpus N] [--regions_per_batch N]\n"
             "  --devices: one contiguous block of merged regions per listed HIP device (a device may repeat);\n"
@@ -23,7 +24,11 @@ static void usage() {
             "  --hits_output FILE: also write where the sites are, as BGZF TSV: per merged region and distinct\n"
             "  haplotype its matches (pattern, strand, range, score).  --hits_mode all: one `hit` line per match;\n"
             "  diff (default): per haplotype a `hap` line with its carrier ids, the most carried haplotype's\n"
-            "  matches as `base` lines, the others' `gain` and `loss` lines against it.  --output is unchanged.\n");
+            "  matches as `base` lines, the others' `gain` and `loss` lines against it.  --output is unchanged.\n"
+            "  --best_output FILE: also write how strongly each haplotype binds, as BGZF TSV: per (bed, inner range),\n"
+            "  pattern_id and distinct haplotype the best-scoring site whatever the threshold (strand, range, score).\n"
+            "  --best_mode all: one `best` line each; diff (default): `hap` lines, then where a haplotype's best\n"
+            "  score differs from the most carried haplotype's a `base` line and `alt` lines with the score's delta.\n");
 }
 
 int main(int argc, char **argv) {
@@ -31,6 +36,7 @@ int main(int argc, char **argv) {
     memset(&a, 0, sizeof a);
     a.threads = 1;
     a.hits_mode = TFBS_HITS_DIFF;
+    a.best_mode = TFBS_BEST_DIFF;
     bool have_thr = false;
     std::string gpus;
     for (int i = 1; i < argc; i++) {
@@ -58,6 +64,15 @@ int main(int argc, char **argv) {
                 return 2;
             }
             a.hits_mode = m == "all" ? TFBS_HITS_ALL : TFBS_HITS_DIFF;
+        }
+        else if (k == "--best_output") a.best_output = val("--best_output");
+        else if (k == "--best_mode") {
+            const std::string m = val("--best_mode");
+            if (m != "all" && m != "diff") {
+                fprintf(stderr, "error: --best_mode is all or diff\n");
+                return 2;
+            }
+            a.best_mode = m == "all" ? TFBS_BEST_ALL : TFBS_BEST_DIFF;
         }
         else if (k == "--pwm_threshold_directory") a.pwm_threshold_dir = val(k.c_str());
         else if (k == "--pwm_threshold" || k == "-t") {

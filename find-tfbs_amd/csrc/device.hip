@@ -283,6 +283,8 @@ struct tfbs_ctx {
     bool post_fuse_env = true, post_fuse_ok = false, post_fused = false;
     // hit lists (tfbs_batch_hits): tables, scratch and timers, made by the first hits call
     tfbs::HitsState *hits_state = nullptr;
+    // best sites (tfbs_batch_best): the same, made by the first best call
+    tfbs::BestState *best_state = nullptr;
 };
 
 namespace tfbs {
@@ -813,6 +815,8 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     ctx->cands.release(); ctx->hitl.release(); ctx->hitn.release(); ctx->candn.release(); ctx->cand_over.release(); ctx->ref_hits.release();
     tfbs::hits_state_destroy(ctx->hits_state);
     ctx->hits_state = nullptr;
+    tfbs::best_state_destroy(ctx->best_state);
+    ctx->best_state = nullptr;
     ctx->ref_count.release(); ctx->spill.release(); ctx->over.release(); ctx->spill_sorted.release();
     ctx->spill_bcnt.release(); ctx->spill_boff.release(); ctx->srcs.release();
     if (ctx->over_host) (void)hipHostFree(ctx->over_host);
@@ -2393,6 +2397,30 @@ int tfbs_batch_hits_count(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, ui
 int tfbs_ctx_last_hits_ms(const tfbs_ctx *ctx, double out[4]) {
     if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
     hits_last_ms(ctx->hits_state, out);
+    return TFBS_OK;
+}
+
+// Best sites (scan_best.hip): the resident image, the ctx's stream, buffers of their own.
+int tfbs_batch_best(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_best **out, size_t *n) {
+    if (!ctx || !b || !out || !n) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (ctx->resident != b) return tfbs::fail(TFBS_E_STATE, "batch not resident on this ctx (tfbs_batch_upload)");
+    const Batch &B = b->b;
+    if (r0 > r1 || r1 > B.rh.size()) return tfbs::fail(TFBS_E_ARG, "bad region range");
+    if (B.haps.size() != ctx->haps.n) return tfbs::fail(TFBS_E_STATE, "regions added since the upload");
+    const BestImage img{ctx->haps.p, ctx->words.p, ctx->nmask.p, ctx->posrel.p, ctx->regions.p, ctx->inner.p};
+    std::vector<tfbs_best> v;
+    if (int rc = best_run(&ctx->best_state, ctx->device, ctx->stream, *ctx->pats, img, B, r0, r1, &v)) return rc;
+    tfbs_best *p = static_cast<tfbs_best *>(malloc(std::max<size_t>(1, v.size()) * sizeof(tfbs_best)));
+    if (!p) return tfbs::fail(TFBS_E_NOMEM, "malloc");
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(tfbs_best));
+    *out = p;
+    *n = v.size();
+    return TFBS_OK;
+}
+
+int tfbs_ctx_last_best_ms(const tfbs_ctx *ctx, double out[2]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    best_last_ms(ctx->best_state, out);
     return TFBS_OK;
 }
 

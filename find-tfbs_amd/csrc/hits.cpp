@@ -68,6 +68,37 @@ inline Key key_of(const tfbs_hit &x) { return Key(x.pattern, x.start, x.end); }
 
 }  // namespace
 
+int region_baseline(const Batch &B, const RegionH &R, std::vector<std::vector<uint32_t>> &ids, uint32_t *base) {
+    const uint32_t U = R.hap_count;
+    ids.assign(U, {});
+    if (B.keep_membership && U) {
+        std::vector<uint32_t> memb;
+        if (int rc = dense_membership(B, R, memb)) return rc;
+        for (uint32_t id = 0; id < memb.size(); id++)
+            if (memb[id] < U) ids[memb[id]].push_back(id);
+    }
+    // the baseline: most carrier ids, ties to the haplotype holding the lowest id
+    uint32_t b = 0;
+    auto low = [&](uint32_t h) { return ids[h].empty() ? UINT32_MAX : ids[h][0]; };
+    for (uint32_t h = 1; h < U; h++) {
+        const uint32_t ch = B.hap_carriers[R.hap_begin + h], cb = B.hap_carriers[R.hap_begin + b];
+        if (ch > cb || (ch == cb && low(h) < low(b))) b = h;
+    }
+    *base = b;
+    return TFBS_OK;
+}
+
+std::string carrier_id_text(const Batch &B, const std::vector<std::vector<uint32_t>> &ids, uint32_t h, uint32_t base) {
+    if (h == base) return "*";
+    if (!B.keep_membership) return ".";
+    std::string out;
+    for (size_t k = 0; k < ids[h].size(); k++) {
+        if (k) out += ',';
+        out += std::to_string(ids[h][k]);
+    }
+    return out;
+}
+
 int hits_tsv(const Batch &B, const tfbs_hit *hits, size_t n, const std::string &chrom, int mode, std::string &out) {
     const Patterns &P = *B.pats;
     for (size_t i = 0; i < n; i++) {
@@ -90,7 +121,6 @@ int hits_tsv(const Batch &B, const tfbs_hit *hits, size_t n, const std::string &
     }
     if (mode != TFBS_HITS_DIFF) return fail(TFBS_E_ARG, "hits mode is TFBS_HITS_ALL or TFBS_HITS_DIFF");
     size_t at = 0;
-    std::vector<uint32_t> memb;
     for (size_t r = 0; r < B.rh.size(); r++) {
         const RegionH &R = B.rh[r];
         set_region(R);
@@ -103,34 +133,15 @@ int hits_tsv(const Batch &B, const tfbs_hit *hits, size_t n, const std::string &
         }
         first[U] = at;
         if (at < n && hits[at].region == r) return fail(TFBS_E_ARG, "hits not sorted by (region, haplotype, pattern, window)");
-        std::vector<std::vector<uint32_t>> ids(U);
-        if (B.keep_membership && U) {
-            if (int rc = dense_membership(B, R, memb)) return rc;
-            for (uint32_t id = 0; id < memb.size(); id++)
-                if (memb[id] < U) ids[memb[id]].push_back(id);
-        }
-        // the baseline: most carrier ids, ties to the haplotype holding the lowest id
+        std::vector<std::vector<uint32_t>> ids;
         uint32_t base = 0;
-        auto low = [&](uint32_t h) { return ids[h].empty() ? UINT32_MAX : ids[h][0]; };
-        for (uint32_t h = 1; h < U; h++) {
-            const uint32_t ch = B.hap_carriers[R.hap_begin + h], cb = B.hap_carriers[R.hap_begin + base];
-            if (ch > cb || (ch == cb && low(h) < low(base))) base = h;
-        }
+        if (int rc = region_baseline(B, R, ids, &base)) return rc;
         std::map<Key, uint32_t> nb;  // the baseline's hits per key
         if (U)
             for (size_t i = first[base]; i < first[base + 1]; i++) nb[key_of(hits[i])]++;
-        std::string idtext;
         for (uint32_t h = 0; h < U; h++) {
             const uint32_t car = B.hap_carriers[R.hap_begin + h];
-            idtext.clear();
-            if (h == base) idtext = "*";
-            else if (!B.keep_membership) idtext = ".";
-            else
-                for (size_t k = 0; k < ids[h].size(); k++) {
-                    if (k) idtext += ',';
-                    idtext += std::to_string(ids[h][k]);
-                }
-            L.hap(h, car, idtext);
+            L.hap(h, car, carrier_id_text(B, ids, h, base));
             if (h == base) {
                 for (size_t i = first[h]; i < first[h + 1]; i++) L.hit(h, car, "base", P.pats[hits[i].pattern], hits[i]);
                 continue;

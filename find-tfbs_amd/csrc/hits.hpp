@@ -1,5 +1,6 @@
-// Hit lists (tfbs_batch_hits): the interface of scan_hits.hip to device.hip, and the
-// host-only helpers of hits.cpp.
+// Hit lists (tfbs_batch_hits) and best sites (tfbs_batch_best): the interfaces of
+// scan_hits.hip and scan_best.hip to device.hip, and the host-only helpers of hits.cpp
+// and best.cpp.
 #pragma once
 
 #include <cstdint>
@@ -62,5 +63,38 @@ void region_haplotype(const Batch &B, const RegionH &R, uint32_t h, std::vector<
                       std::vector<uint64_t> &pos);
 // tfbs_batch_hits_tsv's text appended to out (no header line).
 int hits_tsv(const Batch &B, const tfbs_hit *hits, size_t n, const std::string &chrom, int mode, std::string &out);
+// The diff modes' baseline of a region (hits.cpp): ids[h] = the ascending haplotype ids of
+// distinct haplotype h (empty without membership), *base = the haplotype with the most
+// carrier ids, ties to the one holding the lowest id (0 for a region without haplotypes).
+int region_baseline(const Batch &B, const RegionH &R, std::vector<std::vector<uint32_t>> &ids, uint32_t *base);
+// A `hap` line's carrier_ids column: "*" for the baseline, "." without membership.
+std::string carrier_id_text(const Batch &B, const std::vector<std::vector<uint32_t>> &ids, uint32_t h, uint32_t base);
+
+// ---- best sites (tfbs_batch_best): scan_best.hip's interface to device.hip, best.cpp's formatter
+// One (haplotype, strand, range) as the kernel writes it: 16 bytes, one vector store.
+struct alignas(16) DevBestRec {
+    int32_t score;
+    uint32_t window, n_windows, zero;
+};
+struct BestState;
+void best_state_destroy(BestState *s);
+// The resident batch image as the best kernel reads it (device pointers).
+struct BestImage {
+    const DevHap *haps;
+    const uint32_t *words;
+    const uint32_t *nmask;
+    const int32_t *posrel;
+    const DevRegion *regions;
+    const int32_t *inner;
+};
+// The dense best records of regions [r0, r1) of B (resident as img on `device`) appended to
+// *out, sorted by (region, haplotype, pattern, range).  *state is made on the first call.
+// Synchronises `stream` (a hipStream_t).
+int best_run(BestState **state, int device, void *stream, const Patterns &P, const BestImage &img, const Batch &B,
+             size_t r0, size_t r1, std::vector<tfbs_best> *out);
+// The last best_run's times (ms): the kernel (HIP events, summed over the chunks), copy-back + host part (wall).
+void best_last_ms(const BestState *s, double out[2]);
+// tfbs_batch_best_tsv's text appended to out (no header line); the records are whole regions.
+int best_tsv(const Batch &B, const tfbs_best *best, size_t n, const std::string &chrom, int mode, std::string &out);
 
 }  // namespace tfbs

@@ -96,8 +96,8 @@ struct Shard {
     double t_setup = 0, t_boot = 0, t_end = 0;  // readers + ctx + grouper; the first batches' stages; flush + ctx release
 };
 
-// --hits_output: the batches' hit list texts (tfbs_batch_hits_tsv) written in batch
-// order by the host BGZF writer, whichever shard hands them in first.
+// --hits_output, --best_output: the batches' texts (tfbs_batch_hits_tsv, tfbs_batch_best_tsv)
+// written in batch order by the host BGZF writer, whichever shard hands them in first.
 struct HitsOut {
     std::mutex mu;
     tfbs::BgzfWriter w;
@@ -114,9 +114,14 @@ struct HitsOut {
     }
 };
 
+// Best records (48 bytes each) the run flow holds at once: whole regions up to this many, one
+// region at least (the text does not depend on the split: tfbs_batch_best_tsv takes whole regions).
+constexpr size_t kBestRunRecords = 1u << 20;
+
 struct RunSetup {
     const tfbs_run_args *a;
     HitsOut *hits = nullptr;  // null without --hits_output: the run does nothing more
+    HitsOut *best = nullptr;  // null without --best_output: the same
     std::string chrom;
     tfbs_patterns *pp;
     std::vector<std::pair<std::string, std::vector<std::pair<uint64_t, uint64_t>>>> beds;
@@ -359,6 +364,22 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
             if ((rc = hits_tsv(B, hits, nh, strip_chr(S.chrom), a->hits_mode, text)) ||
                 (rc = S.hits->submit(g, std::move(text))))
                 return rc;
+        }
+        if (S.best) {  // the batch's best sites: dense records, so a bounded number of whole regions at a time
+            std::string text;
+            const size_t np = B.pats->pats.size();
+            auto records_of = [&](size_t r) { return (size_t)B.rh[r].hap_count * np * B.rh[r].ranges.size(); };
+            for (size_t q0 = 0; q0 < B.rh.size();) {
+                size_t q1 = q0 + 1, recs = records_of(q0);  // regions [q0, q1): one at least
+                while (q1 < B.rh.size() && recs + records_of(q1) <= kBestRunRecords) recs += records_of(q1++);
+                tfbs_best *best = nullptr;
+                size_t nbest = 0;
+                if ((rc = tfbs_batch_best(ctx, bb, q0, q1, &best, &nbest))) return rc;
+                std::unique_ptr<tfbs_best, void (*)(void *)> bguard(best, free);
+                if ((rc = best_tsv(B, best, nbest, strip_chr(S.chrom), a->best_mode, text))) return rc;
+                q0 = q1;
+            }
+            if ((rc = S.best->submit(g, std::move(text)))) return rc;
         }
         if (a->verbose) {
             for (size_t r = 0; r < B.rh.size(); r++)
@@ -651,6 +672,16 @@ int tfbs_run(const tfbs_run_args *a) {
             return rc;
         S.hits = &hits_out;
     }
+    HitsOut best_out;
+    const std::string best_path = a->best_output ? a->best_output : "";
+    if (a->best_output) {
+        if (a->best_mode != TFBS_BEST_ALL && a->best_mode != TFBS_BEST_DIFF)
+            return fail(TFBS_E_ARG, "best_mode is TFBS_BEST_ALL or TFBS_BEST_DIFF");
+        if ((rc = best_out.w.open(best_path + ".part", threads)) ||
+            (rc = best_out.w.write(TFBS_BEST_HEADER, strlen(TFBS_BEST_HEADER))))
+            return rc;
+        S.best = &best_out;
+    }
 
     // shards: batch g of merged regions on device g % n (one device:
     // every batch); rows in merged-peak order, POS counted across the devices
@@ -811,6 +842,11 @@ int tfbs_run(const tfbs_run_args *a) {
         if ((rc = hits_out.w.close())) return rc;
         if (rename((hits_path + ".part").c_str(), hits_path.c_str()) != 0)
             return fail(TFBS_E_IO, "Could not rename " + hits_path + ".part into " + hits_path);
+    }
+    if (S.best) {
+        if ((rc = best_out.w.close())) return rc;
+        if (rename((best_path + ".part").c_str(), best_path.c_str()) != 0)
+            return fail(TFBS_E_IO, "Could not rename " + best_path + ".part into " + best_path);
     }
     const double t_close = now() - t0;
     if (timing)

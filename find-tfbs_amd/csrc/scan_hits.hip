@@ -15,7 +15,8 @@
 //    where the 16 entries of a row lie on 16 banks (lanes on one entry broadcast).
 //  * A lane takes the bases of its window 16 at a time: two packed words and two N-mask
 //    words funnel-shifted to the window's phase.  It has up to four chunks' windows in
-//    flight: their words are loaded together and a column's weights are fetched once.
+//    flight: their words are loaded together and a column's weights are fetched once
+//    (hit_score.hpp: the scoring code is scan_best.hip's too).
 //  * Two passes run the same scoring code.  The count pass stores each pair's hits; an
 //    exclusive u64 scan over the pairs, haplotype-major, turns them into offsets; the
 //    fill pass places each chunk's hits behind the pair's offset with a ballot and a
@@ -29,23 +30,12 @@
 #include <cstring>
 #include <string>
 
+#include "hit_score.hpp"
 #include "hits.hpp"
 #include "scan.hpp"
 
 namespace tfbs {
 namespace {
-
-constexpr uint32_t kHitWaves = 4;                       // waves (pairs) per workgroup
-constexpr uint32_t kHitBlock = 64 * kHitWaves;
-constexpr int kHitChunks = 4;                           // 64-window chunks a lane has in flight
-constexpr uint32_t kHitDiInts = (kDiMaxLen - 1) * 16;   // a dinucleotide strand's rows
-constexpr uint64_t kHitsMaxPairs = 1ull << 30;          // pairs per launch: the grid stays below 2^31
-
-typedef const __attribute__((address_space(4))) DevHitStrand CStrand;  // wave-uniform: scalar loads
-struct alignas(16) Col4 {  // one mono column: [A,C,G,T]
-    int32_t x, y, z, w;
-};
-typedef const __attribute__((address_space(4))) Col4 CInt4;
 
 struct HitsArgs {
     const DevHitStrand *strands;
@@ -65,70 +55,6 @@ struct HitsArgs {
     uint64_t rec_base, rec_cap;
     DevHitRec *recs;
 };
-
-// The 16 bases from base q of a haplotype (2 bits each, base q lowest) and their N bits.
-__device__ __forceinline__ void bases16(const uint32_t *W, const uint32_t *M, uint32_t q, uint32_t &bits,
-                                        uint32_t &nm) {
-    const uint32_t wi = q >> 4;
-    bits = __builtin_amdgcn_alignbit(W[wi + 1], W[wi], 2 * (q & 15));
-    nm = M ? __builtin_amdgcn_alignbit(M[(q >> 5) + 1], M[q >> 5], q & 31) : 0u;
-}
-
-// Wrapping column sums of the windows at bases i[0 .. NCH) (one per 64-window chunk in
-// flight: their words are loaded together, a column's weights once); an N column adds 0.
-template <int NCH>
-__device__ __forceinline__ void score_mono(const uint32_t *W, const uint32_t *M, const uint32_t (&i)[NCH], uint32_t L,
-                                           CInt4 *wq, uint32_t (&s)[NCH]) {
-#pragma unroll
-    for (int c = 0; c < NCH; c++) s[c] = 0;
-    for (uint32_t g = 0; g < L; g += 16) {  // (wave-uniform trip counts)
-        uint32_t bits[NCH], nm[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; c++) bases16(W, M, i[c] + g, bits[c], nm[c]);
-        const uint32_t cnt = min(16u, L - g);
-        for (uint32_t t = 0; t < cnt; t++) {
-            CInt4 &w = wq[g + t];
-            const int32_t wa = w.x, wc = w.y, wg = w.z, wt = w.w;
-#pragma unroll
-            for (int c = 0; c < NCH; c++) {
-                const uint32_t b = bits[c] & 3u;
-                const int32_t v = b == 0 ? wa : b == 1 ? wc : b == 2 ? wg : wt;
-                s[c] += (nm[c] & 1u) ? 0u : (uint32_t)v;
-                bits[c] >>= 2;
-                nm[c] >>= 1;
-            }
-        }
-    }
-}
-
-// Wrapping pair sums of the windows at bases i[0 .. NCH) (L <= 32 bases); a pair holding an
-// N adds 0.
-template <int NCH>
-__device__ __forceinline__ void score_dinuc(const uint32_t *W, const uint32_t *M, const uint32_t (&i)[NCH],
-                                            uint32_t L, const int32_t *rows, uint32_t (&s)[NCH]) {
-    uint32_t prev[NCH], prevn[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; c++) s[c] = 0, prev[c] = 0, prevn[c] = 1;  // (no pair ends on the first base)
-    for (uint32_t g = 0; g < L; g += 16) {
-        uint32_t bits[NCH], nm[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; c++) bases16(W, M, i[c] + g, bits[c], nm[c]);
-        const uint32_t cnt = min(16u, L - g);
-        for (uint32_t t = 0; t < cnt; t++) {
-            const uint32_t j = g + t;  // the pair (base j - 1, base j) is row j - 1
-#pragma unroll
-            for (int c = 0; c < NCH; c++) {
-                const uint32_t b = bits[c] & 3u, n = nm[c] & 1u;
-                const int32_t v = j ? rows[16 * (j - 1) + 4 * prev[c] + b] : 0;
-                s[c] += (n | prevn[c]) ? 0u : (uint32_t)v;
-                prev[c] = b;
-                prevn[c] = n;
-                bits[c] >>= 2;
-                nm[c] >>= 1;
-            }
-        }
-    }
-}
 
 struct HitsPair {  // what a wave knows of its pair (wave-uniform)
     const uint32_t *W, *M;
@@ -184,8 +110,7 @@ __global__ __launch_bounds__(kHitBlock) void scan_hits_kernel(HitsArgs A) {
     const int32_t min_score = S.min_score;
     const bool di = kind == TFBS_KIND_DIPWM;
     if (di) {  // (L <= kDiMaxLen: check_dipwm_length)
-        const uint32_t n = min((L - 1) * 16, kHitDiInts);
-        for (uint32_t x = lane; x < n; x += 64) s_rows[wave][x] = A.weights[w_off + x];
+        stage_dinuc_rows(s_rows[wave], A.weights, w_off, L, lane);
     }
     __syncthreads();
     if (!active) return;
@@ -214,40 +139,6 @@ __global__ __launch_bounds__(256) void hits_hap_offsets_kernel(const uint64_t *_
                                                                 uint32_t n_strands, uint64_t *__restrict__ hap_off) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k <= n_haps) hap_off[k] = off[(uint64_t)k * n_strands];
-}
-
-template <typename T>
-struct Buf {  // a device buffer that only grows
-    T *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return TFBS_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(TFBS_E_HIP, std::string("hipMalloc (hit lists): ") + hipGetErrorString(e));
-        }
-        cap = n;
-        return TFBS_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-#define HITS_TRY(expr)                                                                       \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) return fail(TFBS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 }  // namespace
@@ -353,9 +244,7 @@ int hits_run(HitsState **state, int device, void *stream_, const Patterns &P, co
         for (uint32_t h = 0; h < B.rh[r].hap_count; h++) ids.push_back(B.rh[r].hap_begin + h);
     if (ids.empty() || ns == 0) return TFBS_OK;
     if (ns > kHitsMaxPairs) return fail(TFBS_E_ARG, "too many strands for the hit list kernel");
-    const char *env = getenv("TFBS_HITS_SCRATCH_MB");  // read at the call
-    const double mb = env && *env ? strtod(env, nullptr) : 256.0;  // (fractions of a MiB too)
-    const uint64_t budget = mb > 0 ? (uint64_t)std::min(mb * 1048576.0, 9.0e18) : 0;
+    const uint64_t budget = scratch_budget("TFBS_HITS_SCRATCH_MB", 256.0);  // read at the call
 
     HitsArgs A{};
     A.strands = S.strands.p;

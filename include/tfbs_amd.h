@@ -483,6 +483,86 @@ int tfbs_batch_region_membership(const tfbs_batch *b, size_t region, uint32_t *o
 int tfbs_batch_hits_tsv(const tfbs_batch *b, const tfbs_hit *hits, size_t n, const char *chromosome, int mode,
                         char **text, size_t *len);
 
+/* ------------------------------------------------------------------ */
+/* Best sites: the threshold-free best score per haplotype, strand and  */
+/* inner range                                                          */
+/* ------------------------------------------------------------------ */
+/* One best record.  Take a region of a batch, h one of its n_haplotypes distinct
+ * haplotypes (helper reference copies are not included), p a pattern strand in creation
+ * order of L bases, k one of the region's distinct non-empty inner ranges, numbered in
+ * ascending (start, end) order (tfbs_batch_region_range).  Window i of h exists for p iff
+ * i + L <= len(h); its match range is [pos[i], pos[i] + L - 1] (pattern.rs:157-160) and its
+ * score the count path's and the hit list's (the wrapping int32 column sum, an N column
+ * adding 0, any L; or the wrapping int32 pair sum, a pair holding an N adding 0).  Window i
+ * belongs to range k iff range_overlaps(inner_k, match) (range.rs:18-21, the count path's
+ * asymmetric rule: the match's start or its end lies inside the inner range).
+ *   n_windows  the windows that belong to k
+ *   score      the maximum of their wrapped scores, compared as signed int32
+ *   window     the lowest i attaining it
+ *   start, end that window's match range
+ * n_windows == 0 (TFBS_KIND_OTHER, a haplotype shorter than L, no window overlapping the
+ * range): score = INT32_MIN, window = UINT32_MAX, start = end = 0; n_windows tells a genuine
+ * INT32_MIN from this.  min_score and the bed multiplicity play no part; empty inner ranges
+ * (end < start) have no record.  The result is dense: every (region, h, p, k) has exactly
+ * one record, sorted by (region, haplotype, pattern, range), so regions [r0, r1) give
+ * sum_r n_haplotypes(r) * n_patterns * n_ranges(r) records and a region's block reshapes to
+ * [h][p][k]. */
+typedef struct tfbs_best {
+    uint32_t region, haplotype, pattern, range;
+    uint32_t window, n_windows;
+    int32_t score;
+    uint32_t reserved;
+    uint64_t start, end;
+} tfbs_best; /* 48 bytes */
+
+/* The best records of regions [r0, r1) of the batch resident on ctx (after
+ * tfbs_batch_upload; needs no scan; leaves every scan / reduce / encode result and later
+ * step untouched).  *out is malloc'd (tfbs_free).  Its own kernel (scan_best.hip) scores
+ * every window of every distinct haplotype with the hit list's scoring code and reduces
+ * per range; it works in chunks of whole haplotypes whose device records fit
+ * TFBS_BEST_SCRATCH_MB (default 256; at least one haplotype; read at the call) and the
+ * result does not depend on it.  TFBS_E_STATE for a batch not resident, TFBS_E_ARG for
+ * r0 > r1 or r1 > num_regions; an empty range of regions or an empty pattern set gives
+ * *n = 0. */
+int tfbs_batch_best(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_best **out, size_t *n);
+/* Host only.  The region's distinct non-empty inner ranges (tfbs_best.range indexes them)
+ * and range k of them, in ascending (start, end) order. */
+int tfbs_batch_region_num_ranges(const tfbs_batch *b, size_t region, size_t *n);
+int tfbs_batch_region_range(const tfbs_batch *b, size_t region, size_t k, uint64_t *start, uint64_t *end);
+/* The last tfbs_batch_best's times (ms): out[0] the kernel (HIP events on the ctx stream,
+ * summed over the scratch chunks), out[1] the copy-back and host part (wall). */
+int tfbs_ctx_last_best_ms(const tfbs_ctx *ctx, double out[2]);
+/* Host only.  Formats best records as TSV, tab-separated, under the header
+ *   #chrom region bed inner_start inner_end name pattern_id haplotype carriers kind strand start end score delta carrier_ids
+ * The n records passed must be whole regions (each region's n_haplotypes * n_patterns *
+ * n_ranges records, regions ascending), not the whole batch: the text of a batch is the
+ * concatenation of its regions' texts, so a caller may format one region at a time.  A
+ * region without a record (no non-empty inner range, no pattern) writes nothing.
+ * Lines are per pattern_id, not per strand: the value of (haplotype, pattern_id, key) is
+ * the best over the pattern_id's strands -- the highest score, ties to the strand earlier
+ * in creation order; a strand with n_windows == 0 never wins; all of them so: "none".
+ * Keys are the region's (bed, inner range) pairs with a non-empty range, each once
+ * whatever its multiplicity, in the rows' order (inner start, inner end, bed as
+ * registered); under a key ascending pattern_id, then the haplotype index.  chrom, region,
+ * haplotype, carriers, name and strand are the hit TSV's; bed is the registered basename.
+ * TFBS_BEST_ALL: one `best` line per (key, pattern_id, haplotype); a "none" value writes
+ * "." for strand, start, end and score; delta and carrier_ids are ".".
+ * TFBS_BEST_DIFF: per region the hit TSV's baseline (the distinct haplotype with the most
+ * carrier ids, ties: the one holding the lowest haplotype id) and first its `hap` lines
+ * as the hit TSV's diff mode writes them (bed, inner_start, inner_end, name, pattern_id,
+ * strand, start, end, score and delta "."); then for each (key, pattern_id) where some
+ * haplotype's value differs from the baseline's in score or in being "none" one `base`
+ * line for the baseline and one `alt` line per differing haplotype in index order.  delta
+ * on an `alt` line is the haplotype's score minus the baseline's as a signed 64-bit
+ * difference (no wrap), "." when either is "none"; elsewhere ".".  A (key, pattern_id)
+ * where nothing differs writes nothing.
+ * The header line is not part of *text (malloc'd, tfbs_free). */
+#define TFBS_BEST_ALL 0
+#define TFBS_BEST_DIFF 1
+#define TFBS_BEST_HEADER "#chrom\tregion\tbed\tinner_start\tinner_end\tname\tpattern_id\thaplotype\tcarriers\tkind\tstrand\tstart\tend\tscore\tdelta\tcarrier_ids\n"
+int tfbs_batch_best_tsv(const tfbs_batch *b, const tfbs_best *best, size_t n, const char *chromosome, int mode,
+                        char **text, size_t *len);
+
 void tfbs_free(void *p);
 
 /* counts_as_genotypes alone (main.rs:439-498): 1 = row (strings written), 0 = no variation. */
@@ -519,6 +599,9 @@ typedef struct tfbs_run_args {
     const char *hits_output;       /* --hits_output: the batches' hit lists as BGZF TSV (tfbs_batch_hits_tsv under
                                       TFBS_HITS_HEADER), NULL = none: the run does nothing more than without it */
     int hits_mode;                 /* --hits_mode: TFBS_HITS_ALL / TFBS_HITS_DIFF */
+    const char *best_output;       /* --best_output: the batches' best sites as BGZF TSV (tfbs_batch_best_tsv under
+                                      TFBS_BEST_HEADER), NULL = none: the run does nothing more than without it */
+    int best_mode;                 /* --best_mode: TFBS_BEST_ALL / TFBS_BEST_DIFF */
 } tfbs_run_args;
 /* Replaces run() (main.rs:234-393): writes <output>.part, renames it to output.
  * The merged regions go in batches of regions_per_batch (the reference's 50-peak
