@@ -295,6 +295,14 @@ class Scanner:
     def __del__(self):
         self.close()
 
+    def rows_bgzf_blocks(self):
+        """tfbs_ctx_rows_bgzf_blocks: the BGZF blocks of the last RegionBatch.rows_bgzf call on
+        this scanner -- {"blocks" (written), "wave" (all rows staged: bgzf_wave_kernel; the
+        others went to bgzf_block_kernel), "stored" (BTYPE 00)}."""
+        out = (C.c_uint64 * 3)()
+        check(lib().tfbs_ctx_rows_bgzf_blocks(self.h, out))
+        return dict(zip(("blocks", "wave", "stored"), (int(x) for x in out)))
+
     def matches_all(self, haplotype):
         """pattern.rs:141-171 for every pattern: list (per pattern, creation order) of [(start, end)]."""
         n = len(haplotype)
@@ -473,6 +481,15 @@ class RegionBatch:
         per-sample codes on the GPU (for rows_bgzf)."""
         check(lib().tfbs_batch_encode_flags(scanner.h, self.h, r0, self.num_regions if r1 is None else r1,
                                             1 if device_codes else 0))
+
+    def encode_stats(self):
+        """tfbs_batch_encode_stats: which path the varying keys of the last encode() took --
+        {"keys", "w2", "w4", "w8" (encoded at that code width), "no_pairs" (the region's
+        haplotype pairs were not listed), "range", "values" (left to the host for the total
+        range / the number of distinct totals)}; keys is the sum of the others."""
+        out = (C.c_uint64 * 7)()
+        check(lib().tfbs_batch_encode_stats(self.h, out))
+        return dict(zip(("keys", "w2", "w4", "w8", "no_pairs", "range", "values"), (int(x) for x in out)))
 
     def keys(self, region):
         """count_matches_by_sample for one region: {(bed, (s, e), pattern_id): (L, R)}."""

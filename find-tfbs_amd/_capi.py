@@ -131,7 +131,9 @@ SIGNATURES = [
     ("tfbs_ctx_last_assemble_ms", C.c_float, [vp]),
     ("tfbs_batch_encode", C.c_int, [vp, vp, C.c_size_t, C.c_size_t]),
     ("tfbs_batch_encode_flags", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_int]),
+    ("tfbs_batch_encode_stats", C.c_int, [vp, u64p]),
     ("tfbs_ctx_rows_bgzf_seconds", C.c_int, [vp, C.POINTER(C.c_double)]),
+    ("tfbs_ctx_rows_bgzf_blocks", C.c_int, [vp, u64p]),
     ("tfbs_batch_rows_bgzf", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_char_p, C.c_uint32, u32p, C.c_int,
                                        u64p, u64p, u64p]),
     ("tfbs_batch_region_num_keys", C.c_int, [vp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -1259,6 +1259,27 @@ int tfbs_batch_build_stats(const tfbs_batch *b, uint64_t *dev_regions, uint64_t 
     return TFBS_OK;
 }
 
+int tfbs_batch_encode_stats(const tfbs_batch *b, uint64_t out[7]) {
+    if (!b || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    const Batch &B = b->b;
+    for (int i = 0; i < 7; i++) out[i] = 0;
+    // (var_keys is in region order; enc_idx is sized by the last encode)
+    for (size_t i = 0; i < B.var_keys.size() && i < B.enc_idx.size(); i++) {
+        const uint32_t r = B.var_keys[i].region;
+        if (r < B.enc_r0 || r >= B.enc_r1) continue;
+        out[0]++;
+        const uint32_t e = B.enc_idx[i];
+        if (e == UINT32_MAX || e >= B.enc_hdr.size()) {
+            out[4]++;
+            continue;
+        }
+        const tfbs::EncHdr &h = B.enc_hdr[e];
+        if (h.status) out[h.n_vals ? 6 : 5]++;  // (key_encode_kernel: n_vals = 0 for the range)
+        else out[h.width == 2 ? 1 : h.width == 4 ? 2 : 3]++;
+    }
+    return TFBS_OK;
+}
+
 int tfbs_batch_patch_stats(const tfbs_batch *b, uint64_t *patched_regions) {
     if (!b) return tfbs::fail(TFBS_E_ARG, "null argument");
     if (patched_regions) *patched_regions = b->b.patched_regions;

@@ -1523,16 +1523,27 @@ __global__ __launch_bounds__(256) void tok_lit_kernel(uint32_t *__restrict__ tex
     litn[k] = (uint8_t)(nb <= 128 ? nb : kNoTokLit);
 }
 
-// off[i] = the sizes of blocks before i, off[nb] = their total (one workgroup).
+// off[i] = the sizes of blocks before i, off[nb] = their total (one workgroup); behind it
+// the launch's path counters (tfbs_ctx_rows_bgzf_blocks): off[nb + 1] the blocks
+// bgzf_plan_kernel left to bgzf_wave_kernel (BlockPlan::all), off[nb + 2] = 0 for
+// bgzf_compact_kernel's count of the blocks that came out stored.
 __global__ __launch_bounds__(1024) void bgzf_offsets_kernel(const uint32_t *__restrict__ len, uint32_t nb,
-                                                            uint64_t *__restrict__ off) {
+                                                            uint64_t *__restrict__ off,
+                                                            const BlockPlan *__restrict__ plans) {
     __shared__ uint64_t s_sum[1024];
+    __shared__ uint32_t s_all;
     const uint32_t tid = threadIdx.x, per = (nb + 1023) / 1024;
     const uint32_t i0 = min(nb, tid * per), i1 = min(nb, i0 + per);
+    if (tid == 0) s_all = 0;
     uint64_t mine = 0;
-    for (uint32_t i = i0; i < i1; i++) mine += len[i];
+    uint32_t n_all = 0;
+    for (uint32_t i = i0; i < i1; i++) {
+        mine += len[i];
+        n_all += plans[i].all ? 1u : 0u;
+    }
     s_sum[tid] = mine;
     __syncthreads();
+    if (n_all) atomicAdd(&s_all, n_all);
     for (uint32_t o = 1; o < 1024; o <<= 1) {
         const uint64_t t = tid >= o ? s_sum[tid - o] : 0;
         __syncthreads();
@@ -1544,16 +1555,27 @@ __global__ __launch_bounds__(1024) void bgzf_offsets_kernel(const uint32_t *__re
         off[i] = at;
         at += len[i];
     }
-    if (tid == 1023) off[nb] = s_sum[1023];
+    if (tid == 1023) {
+        off[nb] = s_sum[1023];
+        off[nb + 1] = s_all;
+        off[nb + 2] = 0;
+    }
 }
 
-// Copies each block to its offset of one contiguous buffer.
+// Copies each block to its offset of one contiguous buffer; a stored block (BFINAL = 1,
+// BTYPE = 00: the low bits of its first deflate byte, byte 18, are 001) adds 1 to *n_stored
+// (zeroed by bgzf_offsets_kernel).
 __global__ __launch_bounds__(256) void bgzf_compact_kernel(const uint8_t *__restrict__ in,
                                                            const uint64_t *__restrict__ off,
-                                                           uint8_t *__restrict__ out) {
+                                                           uint8_t *__restrict__ out,
+                                                           unsigned long long *__restrict__ n_stored) {
     const uint64_t o = off[blockIdx.x], n = off[blockIdx.x + 1] - o;
     const uint8_t *src = in + (size_t)blockIdx.x * kBgzfMax;
-    for (uint64_t i = threadIdx.x; i < n; i += 256) out[o + i] = src[i];
+    for (uint64_t i = threadIdx.x; i < n; i += 256) {
+        const uint8_t b = src[i];
+        out[o + i] = b;
+        if (i == 18 && (b & 7u) == 1u) atomicAdd(n_stored, 1ull);
+    }
 }
 
 }  // namespace
@@ -1638,10 +1660,12 @@ int launch_bgzf_blocks(const BgArgs &a, uint32_t n_blocks, hipStream_t stream) {
 }
 
 int launch_bgzf_compact(const uint8_t *in, const uint32_t *len, uint64_t *off, uint32_t n_blocks, uint8_t *out,
-                        hipStream_t stream) {
+                        const void *plans, hipStream_t stream) {
     if (n_blocks == 0) return TFBS_OK;
-    hipLaunchKernelGGL(bgzf_offsets_kernel, dim3(1), dim3(1024), 0, stream, len, n_blocks, off);
-    hipLaunchKernelGGL(bgzf_compact_kernel, dim3(n_blocks), dim3(256), 0, stream, in, off, out);
+    hipLaunchKernelGGL(bgzf_offsets_kernel, dim3(1), dim3(1024), 0, stream, len, n_blocks, off,
+                       reinterpret_cast<const BlockPlan *>(plans));
+    hipLaunchKernelGGL(bgzf_compact_kernel, dim3(n_blocks), dim3(256), 0, stream, in, off, out,
+                       reinterpret_cast<unsigned long long *>(off + n_blocks + 2));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("bgzf_compact_kernel: ") + hipGetErrorString(e));
     return TFBS_OK;

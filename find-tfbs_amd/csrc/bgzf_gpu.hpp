@@ -55,8 +55,10 @@ int launch_row_cum(const BgArgs &a, hipStream_t stream);
 // planning kernel, one thread per block).
 int launch_bgzf_blocks(const BgArgs &a, uint32_t n_blocks, hipStream_t stream);
 // The blocks back to back: off[i] = the sizes len[] of the blocks before i (off[n_blocks] =
-// their total), block i's bytes at off[i] of out.
+// their total), block i's bytes at off[i] of out.  off holds n_blocks + 3 entries: behind
+// the total, how many of the launch's blocks (plans: launch_bgzf_blocks' a.plans) went to
+// bgzf_wave_kernel and how many came out stored.
 int launch_bgzf_compact(const uint8_t *in, const uint32_t *len, uint64_t *off, uint32_t n_blocks, uint8_t *out,
-                        hipStream_t stream);
+                        const void *plans, hipStream_t stream);
 
 }  // namespace tfbs

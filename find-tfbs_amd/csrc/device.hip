@@ -225,7 +225,9 @@ struct tfbs_ctx {
     DevBuf<uint32_t> bg_out_len[kBgSlots];
     DevBuf<uint64_t> bg_off[kBgSlots];
     tfbs::PinnedBytes bg_host[kBgSlots];  // compressed blocks staged for the host
-    uint64_t *bg_total_host = nullptr;  // pinned: each slot's packed bytes
+    uint64_t *bg_total_host = nullptr;  // pinned, 3 per slot: its packed bytes, wave-kernel blocks, stored blocks
+    uint32_t bg_slot_blocks[kBgSlots] = {};  // the blocks of each slot's launch
+    uint64_t bg_blocks[3] = {0, 0, 0};       // the last call's blocks: written, wave kernel's, stored (tfbs_ctx_rows_bgzf_blocks)
     hipEvent_t bg_done[kBgSlots] = {}, bg_copied[kBgSlots] = {};
     hipStream_t copy_stream = nullptr;
     double rows_s[2] = {0, 0};            // tfbs_batch_rows_bgzf seconds: row plan (host), the rest
@@ -1010,6 +1012,12 @@ int tfbs_ctx_rows_bgzf_seconds(const tfbs_ctx *ctx, double *out) {
     if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
     out[0] = ctx->rows_s[0];
     out[1] = ctx->rows_s[1];
+    return TFBS_OK;
+}
+
+int tfbs_ctx_rows_bgzf_blocks(const tfbs_ctx *ctx, uint64_t out[3]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    for (int i = 0; i < 3; i++) out[i] = ctx->bg_blocks[i];
     return TFBS_OK;
 }
 
@@ -1987,7 +1995,10 @@ int bgzf_drain(tfbs_ctx *ctx, int k, int fd, uint64_t &written) {
     const double t0 = now();
     HIP_TRY(hipEventSynchronize(ctx->bg_done[k]));
     const double t1 = now();
-    const uint64_t total = ctx->bg_total_host[k];
+    const uint64_t total = ctx->bg_total_host[3 * k];
+    ctx->bg_blocks[0] += ctx->bg_slot_blocks[k];
+    ctx->bg_blocks[1] += ctx->bg_total_host[3 * k + 1];
+    ctx->bg_blocks[2] += ctx->bg_total_host[3 * k + 2];
     int r;
     if (ctx->rows_async) {  // the writer thread copies it back and writes it (in order)
         if (!ctx->rw.th.joinable()) {
@@ -2122,7 +2133,7 @@ int rows_bgzf_device(tfbs_ctx *ctx, const Batch &B, tfbs::RowPlan &plan, std::ve
     const uint64_t kBatchBlocks = (uint64_t)std::max(1, env_int("TFBS_BGZF_BATCH_BLOCKS", 8192));
     const uint64_t n_batches = (n_blocks + kBatchBlocks - 1) / kBatchBlocks;
     if (!ctx->bg_total_host)
-        HIP_TRY(hipHostMalloc((void **)&ctx->bg_total_host, 8 * tfbs_ctx::kBgSlots, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void **)&ctx->bg_total_host, 3 * 8 * tfbs_ctx::kBgSlots, hipHostMallocDefault));
     for (int k = 0; k < tfbs_ctx::kBgSlots; k++) {
         if (!ctx->bg_done[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->bg_done[k], hipEventDisableTiming));
         if (!ctx->bg_copied[k]) HIP_TRY(hipEventCreateWithFlags(&ctx->bg_copied[k], hipEventDisableTiming));
@@ -2138,11 +2149,11 @@ int rows_bgzf_device(tfbs_ctx *ctx, const Batch &B, tfbs::RowPlan &plan, std::ve
             // the stream may wait for it (below), and done before the slot's buffers grow
             // (a reallocation under a pending copy sent zeros to the file)
             const bool grows = ctx->bg_out[k].cap < (size_t)nb * kBgzfMax || ctx->bg_packed[k].cap < (size_t)nb * kBgzfMax ||
-                               ctx->bg_out_len[k].cap < nb || ctx->bg_off[k].cap < (size_t)nb + 1;
+                               ctx->bg_out_len[k].cap < nb || ctx->bg_off[k].cap < (size_t)nb + 3;
             if ((rc = rows_wait(ctx, k, !grows))) return rc;
         }
         if ((rc = ctx->bg_out[k].ensure((size_t)nb * kBgzfMax)) || (rc = ctx->bg_out_len[k].ensure(nb)) ||
-            (rc = ctx->bg_off[k].ensure(nb + 1)) || (rc = ctx->bg_packed[k].ensure((size_t)nb * kBgzfMax)) ||
+            (rc = ctx->bg_off[k].ensure(nb + 3)) || (rc = ctx->bg_packed[k].ensure((size_t)nb * kBgzfMax)) ||
             (rc = ctx->bg_plans.ensure((size_t)nb * tfbs::bgzf_plan_bytes())))
             return rc;
         // slot k's packed blocks were copied back (kBgSlots batches ago) before they are overwritten
@@ -2163,7 +2174,7 @@ int rows_bgzf_device(tfbs_ctx *ctx, const Batch &B, tfbs::RowPlan &plan, std::ve
         }
         if ((rc = tfbs::launch_bgzf_blocks(a, nb, ctx->stream)) || (prof && (rc = bgzf_prof_report(ctx, nb))) ||
             (rc = tfbs::launch_bgzf_compact(ctx->bg_out[k].p, ctx->bg_out_len[k].p, ctx->bg_off[k].p, nb,
-                                            ctx->bg_packed[k].p, ctx->stream)))
+                                            ctx->bg_packed[k].p, ctx->bg_plans.p, ctx->stream)))
             return rc;
         if (bg_check) {
             uint32_t bad = 0;
@@ -2173,7 +2184,8 @@ int rows_bgzf_device(tfbs_ctx *ctx, const Batch &B, tfbs::RowPlan &plan, std::ve
                 return fail(TFBS_E_STATE, "bgzf_wave_kernel: " + std::to_string(bad) +
                                                  " block-text writes met bits already set (TFBS_BGZF_CHECK)");
         }
-        HIP_TRY(hipMemcpyAsync(ctx->bg_total_host + k, ctx->bg_off[k].p + nb, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(ctx->bg_total_host + 3 * k, ctx->bg_off[k].p + nb, 24, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->bg_slot_blocks[k] = nb;
         HIP_TRY(hipEventRecord(ctx->bg_done[k], ctx->stream));
         pp.pending[pp.n_pending++] = k;
         if (pp.n_pending == tfbs_ctx::kBgSlots && (rc = pp.drain_oldest(ctx, fd))) return rc;
@@ -2251,6 +2263,7 @@ int rows_bgzf_chained(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, const 
     int rc = build(0);
     if (rc) return rc;
     BgPipe pp;
+    ctx->bg_blocks[0] = ctx->bg_blocks[1] = ctx->bg_blocks[2] = 0;
     uint64_t rows = 0, text = 0;
     for (size_t j = 0; j < pieces; j++) {
         int next_rc = TFBS_OK;

@@ -348,6 +348,13 @@ int tfbs_batch_encode(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1);
  * slower path for these keys). */
 #define TFBS_ENC_DEVICE_CODES 1
 int tfbs_batch_encode_flags(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, int flags);
+/* Which path the keys of the last tfbs_batch_encode call took (read-only, zeros
+ * before one): out[0] the varying keys of its regions, out[1] / out[2] / out[3] those
+ * encoded with 2- / 4- / 8-bit codes, out[4] those not encoded because their
+ * region's haplotype pairs were not listed (> 8 192 pairs or > 65 535 distinct
+ * haplotypes), out[5] those left to the host for their total range (>= 65 536),
+ * out[6] for their number of distinct totals (> 255).  out[0] is the sum of the rest. */
+int tfbs_batch_encode_stats(const tfbs_batch *b, uint64_t out[7]);
 
 /* The rows of regions [r0, r1) (main.rs:415-429, same text as tfbs_batch_rows) as
  * BGZF blocks (main.rs:258-290's BGzWriter) built on the GPU
@@ -364,6 +371,11 @@ int tfbs_batch_rows_bgzf(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, con
 /* Seconds spent in tfbs_batch_rows_bgzf on this ctx so far: out[0] the row plan on
  * the host (heads, token tables), out[1] the rest (uploads, kernels, copy-back, write). */
 int tfbs_ctx_rows_bgzf_seconds(const tfbs_ctx *ctx, double *out);
+/* The BGZF blocks of the last tfbs_batch_rows_bgzf call on this ctx (read-only):
+ * out[0] the blocks written, out[1] those whose rows were all staged (deflated by
+ * bgzf_wave_kernel; the others by bgzf_block_kernel), out[2] those that did not
+ * deflate to half their size and were stored (BTYPE 00). */
+int tfbs_ctx_rows_bgzf_blocks(const tfbs_ctx *ctx, uint64_t out[3]);
 
 /* After download: count_matches_by_sample (main.rs:500-534), keys ordered by
  * (inner.start, inner.end, bed basename, pattern_id).  keys are per region. */

@@ -548,8 +548,9 @@ def test_large_scan_counts_are_invariant_to_tiling(tmp_path, monkeypatch):
 def test_many_variant_regions_vs_oracle(tmp_path, n):
     """Regions with 64 and ~90 distinct diffs: both haplotype-grouping paths of the
     host (64-bit diff masks / sorted diff lists) through the GPU scan vs the oracle;
-    at 300 samples the regions have > 255 distinct haplotypes, beyond the device
-    encoding's u8 membership (those keys take the host path)."""
+    at 300 samples the regions have > 255 distinct haplotypes, which the device
+    encoding's u16 membership covers (up to 65 535: their keys are encoded on the
+    device; test_gpu_encode_edges.py pins the encoding's real limits)."""
     from helpers import many_variant_regions
     ps, _ = synth_patterns(tmp_path, 10, 2, 31, thr=2e-3)
     regions = many_variant_regions(n, ps.max_length)
