@@ -3,8 +3,6 @@
 #include <algorithm>
 #include <cinttypes>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
 #include <string>
 
@@ -163,13 +161,7 @@ int tfbs_batch_best_tsv(const tfbs_batch *b, const tfbs_best *best, size_t n, co
     if (!b || !chromosome || !text || !len || (n && !best)) return tfbs::fail(TFBS_E_ARG, "null argument");
     std::string out;
     if (int rc = tfbs::best_tsv(b->b, best, n, chromosome, mode, out)) return rc;
-    char *p = (char *)malloc(out.size() + 1);
-    if (!p) return tfbs::fail(TFBS_E_NOMEM, "malloc");
-    memcpy(p, out.data(), out.size());
-    p[out.size()] = 0;
-    *text = p;
-    *len = out.size();
-    return TFBS_OK;
+    return tfbs::text_out(out, text, len);
 }
 
 }  // extern "C"

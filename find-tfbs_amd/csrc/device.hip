@@ -2291,6 +2291,17 @@ int rows_bgzf_chained(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, const 
 
 }  // namespace tfbs
 
+// A result list handed out through the C API: *out a malloc'd copy (never null), *n its length.
+template <typename T>
+static int hand_out(const std::vector<T> &v, T **out, size_t *n) {
+    T *p = static_cast<T *>(malloc(std::max<size_t>(1, v.size()) * sizeof(T)));
+    if (!p) return tfbs::fail(TFBS_E_NOMEM, "malloc");
+    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T));
+    *out = p;
+    *n = v.size();
+    return TFBS_OK;
+}
+
 extern "C" {
 
 int tfbs_batch_rows_bgzf(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, const char *chromosome,
@@ -2378,33 +2389,30 @@ int tfbs_matches(tfbs_ctx *ctx, const uint8_t *nucs, const uint64_t *pos, size_t
     return TFBS_OK;
 }
 
-// Hit lists (scan_hits.hip): the resident image, the ctx's stream, buffers of their own.
-static int hits_call(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, std::vector<tfbs_hit> *out,
-                     uint64_t *per_region) {
-    if (!ctx || !b) return tfbs::fail(TFBS_E_ARG, "null argument");
+// Hit lists and best sites (scan_hits.hip, scan_best.hip): a call's arguments checked (null_out:
+// the entry point's own null rule), then *img.
+static int resident_image(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, bool null_out, ScanImage *img) {
+    if (!ctx || !b || null_out) return tfbs::fail(TFBS_E_ARG, "null argument");
     if (ctx->resident != b) return tfbs::fail(TFBS_E_STATE, "batch not resident on this ctx (tfbs_batch_upload)");
-    const Batch &B = b->b;
-    if (r0 > r1 || r1 > B.rh.size()) return tfbs::fail(TFBS_E_ARG, "bad region range");
-    if (B.haps.size() != ctx->haps.n) return tfbs::fail(TFBS_E_STATE, "regions added since the upload");
-    const HitsImage img{ctx->haps.p, ctx->words.p, ctx->nmask.p};
-    return hits_run(&ctx->hits_state, ctx->device, ctx->stream, *ctx->pats, img, B, r0, r1, out, per_region);
-}
-
-int tfbs_batch_hits(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_hit **out, size_t *n) {
-    if (!out || !n) return tfbs::fail(TFBS_E_ARG, "null argument");
-    std::vector<tfbs_hit> v;
-    if (int rc = hits_call(ctx, b, r0, r1, &v, nullptr)) return rc;
-    tfbs_hit *p = static_cast<tfbs_hit *>(malloc(std::max<size_t>(1, v.size()) * sizeof(tfbs_hit)));
-    if (!p) return tfbs::fail(TFBS_E_NOMEM, "malloc");
-    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(tfbs_hit));
-    *out = p;
-    *n = v.size();
+    if (r0 > r1 || r1 > b->b.rh.size()) return tfbs::fail(TFBS_E_ARG, "bad region range");
+    if (b->b.haps.size() != ctx->haps.n) return tfbs::fail(TFBS_E_STATE, "regions added since the upload");
+    *img = ScanImage{ctx->haps.p, ctx->words.p, ctx->nmask.p, ctx->posrel.p, ctx->regions.p, ctx->inner.p};
     return TFBS_OK;
 }
 
+int tfbs_batch_hits(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_hit **out, size_t *n) {
+    ScanImage img;
+    std::vector<tfbs_hit> v;
+    if (int rc = resident_image(ctx, b, r0, r1, !out || !n, &img)) return rc;
+    if (int rc = hits_run(&ctx->hits_state, ctx->device, ctx->stream, *ctx->pats, img, b->b, r0, r1, &v, nullptr))
+        return rc;
+    return hand_out(v, out, n);
+}
+
 int tfbs_batch_hits_count(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, uint64_t *per_region) {
-    if (!per_region && r1 > r0) return tfbs::fail(TFBS_E_ARG, "null argument");
-    return hits_call(ctx, b, r0, r1, nullptr, per_region);
+    ScanImage img;
+    if (int rc = resident_image(ctx, b, r0, r1, !per_region && r1 > r0, &img)) return rc;
+    return hits_run(&ctx->hits_state, ctx->device, ctx->stream, *ctx->pats, img, b->b, r0, r1, nullptr, per_region);
 }
 
 int tfbs_ctx_last_hits_ms(const tfbs_ctx *ctx, double out[4]) {
@@ -2413,22 +2421,12 @@ int tfbs_ctx_last_hits_ms(const tfbs_ctx *ctx, double out[4]) {
     return TFBS_OK;
 }
 
-// Best sites (scan_best.hip): the resident image, the ctx's stream, buffers of their own.
 int tfbs_batch_best(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_best **out, size_t *n) {
-    if (!ctx || !b || !out || !n) return tfbs::fail(TFBS_E_ARG, "null argument");
-    if (ctx->resident != b) return tfbs::fail(TFBS_E_STATE, "batch not resident on this ctx (tfbs_batch_upload)");
-    const Batch &B = b->b;
-    if (r0 > r1 || r1 > B.rh.size()) return tfbs::fail(TFBS_E_ARG, "bad region range");
-    if (B.haps.size() != ctx->haps.n) return tfbs::fail(TFBS_E_STATE, "regions added since the upload");
-    const BestImage img{ctx->haps.p, ctx->words.p, ctx->nmask.p, ctx->posrel.p, ctx->regions.p, ctx->inner.p};
+    ScanImage img;
     std::vector<tfbs_best> v;
-    if (int rc = best_run(&ctx->best_state, ctx->device, ctx->stream, *ctx->pats, img, B, r0, r1, &v)) return rc;
-    tfbs_best *p = static_cast<tfbs_best *>(malloc(std::max<size_t>(1, v.size()) * sizeof(tfbs_best)));
-    if (!p) return tfbs::fail(TFBS_E_NOMEM, "malloc");
-    if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(tfbs_best));
-    *out = p;
-    *n = v.size();
-    return TFBS_OK;
+    if (int rc = resident_image(ctx, b, r0, r1, !out || !n, &img)) return rc;
+    if (int rc = best_run(&ctx->best_state, ctx->device, ctx->stream, *ctx->pats, img, b->b, r0, r1, &v)) return rc;
+    return hand_out(v, out, n);
 }
 
 int tfbs_ctx_last_best_ms(const tfbs_ctx *ctx, double out[2]) {

@@ -1,12 +1,19 @@
-// The exact scoring code of the brute-force kernels (scan_hits.hip, scan_best.hip) and the
-// small host helpers of their drivers.  A HIP header: only .hip sources include it.
+// What the brute-force kernels (scan_hits.hip, scan_best.hip) and their drivers share.  A HIP
+// header: only .hip sources include it.
+//  * Device: the exact scoring code (bases16, score_mono, score_dinuc), the kernels' prologue
+//    in two steps (pair_head, PAIR_OPEN), what a wave knows of its pair (PairScan) and the walk
+//    over the pair's windows (WALK_CHUNKS, scored_window, SCORE_WINDOWS).  A kernel keeps what
+//    it does with a chunk's scores.
+//  * Host: the drivers' common state (PairState, first_use), Buf, HITS_TRY, the scratch budget.
 //
-// A lane takes the bases of its window 16 at a time: two packed words and two N-mask
-// words funnel-shifted to the window's phase.  It has up to four 64-window chunks' windows
-// in flight: their words are loaded together and a column's weights are fetched once.  The
-// strand is wave-uniform: a mono column's four weights come through one scalar load and
-// three selects, a dinucleotide strand's rows (at most 31 x 16 ints) sit in the wave's LDS
-// slice, where the 16 entries of a row lie on 16 banks (lanes on one entry broadcast).
+// A wave owns one (haplotype, strand) pair; its lanes are 64 consecutive windows and it walks
+// the 64-window chunks in ascending order.  A lane takes the bases of its window 16 at a time:
+// two packed words and two N-mask words funnel-shifted to the window's phase.  It has up to
+// four 64-window chunks' windows in flight: their words are loaded together and a column's
+// weights are fetched once.  The strand is wave-uniform: a mono column's four weights come
+// through one scalar load and three selects, a dinucleotide strand's rows (at most 31 x 16
+// ints) sit in the wave's LDS slice, where the 16 entries of a row lie on 16 banks (lanes on
+// one entry broadcast).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -104,6 +111,105 @@ __device__ __forceinline__ void stage_dinuc_rows(int32_t *slice, const int32_t *
     for (uint32_t x = lane; x < n; x += 64) slice[x] = weights[w_off + x];
 }
 
+struct PairSrc {  // the tables and the batch image: the head of both kernels' arguments
+    const DevHitStrand *strands;
+    const int32_t *weights;
+    uint32_t n_strands;
+    const DevHap *haps;
+    const uint32_t *words;
+    const uint32_t *nmask;
+};
+
+struct PairHead {  // the prologue's first step (wave-uniform but lane)
+    uint32_t lane;
+    uint64_t pl, p;    // the wave's pair: of the launch, of the chunk
+    bool active;       // the launch has a pair pl
+    uint32_t k, sidx;  // p = chunk haplotype k * n_strands + strand sidx
+    uint32_t kind, L, w_off;
+    int32_t min_score;
+    bool di;
+    const int32_t *rows;  // the wave's LDS slice: a dinucleotide strand's rows
+};
+
+struct PairScan {  // what a wave knows of its pair to score it (wave-uniform)
+    const uint32_t *W, *M;
+    CInt4 *wq;
+    const int32_t *rows;
+    uint32_t L, nwin;
+    bool di;
+};
+
+// The prologue up to and including the workgroup's barrier.  The launch takes the pairs of
+// chunk haplotypes [k0, k1) (pairs are haplotype-major: the first is k0 * n_strands); the wave
+// takes pair blockIdx.x * kHitWaves + wave of them, loads its strand through scalar loads and
+// stages a dinucleotide strand's rows.  An inactive wave (the last workgroup's tail) takes the
+// last pair, so that every wave of the workgroup reaches the barrier.
+__device__ __forceinline__ PairHead pair_head(const PairSrc &T, uint32_t k0, uint32_t k1,
+                                              int32_t (&s_rows)[kHitWaves][kHitDiInts]) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t n_pairs = (uint64_t)(k1 - k0) * T.n_strands;
+    const uint64_t pl = (uint64_t)blockIdx.x * kHitWaves + wave;
+    const bool active = pl < n_pairs;
+    const uint64_t p = (uint64_t)k0 * T.n_strands + (active ? pl : n_pairs - 1);
+    const uint32_t k = (uint32_t)(p / T.n_strands);
+    const uint32_t sidx = (uint32_t)(p - (uint64_t)k * T.n_strands);
+    CStrand &S = ((CStrand *)T.strands)[sidx];
+    const uint32_t kind = S.kind, L = S.len, w_off = S.w_off;
+    const int32_t min_score = S.min_score;
+    const bool di = kind == TFBS_KIND_DIPWM;
+    if (di) stage_dinuc_rows(s_rows[wave], T.weights, w_off, L, lane);  // (L <= kDiMaxLen: check_dipwm_length)
+    __syncthreads();
+    return PairHead{lane, pl, p, active, k, sidx, kind, L, w_off, min_score, di, s_rows[wave]};
+}
+
+// The three pieces below are macros, not functions: a function is simplified on its own
+// before it is inlined, and with any of them as one the built kernels differ from those of
+// the code written out in each kernel (registers, occupancy, the branches around a chunk's
+// second half).  Expanded in place they are that code.
+//
+// The prologue's second step, for a wave that goes on: declares the pair's haplotype (batch
+// index `hid`, descriptor `hm`) and `const PairScan P` (and, on the way, `scored` and `nwin`).
+// nwin 0: nothing to score.
+#define PAIR_OPEN(T, H, hap_ids, hid, hm, P)                                                        \
+    const uint32_t hid = (hap_ids)[(H).k];                                                          \
+    const DevHap hm = (T).haps[hid];                                                                \
+    const bool scored = (H).L != 0 && hm.len >= (H).L && ((H).kind == TFBS_KIND_PWM || (H).di);     \
+    const uint32_t nwin = scored ? hm.len - (H).L + 1 : 0;                                          \
+    const PairScan P {                                                                              \
+        (T).words + hm.word_off, (hm.flags & HAP_HAS_N) ? (T).nmask + hm.nmask_off : nullptr,       \
+            (CInt4 *)((T).weights + (H).w_off), (H).rows, (H).L, nwin, (H).di                       \
+    }
+
+// The walk over a pair's windows: BODY, a statement that uses the constant NCH, for NCH
+// 64-window chunks from window c0, ascending.  A 3-chunk tail scores one chunk of window 0.
+#define WALK_CHUNKS(nwin, c0, BODY)                                      \
+    for (uint32_t c0 = 0; c0 < (nwin); c0 += 64 * kHitChunks) {          \
+        const uint32_t nch = ((nwin) - c0 + 63) / 64;                    \
+        if (nch >= 3) {                                                  \
+            constexpr int NCH = kHitChunks;                              \
+            BODY;                                                        \
+        } else if (nch == 2) {                                           \
+            constexpr int NCH = 2;                                       \
+            BODY;                                                        \
+        } else {                                                         \
+            constexpr int NCH = 1;                                       \
+            BODY;                                                        \
+        }                                                                \
+    }
+
+// The chunk scorer: the scores s[] of the windows at bases ii[0 .. NCH) of pair P.
+#define SCORE_WINDOWS(NCH, P, ii, s)                                             \
+    do {                                                                         \
+        if ((P).di) score_dinuc<NCH>((P).W, (P).M, ii, (P).L, (P).rows, s);      \
+        else score_mono<NCH>((P).W, (P).M, ii, (P).L, (P).wq, s);                \
+    } while (0)
+
+// The window a lane scores in place of window i.
+__device__ __forceinline__ uint32_t scored_window(const PairScan &P, uint32_t i) {
+    return i < P.nwin ? i : 0;  // (window 0 exists: reads stay inside the haplotype's pads)
+}
+
 template <typename T>
 struct Buf {  // a device buffer that only grows
     T *p = nullptr;
@@ -127,6 +233,57 @@ struct Buf {  // a device buffer that only grows
         cap = 0;
     }
 };
+
+// What both drivers keep on a ctx: the pattern set's tables on the device (build_hit_tables),
+// the chunk's haplotype list, the pinned buffer of the copy-back and the events.
+struct PairState {
+    Buf<DevHitStrand> strands;
+    Buf<int32_t> weights;
+    uint32_t n_strands = 0;
+    Buf<uint32_t> hap_ids;
+    PinnedBytes host;
+    hipEvent_t ev[3] = {};
+    // The tables uploaded and n_events events created; a failure reads "<label>: ...".
+    int upload(const Patterns &P, hipStream_t stream, int n_events, const char *label) {
+        HitTables T;
+        build_hit_tables(P, &T);
+        n_strands = (uint32_t)T.strands.size();
+        int rc;
+        if ((rc = strands.ensure(T.strands.size())) || (rc = weights.ensure(T.weights.size() + 4))) return rc;
+        hipError_t e = hipSuccess;
+        if (!T.strands.empty())
+            e = hipMemcpyAsync(strands.p, T.strands.data(), T.strands.size() * sizeof(DevHitStrand),
+                               hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess && !T.weights.empty())
+            e = hipMemcpyAsync(weights.p, T.weights.data(), T.weights.size() * 4, hipMemcpyHostToDevice, stream);
+        for (int k = 0; k < n_events; k++)
+            if (e == hipSuccess) e = hipEventCreate(&ev[k]);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);  // (T goes out of scope)
+        return e == hipSuccess ? TFBS_OK : fail(TFBS_E_HIP, std::string(label) + ": " + hipGetErrorString(e));
+    }
+    ~PairState() {
+        strands.release(); weights.release(); hap_ids.release();
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    PairSrc src(const ScanImage &img) const {
+        return PairSrc{strands.p, weights.p, n_strands, img.haps, img.words, img.nmask};
+    }
+};
+
+// A driver's state (a PairState and its own buffers) on its first call: made, its tables
+// uploaded; a failure deletes it and leaves *state null, so the next call tries again.
+template <typename S>
+int first_use(S **state, const Patterns &P, hipStream_t stream, int n_events, const char *label) {
+    if (*state) return TFBS_OK;
+    S *s = new S();
+    if (int rc = s->upload(P, stream, n_events, label)) {
+        delete s;
+        return rc;
+    }
+    *state = s;
+    return TFBS_OK;
+}
 
 #define HITS_TRY(expr)                                                                       \
     do {                                                                                     \

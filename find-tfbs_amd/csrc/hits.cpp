@@ -165,6 +165,16 @@ int hits_tsv(const Batch &B, const tfbs_hit *hits, size_t n, const std::string &
     return TFBS_OK;
 }
 
+int text_out(const std::string &s, char **text, size_t *len) {
+    char *p = (char *)malloc(s.size() + 1);
+    if (!p) return fail(TFBS_E_NOMEM, "malloc");
+    memcpy(p, s.data(), s.size());
+    p[s.size()] = 0;
+    *text = p;
+    *len = s.size();
+    return TFBS_OK;
+}
+
 }  // namespace tfbs
 
 extern "C" {
@@ -207,13 +217,7 @@ int tfbs_batch_hits_tsv(const tfbs_batch *b, const tfbs_hit *hits, size_t n, con
     if (!b || !chromosome || !text || !len || (n && !hits)) return tfbs::fail(TFBS_E_ARG, "null argument");
     std::string out;
     if (int rc = tfbs::hits_tsv(b->b, hits, n, chromosome, mode, out)) return rc;
-    char *p = (char *)malloc(out.size() + 1);
-    if (!p) return tfbs::fail(TFBS_E_NOMEM, "malloc");
-    memcpy(p, out.data(), out.size());
-    p[out.size()] = 0;
-    *text = p;
-    *len = out.size();
-    return TFBS_OK;
+    return tfbs::text_out(out, text, len);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // Hit lists (tfbs_batch_hits) and best sites (tfbs_batch_best): the interfaces of
-// scan_hits.hip and scan_best.hip to device.hip, and the host-only helpers of hits.cpp
-// and best.cpp.
+// scan_hits.hip and scan_best.hip to device.hip, what the two share on the host (the tables,
+// ScanImage, site_range, text_out) and the host-only helpers of hits.cpp and best.cpp.
 #pragma once
 
 #include <cstdint>
@@ -41,17 +41,31 @@ struct DevHitRec {
 // timers; made by the ctx's first hits call.
 struct HitsState;
 void hits_state_destroy(HitsState *s);
-// The resident batch image as the scan reads it (device pointers).
-struct HitsImage {
+// The resident batch image as the two kernels read it (device pointers); the hit kernel
+// reads the first three.
+struct ScanImage {
     const DevHap *haps;
     const uint32_t *words;
     const uint32_t *nmask;
+    const int32_t *posrel;
+    const DevRegion *regions;
+    const int32_t *inner;
 };
+// The public range of the site of strand `pattern` at `window` of haplotype hm of region R
+// (the callers' record loops hold both).
+inline void site_range(const Batch &B, const Patterns &P, const RegionH &R, const DevHap &hm, uint32_t pattern,
+                       uint32_t window, uint64_t *start, uint64_t *end) {
+    const int64_t rel = (hm.flags & HAP_HAS_POS) ? B.posrel[hm.pos_off + window] : (int64_t)window;
+    *start = R.es + (uint64_t)rel;
+    *end = *start + P.pats[pattern].len - 1;
+}
+// A text handed out through the C API: *text a malloc'd, 0-terminated copy, *len its length.
+int text_out(const std::string &s, char **text, size_t *len);
 // The hit list of regions [r0, r1) of B (resident as img on `device`): appended to *out
 // (sorted as specified), or -- out null -- the count pass alone into per_region[r - r0].
 // *state is made on the first call.  Synchronises `stream` (a hipStream_t; this header
 // is also the host sources', which include no HIP header).
-int hits_run(HitsState **state, int device, void *stream, const Patterns &P, const HitsImage &img,
+int hits_run(HitsState **state, int device, void *stream, const Patterns &P, const ScanImage &img,
              const Batch &B, size_t r0, size_t r1, std::vector<tfbs_hit> *out, uint64_t *per_region);
 // The last hits_run's times (ms): count pass, scan, fill pass (HIP events, summed over
 // the chunks), copy-back + host part (wall).
@@ -78,19 +92,10 @@ struct alignas(16) DevBestRec {
 };
 struct BestState;
 void best_state_destroy(BestState *s);
-// The resident batch image as the best kernel reads it (device pointers).
-struct BestImage {
-    const DevHap *haps;
-    const uint32_t *words;
-    const uint32_t *nmask;
-    const int32_t *posrel;
-    const DevRegion *regions;
-    const int32_t *inner;
-};
 // The dense best records of regions [r0, r1) of B (resident as img on `device`) appended to
 // *out, sorted by (region, haplotype, pattern, range).  *state is made on the first call.
 // Synchronises `stream` (a hipStream_t).
-int best_run(BestState **state, int device, void *stream, const Patterns &P, const BestImage &img, const Batch &B,
+int best_run(BestState **state, int device, void *stream, const Patterns &P, const ScanImage &img, const Batch &B,
              size_t r0, size_t r1, std::vector<tfbs_best> *out);
 // The last best_run's times (ms): the kernel (HIP events, summed over the chunks), copy-back + host part (wall).
 void best_last_ms(const BestState *s, double out[2]);

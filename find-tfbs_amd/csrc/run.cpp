@@ -98,13 +98,25 @@ struct Shard {
 
 // --hits_output, --best_output: the batches' texts (tfbs_batch_hits_tsv, tfbs_batch_best_tsv)
 // written in batch order by the host BGZF writer, whichever shard hands them in first.
-struct HitsOut {
+struct TextOut {
     std::mutex mu;
     tfbs::BgzfWriter w;
+    std::string path;                       // written as path + ".part", renamed by finish()
     std::map<size_t, std::string> pending;  // batches past `next`, waiting for their turn
     size_t next = 0;
     int rc = TFBS_OK;
     std::string err;
+    int open(const char *path_, uint32_t threads, const char *header) {
+        path = path_;
+        if (int e = w.open(path + ".part", threads)) return e;
+        return w.write(header, strlen(header));
+    }
+    int finish() {
+        if (int e = w.close()) return e;
+        if (rename((path + ".part").c_str(), path.c_str()) != 0)
+            return tfbs::fail(TFBS_E_IO, "Could not rename " + path + ".part into " + path);
+        return TFBS_OK;
+    }
     int submit(size_t g, std::string &&text) {
         std::lock_guard<std::mutex> l(mu);
         pending[g] = std::move(text);
@@ -120,8 +132,8 @@ constexpr size_t kBestRunRecords = 1u << 20;
 
 struct RunSetup {
     const tfbs_run_args *a;
-    HitsOut *hits = nullptr;  // null without --hits_output: the run does nothing more
-    HitsOut *best = nullptr;  // null without --best_output: the same
+    TextOut *hits = nullptr;  // null without --hits_output: the run does nothing more
+    TextOut *best = nullptr;  // null without --best_output: the same
     std::string chrom;
     tfbs_patterns *pp;
     std::vector<std::pair<std::string, std::vector<std::pair<uint64_t, uint64_t>>>> beds;
@@ -662,24 +674,17 @@ int tfbs_run(const tfbs_run_args *a) {
     header += "\n";
     rc = w.write(header.data(), header.size());
     if (rc) return rc;
-    HitsOut hits_out;
-    const std::string hits_path = a->hits_output ? a->hits_output : "";
+    TextOut hits_out, best_out;
     if (a->hits_output) {
         if (a->hits_mode != TFBS_HITS_ALL && a->hits_mode != TFBS_HITS_DIFF)
             return fail(TFBS_E_ARG, "hits_mode is TFBS_HITS_ALL or TFBS_HITS_DIFF");
-        if ((rc = hits_out.w.open(hits_path + ".part", threads)) ||
-            (rc = hits_out.w.write(TFBS_HITS_HEADER, strlen(TFBS_HITS_HEADER))))
-            return rc;
+        if ((rc = hits_out.open(a->hits_output, threads, TFBS_HITS_HEADER))) return rc;
         S.hits = &hits_out;
     }
-    HitsOut best_out;
-    const std::string best_path = a->best_output ? a->best_output : "";
     if (a->best_output) {
         if (a->best_mode != TFBS_BEST_ALL && a->best_mode != TFBS_BEST_DIFF)
             return fail(TFBS_E_ARG, "best_mode is TFBS_BEST_ALL or TFBS_BEST_DIFF");
-        if ((rc = best_out.w.open(best_path + ".part", threads)) ||
-            (rc = best_out.w.write(TFBS_BEST_HEADER, strlen(TFBS_BEST_HEADER))))
-            return rc;
+        if ((rc = best_out.open(a->best_output, threads, TFBS_BEST_HEADER))) return rc;
         S.best = &best_out;
     }
 
@@ -838,16 +843,8 @@ int tfbs_run(const tfbs_run_args *a) {
     // the reference flushes twice before drop (main.rs:271, 275): two empty blocks
     double t0 = now();
     if ((rc = w.flush()) || (rc = w.flush()) || (rc = w.close())) return rc;
-    if (S.hits) {
-        if ((rc = hits_out.w.close())) return rc;
-        if (rename((hits_path + ".part").c_str(), hits_path.c_str()) != 0)
-            return fail(TFBS_E_IO, "Could not rename " + hits_path + ".part into " + hits_path);
-    }
-    if (S.best) {
-        if ((rc = best_out.w.close())) return rc;
-        if (rename((best_path + ".part").c_str(), best_path.c_str()) != 0)
-            return fail(TFBS_E_IO, "Could not rename " + best_path + ".part into " + best_path);
-    }
+    if (S.hits && (rc = hits_out.finish())) return rc;
+    if (S.best && (rc = best_out.finish())) return rc;
     const double t_close = now() - t0;
     if (timing)
         for (size_t k = 0; k < n_sh; k++)

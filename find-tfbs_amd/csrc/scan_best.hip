@@ -2,12 +2,12 @@
 // the highest score among the windows whose match range overlaps the range, the lowest
 // window attaining it and the number of such windows.  min_score plays no part.
 //
-// The scoring is scan_hits.hip's (hit_score.hpp): brute force over every window of every
-// distinct haplotype from the pattern set alone -- no plan, no lookup tables, no window
-// lists, no reuse between haplotypes.
+// The pair a wave owns, the prologue, the walk over the pair's windows and the scoring are
+// hit_score.hpp's, shared with scan_hits.hip, and so is the driver's base (PairState): brute
+// force over every window of every distinct haplotype from the pattern set alone -- no plan,
+// no lookup tables, no window lists, no reuse between haplotypes.  This file keeps what is
+// done with a chunk's scores and the range sweeps.
 //
-//  * A wave owns one (haplotype, strand) pair; its lanes are 64 consecutive windows and it
-//    walks the 64-window chunks in ascending order, up to four chunks in flight.
 //  * The region's ranges go in groups of kBestRanges per sweep over the windows: their
 //    (s_rel, e_rel) pairs sit in scalar registers, and a lane keeps (score, window, count)
 //    per range of the group.  A lane meets its windows in ascending order, so a strictly
@@ -21,11 +21,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
-#include <string>
+#include <vector>
 
 #include "hit_score.hpp"
-#include "hits.hpp"
 
 namespace tfbs {
 namespace {
@@ -37,12 +35,7 @@ namespace {
 constexpr int kBestRanges = 4;
 
 struct BestArgs {
-    const DevHitStrand *strands;
-    const int32_t *weights;
-    uint32_t n_strands;
-    const DevHap *haps;
-    const uint32_t *words;
-    const uint32_t *nmask;
+    PairSrc src;
     const int32_t *posrel;
     const DevRegion *regions;
     const int32_t *inner;
@@ -53,15 +46,6 @@ struct BestArgs {
     DevBestRec *recs;
 };
 
-struct BestPair {  // what a wave knows of its pair (wave-uniform)
-    const uint32_t *W, *M;
-    const int32_t *pos;  // null: window i starts at i
-    CInt4 *wq;
-    const int32_t *rows;
-    uint32_t L, nwin;
-    bool di;
-};
-
 template <int NG>
 struct BestLane {  // a lane's running best and count per range of the sweep
     int32_t score[NG];
@@ -70,20 +54,19 @@ struct BestLane {  // a lane's running best and count per range of the sweep
 
 // NCH 64-window chunks from window c0, in ascending order: scored together, then each
 // existing window is tested against the sweep's NG ranges by range_overlaps(inner, match)
-// (range.rs:18-21: the match's start or its end lies inside the inner range).
+// (range.rs:18-21: the match's start or its end lies inside the inner range).  pos: the
+// windows' starts (null: window i starts at i).
 template <int NCH, int NG>
-__device__ __forceinline__ void best_chunks(const BestPair &P, uint32_t c0, uint32_t lane, const int32_t (&rs)[NG],
-                                            const int32_t (&re)[NG], BestLane<NG> &b) {
+__device__ __forceinline__ void best_chunks(const PairScan &P, const int32_t *pos, uint32_t c0, uint32_t lane,
+                                            const int32_t (&rs)[NG], const int32_t (&re)[NG], BestLane<NG> &b) {
     uint32_t ii[NCH], s[NCH];
     int32_t ms[NCH];
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
-        const uint32_t i = c0 + 64 * c + lane;
-        ii[c] = i < P.nwin ? i : 0;  // (window 0 exists: reads stay inside the haplotype's pads)
-        ms[c] = P.pos ? P.pos[ii[c]] : (int32_t)ii[c];
+        ii[c] = scored_window(P, c0 + 64 * c + lane);
+        ms[c] = pos ? pos[ii[c]] : (int32_t)ii[c];
     }
-    if (P.di) score_dinuc<NCH>(P.W, P.M, ii, P.L, P.rows, s);
-    else score_mono<NCH>(P.W, P.M, ii, P.L, P.wq, s);
+    SCORE_WINDOWS(NCH, P, ii, s);
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
         const uint32_t i = c0 + 64 * c + lane;
@@ -104,8 +87,8 @@ __device__ __forceinline__ void best_chunks(const BestPair &P, uint32_t c0, uint
 // sweep is built for 1, 2 and kBestRanges ranges, so a region of one range pays for one),
 // then the reduction and the ng records from recs[rec].
 template <int NG>
-__device__ __forceinline__ void best_sweep(const BestArgs &A, const BestPair &P, uint32_t lane, uint32_t first,
-                                           uint32_t ng, uint64_t rec) {
+__device__ __forceinline__ void best_sweep(const BestArgs &A, const PairScan &P, const int32_t *pos, uint32_t lane,
+                                           uint32_t first, uint32_t ng, uint64_t rec) {
     int32_t rs[NG], re[NG];
     BestLane<NG> b;
 #pragma unroll
@@ -118,12 +101,7 @@ __device__ __forceinline__ void best_sweep(const BestArgs &A, const BestPair &P,
         b.window[r] = UINT32_MAX;
         b.n[r] = 0;
     }
-    for (uint32_t c0 = 0; c0 < P.nwin; c0 += 64 * kHitChunks) {
-        const uint32_t nch = (P.nwin - c0 + 63) / 64;
-        if (nch >= 3) best_chunks<kHitChunks, NG>(P, c0, lane, rs, re, b);  // (a 3-chunk tail scores one chunk of window 0)
-        else if (nch == 2) best_chunks<2, NG>(P, c0, lane, rs, re, b);
-        else best_chunks<1, NG>(P, c0, lane, rs, re, b);
-    }
+    WALK_CHUNKS(P.nwin, c0, (best_chunks<NCH, NG>(P, pos, c0, lane, rs, re, b)));
 #pragma unroll
     for (int r = 0; r < NG; r++) {
         if ((uint32_t)r >= ng) break;  // (wave-uniform)
@@ -144,104 +122,43 @@ __device__ __forceinline__ void best_sweep(const BestArgs &A, const BestPair &P,
 // Grid: ceil(n_haps * n_strands / kHitWaves) workgroups of kHitBlock threads.
 __global__ __launch_bounds__(kHitBlock) void scan_best_kernel(BestArgs A) {
     __shared__ int32_t s_rows[kHitWaves][kHitDiInts];
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t n_pairs = (uint64_t)A.n_haps * A.n_strands;
-    const uint64_t pl = (uint64_t)blockIdx.x * kHitWaves + wave;
-    const bool active = pl < n_pairs;
-    const uint64_t p = active ? pl : n_pairs - 1;
-    const uint32_t k = (uint32_t)(p / A.n_strands);
-    const uint32_t sidx = (uint32_t)(p - (uint64_t)k * A.n_strands);
-    CStrand &S = ((CStrand *)A.strands)[sidx];
-    const uint32_t kind = S.kind, L = S.len, w_off = S.w_off;
-    const bool di = kind == TFBS_KIND_DIPWM;
-    if (di) stage_dinuc_rows(s_rows[wave], A.weights, w_off, L, lane);
-    __syncthreads();
-    if (!active) return;
-    const uint32_t hid = A.hap_ids[k];
-    const DevHap hm = A.haps[hid];
+    const PairHead H = pair_head(A.src, 0, A.n_haps, s_rows);
+    if (!H.active) return;
+    PAIR_OPEN(A.src, H, A.hap_ids, hid, hm, P);  // (nwin 0: every record is the empty one)
     const DevRegion rg = A.regions[hm.region];
     const uint32_t n_inner = __builtin_amdgcn_readfirstlane(rg.n_inner);
     const uint32_t inner_off = __builtin_amdgcn_readfirstlane(rg.inner_off);
-    const bool scored = L != 0 && hm.len >= L && (kind == TFBS_KIND_PWM || di);
-    const uint32_t nwin = scored ? hm.len - L + 1 : 0;  // (0: every record is the empty one)
-    const uint32_t *W = A.words + hm.word_off;
-    const uint32_t *M = (hm.flags & HAP_HAS_N) ? A.nmask + hm.nmask_off : nullptr;
     const int32_t *pos = (hm.flags & HAP_HAS_POS) ? A.posrel + hm.pos_off : nullptr;
-    CInt4 *wq = (CInt4 *)(A.weights + w_off);
-    const BestPair P{W, M, pos, wq, s_rows[wave], L, nwin, di};
-    const uint64_t rec0 = A.hap_off[k] + (uint64_t)sidx * n_inner;
+    const uint32_t lane = H.lane;
+    const uint64_t rec0 = A.hap_off[H.k] + (uint64_t)H.sidx * n_inner;
     for (uint32_t g0 = 0; g0 < n_inner; g0 += kBestRanges) {
         const uint32_t ng = min((uint32_t)kBestRanges, n_inner - g0);
-        if (ng == 1) best_sweep<1>(A, P, lane, inner_off + g0, ng, rec0 + g0);
-        else if (ng == 2) best_sweep<2>(A, P, lane, inner_off + g0, ng, rec0 + g0);
-        else best_sweep<kBestRanges>(A, P, lane, inner_off + g0, ng, rec0 + g0);
+        if (ng == 1) best_sweep<1>(A, P, pos, lane, inner_off + g0, ng, rec0 + g0);
+        else if (ng == 2) best_sweep<2>(A, P, pos, lane, inner_off + g0, ng, rec0 + g0);
+        else best_sweep<kBestRanges>(A, P, pos, lane, inner_off + g0, ng, rec0 + g0);
     }
 }
 
 }  // namespace
 
-struct BestState {
-    Buf<DevHitStrand> strands;
-    Buf<int32_t> weights;
-    uint32_t n_strands = 0;
-    Buf<uint32_t> hap_ids;
+struct BestState : PairState {  // host: a chunk's records, copied back
     Buf<uint64_t> hap_off;
     Buf<DevBestRec> recs;
-    PinnedBytes host;  // a chunk's records, copied back
-    hipEvent_t ev[2] = {};
     double ms[2] = {0, 0};
+    ~BestState() { hap_off.release(); recs.release(); }
 };
 
-void best_state_destroy(BestState *s) {
-    if (!s) return;
-    s->strands.release(); s->weights.release(); s->hap_ids.release(); s->hap_off.release(); s->recs.release();
-    for (hipEvent_t e : s->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete s;
-}
+void best_state_destroy(BestState *s) { delete s; }
 
 void best_last_ms(const BestState *s, double out[2]) {
     for (int k = 0; k < 2; k++) out[k] = s ? s->ms[k] : 0.0;
 }
 
-namespace {
-
-int best_first_use(BestState **state, const Patterns &P, hipStream_t stream) {
-    if (*state) return TFBS_OK;
-    BestState *s = new BestState();
-    HitTables T;
-    build_hit_tables(P, &T);
-    s->n_strands = (uint32_t)T.strands.size();
-    int rc;
-    if ((rc = s->strands.ensure(T.strands.size())) || (rc = s->weights.ensure(T.weights.size() + 4))) {
-        best_state_destroy(s);
-        return rc;
-    }
-    hipError_t e = hipSuccess;
-    if (!T.strands.empty())
-        e = hipMemcpyAsync(s->strands.p, T.strands.data(), T.strands.size() * sizeof(DevHitStrand),
-                           hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess && !T.weights.empty())
-        e = hipMemcpyAsync(s->weights.p, T.weights.data(), T.weights.size() * 4, hipMemcpyHostToDevice, stream);
-    for (hipEvent_t &ev : s->ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // (T goes out of scope)
-    if (e != hipSuccess) {
-        best_state_destroy(s);
-        return fail(TFBS_E_HIP, std::string("best-site tables: ") + hipGetErrorString(e));
-    }
-    *state = s;
-    return TFBS_OK;
-}
-
-}  // namespace
-
-int best_run(BestState **state, int device, void *stream_, const Patterns &P, const BestImage &img, const Batch &B,
+int best_run(BestState **state, int device, void *stream_, const Patterns &P, const ScanImage &img, const Batch &B,
              size_t r0, size_t r1, std::vector<tfbs_best> *out) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HITS_TRY(hipSetDevice(device));
-    if (int rc = best_first_use(state, P, stream)) return rc;
+    if (int rc = first_use(state, P, stream, 2, "best-site tables")) return rc;
     BestState &S = **state;
     S.ms[0] = S.ms[1] = 0;
     const uint64_t ns = S.n_strands;
@@ -263,12 +180,7 @@ int best_run(BestState **state, int device, void *stream_, const Patterns &P, co
     auto recs_of = [&](uint32_t id) { return ns * (uint64_t)B.rh[B.haps[id].region].ranges.size(); };
 
     BestArgs A{};
-    A.strands = S.strands.p;
-    A.weights = S.weights.p;
-    A.n_strands = (uint32_t)ns;
-    A.haps = img.haps;
-    A.words = img.words;
-    A.nmask = img.nmask;
+    A.src = S.src(img);
     A.posrel = img.posrel;
     A.regions = img.regions;
     A.inner = img.inner;
@@ -330,11 +242,7 @@ int best_run(BestState **state, int device, void *stream_, const Patterns &P, co
                     o.score = q->score;
                     o.reserved = 0;
                     o.start = o.end = 0;
-                    if (q->n_windows) {
-                        const int64_t rel = (hm.flags & HAP_HAS_POS) ? B.posrel[hm.pos_off + q->window] : (int64_t)q->window;
-                        o.start = R.es + (uint64_t)rel;
-                        o.end = o.start + P.pats[p].len - 1;
-                    }
+                    if (q->n_windows) site_range(B, P, R, hm, p, q->window, &o.start, &o.end);
                 }
         }
         S.ms[1] += now_ms() - t0;

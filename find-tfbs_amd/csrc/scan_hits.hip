@@ -8,15 +8,9 @@
 // lists, no diff runs, no reuse between haplotypes.  Brute force is the point: the list
 // is a second opinion on the count path at any size.
 //
-//  * A wave owns one (haplotype, strand) pair; its lanes are 64 consecutive windows and
-//    it walks the 64-window chunks in ascending order.  The strand is wave-uniform: a
-//    mono column's four weights come through one scalar load and three selects, a
-//    dinucleotide strand's rows (at most 31 x 16 ints) sit in the wave's LDS slice,
-//    where the 16 entries of a row lie on 16 banks (lanes on one entry broadcast).
-//  * A lane takes the bases of its window 16 at a time: two packed words and two N-mask
-//    words funnel-shifted to the window's phase.  It has up to four chunks' windows in
-//    flight: their words are loaded together and a column's weights are fetched once
-//    (hit_score.hpp: the scoring code is scan_best.hip's too).
+//  * The pair a wave owns, the kernel's prologue, the walk over the pair's windows and the
+//    scoring are hit_score.hpp's, as they are scan_best.hip's; so is the drivers' common
+//    state, which uploads the tables that build_hit_tables makes here.
 //  * Two passes run the same scoring code.  The count pass stores each pair's hits; an
 //    exclusive u64 scan over the pairs, haplotype-major, turns them into offsets; the
 //    fill pass places each chunk's hits behind the pair's offset with a ballot and a
@@ -25,25 +19,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
-#include <cstdlib>
 #include <cstring>
-#include <string>
+#include <vector>
 
 #include "hit_score.hpp"
-#include "hits.hpp"
-#include "scan.hpp"
 
 namespace tfbs {
 namespace {
 
 struct HitsArgs {
-    const DevHitStrand *strands;
-    const int32_t *weights;
-    uint32_t n_strands;
-    const DevHap *haps;
-    const uint32_t *words;
-    const uint32_t *nmask;
+    PairSrc src;
     const uint32_t *hap_ids;  // the chunk's haplotypes (batch indices)
     // pair p = chunk haplotype k * n_strands + strand.  The count pass stores the pair's
     // hits at off[p]; after the exclusive scan over the chunk's pairs + 1 values, off[p]
@@ -56,38 +41,30 @@ struct HitsArgs {
     DevHitRec *recs;
 };
 
-struct HitsPair {  // what a wave knows of its pair (wave-uniform)
-    const uint32_t *W, *M;
-    CInt4 *wq;
-    const int32_t *rows;
-    uint32_t L, nwin, hid, sidx;
+struct HitsPair {  // a record's fields besides the window and the score, and the threshold
+    uint32_t hid, sidx;
     int32_t min_score;
-    bool di;
 };
 
 // NCH 64-window chunks from window c0, in ascending order: scored together, counted or
 // placed chunk by chunk.
 template <bool FILL, int NCH>
-__device__ __forceinline__ void hits_chunks(const HitsArgs &A, const HitsPair &P, uint32_t c0, uint32_t lane,
-                                            uint64_t &at) {
+__device__ __forceinline__ void hits_chunks(const HitsArgs &A, const PairScan &P, const HitsPair &Q, uint32_t c0,
+                                            uint32_t lane, uint64_t &at) {
     uint32_t ii[NCH], s[NCH];
 #pragma unroll
-    for (int c = 0; c < NCH; c++) {
-        const uint32_t i = c0 + 64 * c + lane;
-        ii[c] = i < P.nwin ? i : 0;  // (window 0 exists: reads stay inside the haplotype's pads)
-    }
-    if (P.di) score_dinuc<NCH>(P.W, P.M, ii, P.L, P.rows, s);
-    else score_mono<NCH>(P.W, P.M, ii, P.L, P.wq, s);
+    for (int c = 0; c < NCH; c++) ii[c] = scored_window(P, c0 + 64 * c + lane);
+    SCORE_WINDOWS(NCH, P, ii, s);
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
         const uint32_t i = c0 + 64 * c + lane;
-        const bool hit = i < P.nwin && (int32_t)s[c] > P.min_score;
+        const bool hit = i < P.nwin && (int32_t)s[c] > Q.min_score;
         const uint64_t mask = __ballot(hit);
         if (FILL && hit) {
             const uint32_t rank =
                 __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
             const uint64_t r = at + rank;
-            if (r < A.rec_cap) A.recs[r] = DevHitRec{P.hid, P.sidx, i, (int32_t)s[c]};
+            if (r < A.rec_cap) A.recs[r] = DevHitRec{Q.hid, Q.sidx, i, (int32_t)s[c]};
         }
         at += (uint32_t)__popcll(mask);
     }
@@ -97,41 +74,16 @@ __device__ __forceinline__ void hits_chunks(const HitsArgs &A, const HitsPair &P
 template <bool FILL>
 __global__ __launch_bounds__(kHitBlock) void scan_hits_kernel(HitsArgs A) {
     __shared__ int32_t s_rows[kHitWaves][kHitDiInts];
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t n_pairs = (uint64_t)(A.k1 - A.k0) * A.n_strands;
-    const uint64_t pl = (uint64_t)blockIdx.x * kHitWaves + wave;
-    const bool active = pl < n_pairs;
-    const uint64_t p = (uint64_t)A.k0 * A.n_strands + (active ? pl : n_pairs - 1);
-    const uint32_t k = (uint32_t)(p / A.n_strands);
-    const uint32_t sidx = (uint32_t)(p - (uint64_t)k * A.n_strands);
-    CStrand &S = ((CStrand *)A.strands)[sidx];
-    const uint32_t kind = S.kind, L = S.len, w_off = S.w_off;
-    const int32_t min_score = S.min_score;
-    const bool di = kind == TFBS_KIND_DIPWM;
-    if (di) {  // (L <= kDiMaxLen: check_dipwm_length)
-        stage_dinuc_rows(s_rows[wave], A.weights, w_off, L, lane);
-    }
-    __syncthreads();
-    if (!active) return;
-    if (!FILL && pl == 0 && lane == 0) A.off[(uint64_t)A.n_chunk * A.n_strands] = 0;  // the total's slot
-    if (FILL && A.off[p + 1] == A.off[p]) return;  // the count pass found no hit: nothing to place
-    const uint32_t hid = A.hap_ids[k];
-    const DevHap hm = A.haps[hid];
-    const bool scored = L != 0 && hm.len >= L && (kind == TFBS_KIND_PWM || di);
-    const uint32_t nwin = scored ? hm.len - L + 1 : 0;
-    const uint32_t *W = A.words + hm.word_off;
-    const uint32_t *M = (hm.flags & HAP_HAS_N) ? A.nmask + hm.nmask_off : nullptr;
-    CInt4 *wq = (CInt4 *)(A.weights + w_off);
-    const HitsPair P{W, M, wq, s_rows[wave], L, nwin, hid, sidx, min_score, di};
-    uint64_t at = FILL ? A.off[p] - A.rec_base : 0;  // records of the pair so far (fill: their place)
-    for (uint32_t c0 = 0; c0 < nwin; c0 += 64 * kHitChunks) {
-        const uint32_t nch = (nwin - c0 + 63) / 64;
-        if (nch >= 3) hits_chunks<FILL, kHitChunks>(A, P, c0, lane, at);  // (a 3-chunk tail scores one chunk of window 0)
-        else if (nch == 2) hits_chunks<FILL, 2>(A, P, c0, lane, at);
-        else hits_chunks<FILL, 1>(A, P, c0, lane, at);
-    }
-    if (!FILL && lane == 0) A.off[p] = at;
+    const PairHead H = pair_head(A.src, A.k0, A.k1, s_rows);
+    // before any load of the haplotype: the fill pass's time is the pairs without a hit returning at once
+    if (!H.active) return;
+    if (!FILL && H.pl == 0 && H.lane == 0) A.off[(uint64_t)A.n_chunk * A.src.n_strands] = 0;  // the total's slot
+    if (FILL && A.off[H.p + 1] == A.off[H.p]) return;  // the count pass found no hit: nothing to place
+    PAIR_OPEN(A.src, H, A.hap_ids, hid, hm, P);
+    const HitsPair Q{hid, H.sidx, H.min_score};
+    uint64_t at = FILL ? A.off[H.p] - A.rec_base : 0;  // records of the pair so far (fill: their place)
+    WALK_CHUNKS(P.nwin, c0, (hits_chunks<FILL, NCH>(A, P, Q, c0, H.lane, at)));
+    if (!FILL && H.lane == 0) A.off[H.p] = at;
 }
 
 // hap_off[k] = off[k * n_strands], k = 0 .. n_haps: the records before chunk haplotype k.
@@ -165,26 +117,14 @@ void build_hit_tables(const Patterns &P, HitTables *out) {
     }
 }
 
-struct HitsState {
-    Buf<DevHitStrand> strands;
-    Buf<int32_t> weights;
-    uint32_t n_strands = 0;
-    Buf<uint32_t> hap_ids;
+struct HitsState : PairState {  // host: hap_off, then the records, copied back
     Buf<uint64_t> off, tmp, hap_off;
     Buf<DevHitRec> recs;
-    PinnedBytes host;  // hap_off, then the records, copied back
-    hipEvent_t ev[3] = {};
     double ms[4] = {0, 0, 0, 0};
+    ~HitsState() { off.release(); tmp.release(); hap_off.release(); recs.release(); }
 };
 
-void hits_state_destroy(HitsState *s) {
-    if (!s) return;
-    s->strands.release(); s->weights.release(); s->hap_ids.release(); s->off.release(); s->tmp.release();
-    s->hap_off.release(); s->recs.release();
-    for (hipEvent_t e : s->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete s;
-}
+void hits_state_destroy(HitsState *s) { delete s; }
 
 void hits_last_ms(const HitsState *s, double out[4]) {
     for (int k = 0; k < 4; k++) out[k] = s ? s->ms[k] : 0.0;
@@ -199,41 +139,13 @@ uint64_t chunk_fixed_bytes(uint64_t nh, uint64_t ns) {
     return 8 * np + 8 * scan_tmp_words(np) + 4 * nh + 8 * (nh + 1);
 }
 
-int first_use(HitsState **state, const Patterns &P, hipStream_t stream) {
-    if (*state) return TFBS_OK;
-    HitsState *s = new HitsState();
-    HitTables T;
-    build_hit_tables(P, &T);
-    s->n_strands = (uint32_t)T.strands.size();
-    int rc;
-    if ((rc = s->strands.ensure(T.strands.size())) || (rc = s->weights.ensure(T.weights.size() + 4))) {
-        hits_state_destroy(s);
-        return rc;
-    }
-    hipError_t e = hipSuccess;
-    if (!T.strands.empty())
-        e = hipMemcpyAsync(s->strands.p, T.strands.data(), T.strands.size() * sizeof(DevHitStrand),
-                           hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess && !T.weights.empty())
-        e = hipMemcpyAsync(s->weights.p, T.weights.data(), T.weights.size() * 4, hipMemcpyHostToDevice, stream);
-    for (hipEvent_t &ev : s->ev)
-        if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // (T goes out of scope)
-    if (e != hipSuccess) {
-        hits_state_destroy(s);
-        return fail(TFBS_E_HIP, std::string("hit tables: ") + hipGetErrorString(e));
-    }
-    *state = s;
-    return TFBS_OK;
-}
-
 }  // namespace
 
-int hits_run(HitsState **state, int device, void *stream_, const Patterns &P, const HitsImage &img,
+int hits_run(HitsState **state, int device, void *stream_, const Patterns &P, const ScanImage &img,
              const Batch &B, size_t r0, size_t r1, std::vector<tfbs_hit> *out, uint64_t *per_region) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     HITS_TRY(hipSetDevice(device));
-    if (int rc = first_use(state, P, stream)) return rc;
+    if (int rc = first_use(state, P, stream, 3, "hit tables")) return rc;
     HitsState &S = **state;
     for (double &m : S.ms) m = 0;
     if (per_region) std::fill(per_region, per_region + (r1 - r0), 0ull);
@@ -247,12 +159,7 @@ int hits_run(HitsState **state, int device, void *stream_, const Patterns &P, co
     const uint64_t budget = scratch_budget("TFBS_HITS_SCRATCH_MB", 256.0);  // read at the call
 
     HitsArgs A{};
-    A.strands = S.strands.p;
-    A.weights = S.weights.p;
-    A.n_strands = (uint32_t)ns;
-    A.haps = img.haps;
-    A.words = img.words;
-    A.nmask = img.nmask;
+    A.src = S.src(img);
     int rc;
     for (size_t start = 0; start < ids.size();) {
         // the chunk: as many haplotypes as the budget's counters allow, one at least
@@ -335,9 +242,7 @@ int hits_run(HitsState **state, int device, void *stream_, const Patterns &P, co
                     o.haplotype = q.hap - R.hap_begin;
                     o.pattern = q.pattern;
                     o.window = q.window;
-                    const int64_t rel = (hm.flags & HAP_HAS_POS) ? B.posrel[hm.pos_off + q.window] : (int64_t)q.window;
-                    o.start = R.es + (uint64_t)rel;
-                    o.end = o.start + P.pats[q.pattern].len - 1;
+                    site_range(B, P, R, hm, q.pattern, q.window, &o.start, &o.end);
                     o.score = q.score;
                     o.reserved = 0;
                 }
