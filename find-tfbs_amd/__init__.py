@@ -42,6 +42,15 @@ BEST_DTYPE = [("region", "<u4"), ("haplotype", "<u4"), ("pattern", "<u4"), ("ran
 BEST_MODES = {"all": 0, "diff": 1}
 BEST_HEADER = ("#chrom\tregion\tbed\tinner_start\tinner_end\tname\tpattern_id\thaplotype\tcarriers\tkind\tstrand\t"
                "start\tend\tscore\tdelta\tcarrier_ids\n")
+# tfbs_effect as a numpy dtype (RegionBatch.effects), a record's statuses, the effect TSV's modes and header line
+EFFECT_DTYPE = [("region", "<u4"), ("variant", "<u4"), ("pattern", "<u4"), ("status", "<u4"), ("n_ref", "<u4"),
+                ("ref_score", "<i4"), ("ref_window", "<u4"), ("n_alt", "<u4"), ("alt_score", "<i4"),
+                ("alt_window", "<u4"), ("ref_start", "<u8"), ("ref_end", "<u8"), ("alt_start", "<u8"),
+                ("alt_end", "<u8")]
+VAR_SCORED, VAR_MULTIALLELIC, VAR_NO_CARRIER, VAR_UNPATCHED = 0, 1, 2, 3
+EFFECT_MODES = {"sites": 0, "all": 1}
+EFFECTS_HEADER = ("#chrom\tregion\tvariant\tpos\tref\talt\tcarriers\tkind\tname\tpattern_id\tstrand\tref_start\t"
+                  "ref_end\tref_score\talt_start\talt_end\talt_score\tdelta\n")
 
 Range = namedtuple("Range", "start end")  # range.rs:4-8, inclusive
 NucleotidePos = namedtuple("NucleotidePos", "nuc pos")  # types.rs:23-27 (nuc as 'A'..'N')
@@ -341,6 +350,13 @@ class Scanner:
         check(lib().tfbs_ctx_last_best_ms(self.h, out))
         return out[0], out[1]
 
+    def last_effects_ms(self):
+        """tfbs_ctx_last_effects_ms: (host prep ms, kernel ms from HIP events, copy-back + host ms)
+        of the last effects()."""
+        out = (C.c_double * 3)()
+        check(lib().tfbs_ctx_last_effects_ms(self.h, out))
+        return out[0], out[1], out[2]
+
 
 def matches(pattern, haplotype, haplotype_ids=(), verbose=False):
     """pattern.rs:141-171 for one Pattern on one haplotype (GPU; builds a one-pattern Scanner)."""
@@ -356,7 +372,8 @@ class RegionBatch:
 
     VECTOR_END = -2147483647
 
-    def __init__(self, patterns, n_samples, keep_membership=True, window_lmax=None, build_device=None):
+    def __init__(self, patterns, n_samples, keep_membership=True, window_lmax=None, build_device=None,
+                 keep_variants=False):
         self.patterns = patterns
         self.n_samples = n_samples
         self.h = C.c_void_p()
@@ -366,6 +383,12 @@ class RegionBatch:
             check(lib().tfbs_batch_set_window_lmax(self.h, window_lmax))
         if build_device is not None:  # haplotype grouping on a device (tfbs_batch_set_build_device)
             check(lib().tfbs_batch_set_build_device(self.h, build_device))
+        if keep_variants:  # the regions keep their records (tfbs_batch_keep_variants): variants(), effects()
+            self.keep_variants(True)
+
+    def keep_variants(self, on=True):
+        """tfbs_batch_keep_variants: before the first region."""
+        check(lib().tfbs_batch_keep_variants(self.h, 1 if on else 0))
 
     def build_stats(self):
         """(regions grouped on the device, regions built on the host)."""
@@ -733,6 +756,59 @@ class RegionBatch:
         counts = mine["n_windows"].reshape(nh, npat, nr)
         return scores[memb], counts[memb]
 
+    def variants(self, region):
+        """tfbs_batch_region_variant: the region's records in BCF order as (pos, ref, alt, n_alleles,
+        carriers, status) -- ref / alt as ACGTN text, carriers the number of carrier ids, status one
+        of VAR_SCORED, VAR_MULTIALLELIC, VAR_NO_CARRIER, VAR_UNPATCHED.  Needs keep_variants."""
+        out = []
+        for v in range(self.region_stats(region)[1]):
+            pos = C.c_uint64()
+            nr, na = C.c_size_t(), C.c_size_t()
+            nal, car, st = C.c_uint32(), C.c_uint32(), C.c_uint32()
+            rc = lib().tfbs_batch_region_variant(self.h, region, v, None, None, None, 0, C.byref(nr), C.byref(na),
+                                                 None, None, None)
+            if rc != 0 and nr.value == 0 and na.value == 0:
+                check(rc)
+            cap = max(nr.value, na.value)
+            ref, alt = (C.c_uint8 * max(1, cap))(), (C.c_uint8 * max(1, cap))()
+            check(lib().tfbs_batch_region_variant(self.h, region, v, C.byref(pos), ref, alt, cap, C.byref(nr),
+                                                  C.byref(na), C.byref(nal), C.byref(car), C.byref(st)))
+            out.append((pos.value, "".join("ACGTN"[c] for c in ref[:nr.value]),
+                        "".join("ACGTN"[c] for c in alt[:na.value]), nal.value, car.value, st.value))
+        return out
+
+    def effects(self, scanner, r0=None, r1=None):
+        """tfbs_batch_effects: per (record, pattern strand) of regions [r0, r1) the best site touching
+        the record on the REF and on the ALT allele, on a scanner made from this batch's patterns
+        (no upload, no scan needed): a dense numpy structured array (EFFECT_DTYPE) sorted by
+        (region, variant, pattern); a region's block reshapes to [n_variants][n_patterns]."""
+        import numpy as np
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_effects(scanner.h, self.h, 0 if r0 is None else r0,
+                                       self.num_regions if r1 is None else r1, C.byref(p), C.byref(n)))
+        try:
+            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_effect)), dtype=EFFECT_DTYPE).copy()
+        finally:
+            lib().tfbs_free(p)
+        return out
+
+    def effects_tsv(self, eff, chromosome, mode="sites", header=False):
+        """tfbs_batch_effects_tsv: the TSV of an effects() result over whole regions; per record a
+        `var` line, then per pattern strand mode "sites": its `gain`, `loss` and `change` lines, or
+        "all": `same` and `none` lines too; header: EFFECTS_HEADER first."""
+        import numpy as np
+        eff = np.ascontiguousarray(eff, dtype=EFFECT_DTYPE)
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_effects_tsv(self.h, eff.ctypes.data_as(C.c_void_p), len(eff), _u(chromosome),
+                                           EFFECT_MODES[mode], C.byref(p), C.byref(n)))
+        try:
+            text = C.string_at(p, n.value).decode()
+        finally:
+            lib().tfbs_free(p)
+        return (EFFECTS_HEADER if header else "") + text
+
     def rows(self, chromosome, min_maf=0, fake_position=1):
         """Rows for every region (main.rs:415-429); returns (text, next fake_position)."""
         fp = C.c_uint32(fake_position)
@@ -801,13 +877,16 @@ def select_inner_peaks(merged, beds):
 def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_file, pwm_threshold_directory,
         pwm_threshold, wanted_pwms, output_file, forward_only=False, run_tabix=False, min_maf=0, threads=1,
         after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None,
-        hits_output=None, hits_mode="diff", best_output=None, best_mode="diff"):
+        hits_output=None, hits_mode="diff", best_output=None, best_mode="diff", effects_output=None,
+        effects_mode="sites"):
     """main.rs:234-393 `run` with the reference's argument order; writes the BGZF VCF.
     devices: list of HIP devices; batch g of merged regions runs on devices[g % n] (same
     text for any list; a device may repeat).  hits_output: also write every region's hit
     list there as BGZF TSV (HITS_HEADER, then RegionBatch.hits_tsv's lines in hits_mode "all"
     or "diff"); best_output: the same for every region's best sites (BEST_HEADER, then
-    RegionBatch.best_tsv's lines in best_mode); the main output does not change."""
+    RegionBatch.best_tsv's lines in best_mode); effects_output: the same for every region's variant
+    effects (EFFECTS_HEADER, then RegionBatch.effects_tsv's lines in effects_mode "sites" or "all");
+    the main output does not change."""
     a = _capi.tfbs_run_args()
     keep = [_u(x) if x is not None else None for x in (chromosome, bcf, ",".join(bed_files), reference_genome_file,
                                                         wanted_samples, pwm_file, pwm_threshold_directory,
@@ -833,7 +912,12 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     bo = _u(best_output) if best_output is not None else None
     a.best_output = bo
     a.best_mode = BEST_MODES[best_mode]
-    check(lib().tfbs_run(C.byref(a)))
+    x = _capi.tfbs_run_ext()
+    x.size = C.sizeof(_capi.tfbs_run_ext)
+    eo = _u(effects_output) if effects_output is not None else None
+    x.effects_output = eo
+    x.effects_mode = EFFECT_MODES[effects_mode]
+    check(lib().tfbs_run_ex(C.byref(a), C.byref(x)))
 
 
 class BcfReader:

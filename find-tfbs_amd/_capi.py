@@ -66,6 +66,17 @@ class tfbs_best(C.Structure):
                 ("start", C.c_uint64), ("end", C.c_uint64)]
 
 
+class tfbs_effect(C.Structure):
+    _fields_ = [("region", C.c_uint32), ("variant", C.c_uint32), ("pattern", C.c_uint32), ("status", C.c_uint32),
+                ("n_ref", C.c_uint32), ("ref_score", C.c_int32), ("ref_window", C.c_uint32),
+                ("n_alt", C.c_uint32), ("alt_score", C.c_int32), ("alt_window", C.c_uint32),
+                ("ref_start", C.c_uint64), ("ref_end", C.c_uint64), ("alt_start", C.c_uint64), ("alt_end", C.c_uint64)]
+
+
+class tfbs_run_ext(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("effects_output", C.c_char_p), ("effects_mode", C.c_int)]
+
+
 # (name, restype, argtypes) for every symbol in include/tfbs_amd.h
 SIGNATURES = [
     ("tfbs_strerror", C.c_char_p, [C.c_int]),
@@ -163,10 +174,18 @@ SIGNATURES = [
     ("tfbs_ctx_last_best_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
     ("tfbs_batch_best_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_size_t)]),
+    ("tfbs_batch_keep_variants", C.c_int, [vp, C.c_int]),
+    ("tfbs_batch_region_variant", C.c_int, [vp, C.c_size_t, C.c_size_t, u64p, u8p, u8p, C.c_size_t,
+                                            C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), u32p, u32p, u32p]),
+    ("tfbs_batch_effects", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    ("tfbs_ctx_last_effects_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
+    ("tfbs_batch_effects_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_size_t)]),
     ("tfbs_free", None, [C.c_void_p]),
     ("tfbs_counts_as_genotypes", C.c_int, [u32p, u32p, C.c_size_t, u32p, C.c_char_p, C.c_size_t, C.c_char_p,
                                            C.c_size_t]),
     ("tfbs_run", C.c_int, [C.c_void_p]),
+    ("tfbs_run_ex", C.c_int, [C.c_void_p, C.c_void_p]),
     ("tfbs_bcf_open", C.c_int, [C.c_char_p, C.POINTER(vp)]),
     ("tfbs_inflate_raw", C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     ("tfbs_bcf_close", None, [vp]),

@@ -111,6 +111,11 @@ int patch(uint64_t rs, uint64_t re, std::vector<const Record *> diffs, const uin
     return rc;
 }
 
+int patch_runs(uint64_t rs, uint64_t re, const std::vector<const Record *> &diffs, const uint8_t *ref,
+               uint64_t ref_start, size_t n_ref, std::vector<uint8_t> &nucs, PosRuns &pos) {
+    return patch_window(rs, re, diffs, RefWindow{ref, ref_start, n_ref}, nucs, pos);
+}
+
 // load_haplotypes' HashMap<(nucs, pos), group> insert (haplotype.rs:84): the
 // patched sequences of a region by a hash of their bases (8 at a time) and of their
 // runs of consecutive positions, in a flat open-addressing table; a sequence equal
@@ -627,6 +632,34 @@ static int mask_finish(const Batch &B, RegionInput &I, RegionBuilt &out, const s
     return TFBS_OK;
 }
 
+// A region's inputs as a batch with keep_variants remembers them.  A record's status in the
+// specification's order: multi-allelic, no carrier, refused when patched alone, scored.
+static void keep_inputs(const RegionH &R, const RegionInput &I, KeptRegion &K) {
+    K.ref = I.ref;
+    K.vars.clear();
+    K.vars.reserve(I.recs.size());
+    const RefWindow ref{I.ref.data(), R.es, I.ref.size()};
+    std::vector<const Record *> one(1);
+    std::vector<uint8_t> nuc;
+    for (const Record &r : I.recs) {
+        KeptVariant v;
+        v.pos = r.pos;
+        v.n_alleles = r.n_alleles;
+        v.carriers = (uint32_t)r.carriers.size();
+        v.ref = r.ref;
+        v.alt = r.alt;
+        if (r.n_alleles != 2) v.status = TFBS_VAR_MULTIALLELIC;
+        else if (r.carriers.empty()) v.status = TFBS_VAR_NO_CARRIER;
+        else {
+            one[0] = &r;
+            nuc.clear();
+            PosRuns pos;
+            v.status = patch_window(R.es, R.ee, one, ref, nuc, pos) ? TFBS_VAR_UNPATCHED : TFBS_VAR_SCORED;
+        }
+        K.vars.push_back(std::move(v));
+    }
+}
+
 int build_regions(Batch &B, std::vector<RegionInput> &ins, uint32_t threads, std::vector<RegionBuilt> &built,
                   double *build_s) {
     const size_t n = ins.size();
@@ -760,6 +793,9 @@ int build_regions(Batch &B, std::vector<RegionInput> &ins, uint32_t threads, std
         });
         lap(4);
     }
+    // (every build path leaves a region's reference codes and records in ins[j])
+    if (B.keep_variants && std::all_of(rcs.begin(), rcs.end(), [](int rc) { return rc == TFBS_OK; }))
+        par(n, [&](size_t j) { keep_inputs(built[j].R, ins[j], built[j].kept); });
     for (size_t j = 0; j < n; j++) {
         if (rcs[j]) return rcs[j];
         if (built[j].dev || built[j].dev_grouped) B.dev_regions++;
@@ -1154,6 +1190,7 @@ void commit_regions(Batch &B, std::vector<RegionBuilt> &built, uint32_t threads)
         B.scan_windows += swin[j];
         B.scan_cell_ops += scells[j];
         B.rh.push_back(std::move(built[j].R));
+        if (B.keep_variants) B.kept.push_back(std::move(built[j].kept));
     }
 }
 
@@ -1237,6 +1274,35 @@ int tfbs_batch_set_window_lmax(tfbs_batch *b, uint32_t lmax) {
     if (lmax < b->b.pats->max_length()) return tfbs::fail(TFBS_E_ARG, "window L_max below the longest pattern");
     if (!b->b.rh.empty() || b->b.open) return tfbs::fail(TFBS_E_STATE, "regions already added");
     b->b.window_lmax = lmax;
+    return TFBS_OK;
+}
+
+int tfbs_batch_keep_variants(tfbs_batch *b, int on) {
+    if (!b) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (!b->b.rh.empty() || b->b.open) return tfbs::fail(TFBS_E_STATE, "regions already added");
+    b->b.keep_variants = on != 0;
+    return TFBS_OK;
+}
+
+int tfbs_batch_region_variant(const tfbs_batch *b, size_t region, size_t v, uint64_t *pos, uint8_t *ref, uint8_t *alt,
+                              size_t cap, size_t *n_ref, size_t *n_alt, uint32_t *n_alleles, uint32_t *carriers,
+                              uint32_t *status) {
+    if (!b || !n_ref || !n_alt) return tfbs::fail(TFBS_E_ARG, "null argument");
+    const Batch &B = b->b;
+    if (!B.keep_variants) return tfbs::fail(TFBS_E_STATE, "batch built without tfbs_batch_keep_variants");
+    if (region >= B.kept.size()) return tfbs::fail(TFBS_E_ARG, "bad region");
+    if (v >= B.kept[region].vars.size()) return tfbs::fail(TFBS_E_ARG, "bad variant index");
+    const tfbs::KeptVariant &k = B.kept[region].vars[v];
+    if (pos) *pos = k.pos;
+    if (n_alleles) *n_alleles = k.n_alleles;
+    if (carriers) *carriers = k.carriers;
+    if (status) *status = k.status;
+    *n_ref = k.ref.size();
+    *n_alt = k.alt.size();
+    if (std::max(k.ref.size(), k.alt.size()) > cap) return tfbs::fail(TFBS_E_ARG, "output capacity too small");
+    if ((!k.ref.empty() && !ref) || (!k.alt.empty() && !alt)) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (!k.ref.empty()) memcpy(ref, k.ref.data(), k.ref.size());
+    if (!k.alt.empty()) memcpy(alt, k.alt.data(), k.alt.size());
     return TFBS_OK;
 }
 

@@ -47,6 +47,20 @@ struct Record {  // one BCF record as load_diffs sees it (haplotype.rs:16-60)
     std::vector<uint32_t> carriers;  // haplotype ids carrying alt (2*sample + side)
 };
 
+// A record as a batch built with tfbs_batch_keep_variants remembers it (include/tfbs_amd.h,
+// "Variant effects"): what tfbs_batch_region_variant hands out and effects_run patches.
+struct KeptVariant {
+    uint64_t pos = 0;
+    uint32_t n_alleles = 2;
+    uint32_t carriers = 0;  // carrier ids
+    uint32_t status = 0;    // TFBS_VAR_*
+    std::vector<uint8_t> ref, alt;
+};
+struct KeptRegion {
+    std::vector<uint8_t> ref;  // the fetched reference codes, from es
+    std::vector<KeptVariant> vars;  // BCF order
+};
+
 struct InnerKey {   // one (bed, inner range) of select_inner_peaks (main.rs:62-72)
     uint32_t bed;
     uint64_t s, e;
@@ -182,6 +196,10 @@ struct Batch {
     std::vector<uint64_t> enc_code_off;        // per encoded key, + the end
 
     std::vector<RegionH> rh;
+    // tfbs_batch_keep_variants: each region's reference codes and records, one entry per
+    // region of rh (empty without it)
+    bool keep_variants = false;
+    std::vector<KeptRegion> kept;
     uint64_t windows = 0, eff_windows = 0, cell_ops = 0;
     // reference-window reuse (HAP_DEDUP, TFBS_DEDUP=0 turns it off): windows and
     // column lookups the scan executes (helper reference haplotypes included)
@@ -297,6 +315,7 @@ struct RegionBuilt {
     std::vector<uint32_t> snv_rel;
     std::vector<uint8_t> snv_alt;
     std::vector<uint8_t> ref;
+    KeptRegion kept;  // keep_variants: the region's inputs on their way to commit_regions
     size_t n_haps() const { return dev ? masks.size() : dist.size(); }
 };
 
@@ -308,8 +327,9 @@ int build_region(const Batch &B, RegionInput &&in, RegionBuilt &out);
 // commit_regions of chunk k runs on another thread, TFBS_PREP_OVERLAP): build_regions
 // writes only grouper, memb_allocs and the dev_ / host_ / patched_regions counters;
 // commit_regions writes rh, regions, inner, haps, words, nmask, posrel, druns,
-// hap_carriers, windows and the other scan / count totals.  Both only read the
-// batch's configuration (n_samples, dedup, dev_patch, the patterns).  A field written
+// hap_carriers, kept, windows and the other scan / count totals (a region's kept records
+// travel in its RegionBuilt).  Both only read the batch's configuration (n_samples,
+// dedup, dev_patch, keep_variants, the patterns).  A field written
 // by both would be a data race: keep the two sets disjoint
 // (tests/test_capi_cpu.py::test_prep_overlap_same_batch checks the digests).
 int build_regions(Batch &B, std::vector<RegionInput> &ins, uint32_t threads, std::vector<RegionBuilt> &built,
@@ -341,6 +361,9 @@ int make_record_ids(uint64_t pos, uint32_t n_alleles, const char *ref, const cha
 // [ref_start, ref_start + n_ref).  Diffs are pointers to records.
 int patch(uint64_t rs, uint64_t re, std::vector<const Record *> diffs, const uint8_t *ref, uint64_t ref_start,
           size_t n_ref, std::vector<uint8_t> &nucs, std::vector<uint64_t> &pos);
+// The same with the positions as runs.
+int patch_runs(uint64_t rs, uint64_t re, const std::vector<const Record *> &diffs, const uint8_t *ref,
+               uint64_t ref_start, size_t n_ref, std::vector<uint8_t> &nucs, PosRuns &pos);
 
 }  // namespace tfbs
 

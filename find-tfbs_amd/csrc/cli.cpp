@@ -1,4 +1,4 @@
-// find-tfbs-amd: the find-tfbs command line (main.rs:163-232) over tfbs_run.
+// find-tfbs-amd: the find-tfbs command line (main.rs:163-232) over tfbs_run_ex.
 // Long flags are the reference's; the short ones it binds twice (-n, -t,
 // main.rs:174/179, 177/181) are accepted in their first meaning only.
 #include <cstdio>
@@ -15,6 +15,7 @@ static void usage() {
             "       --pwm_names N1[,N2..] --pwm_file PWM --pwm_threshold_directory DIR --pwm_threshold T\n"
             "       [--dipwm_file DIPWM] [--hits_output FILE [--hits_mode all|diff]]\n"
             "       [--best_output FILE [--best_mode all|diff]]\n"
+            "       [--effects_output FILE [--effects_mode sites|all]]\n"
             "       [--forward_only] [--threads N] [--min_maf N] [--after_position P] [--samples FILE]\n"
             "       [--tabix] [--verbose] [--device D | --devices D1,D2,.. | --gpus N] [--regions_per_batch N]\n"
             "  --devices: one contiguous block of merged regions per listed HIP device (a device may repeat);\n"
@@ -28,7 +29,11 @@ static void usage() {
             "  --best_output FILE: also write how strongly each haplotype binds, as BGZF TSV: per (bed, inner range),\n"
             "  pattern_id and distinct haplotype the best-scoring site whatever the threshold (strand, range, score).\n"
             "  --best_mode all: one `best` line each; diff (default): `hap` lines, then where a haplotype's best\n"
-            "  score differs from the most carried haplotype's a `base` line and `alt` lines with the score's delta.\n");
+            "  score differs from the most carried haplotype's a `base` line and `alt` lines with the score's delta.\n"
+            "  --effects_output FILE: also write which variant does it, as BGZF TSV: per merged region and record a\n"
+            "  `var` line, then per pattern strand the best site touching the record on the REF and on the ALT allele\n"
+            "  (range, score) and the score's delta.  --effects_mode sites (default): the `gain`, `loss` and `change`\n"
+            "  lines (a side passes above the strand's threshold); all: `same` and `none` lines too.\n");
 }
 
 int main(int argc, char **argv) {
@@ -37,6 +42,10 @@ int main(int argc, char **argv) {
     a.threads = 1;
     a.hits_mode = TFBS_HITS_DIFF;
     a.best_mode = TFBS_BEST_DIFF;
+    tfbs_run_ext x;
+    memset(&x, 0, sizeof x);
+    x.size = (uint32_t)sizeof x;
+    x.effects_mode = TFBS_EFFECTS_SITES;
     bool have_thr = false;
     std::string gpus;
     for (int i = 1; i < argc; i++) {
@@ -73,6 +82,15 @@ int main(int argc, char **argv) {
                 return 2;
             }
             a.best_mode = m == "all" ? TFBS_BEST_ALL : TFBS_BEST_DIFF;
+        }
+        else if (k == "--effects_output") x.effects_output = val("--effects_output");
+        else if (k == "--effects_mode") {
+            const std::string m = val("--effects_mode");
+            if (m != "sites" && m != "all") {
+                fprintf(stderr, "error: --effects_mode is sites or all\n");
+                return 2;
+            }
+            x.effects_mode = m == "all" ? TFBS_EFFECTS_ALL : TFBS_EFFECTS_SITES;
         }
         else if (k == "--pwm_threshold_directory") a.pwm_threshold_dir = val(k.c_str());
         else if (k == "--pwm_threshold" || k == "-t") {
@@ -118,7 +136,7 @@ int main(int argc, char **argv) {
         usage();
         return 2;
     }
-    int rc = tfbs_run(&a);
+    int rc = tfbs_run_ex(&a, &x);
     if (rc) {
         fprintf(stderr, "find-tfbs-amd: %s (%s)\n", tfbs_last_error(), tfbs_strerror(rc));
         return 101;  // a Rust panic's exit status

@@ -287,6 +287,8 @@ struct tfbs_ctx {
     tfbs::HitsState *hits_state = nullptr;
     // best sites (tfbs_batch_best): the same, made by the first best call
     tfbs::BestState *best_state = nullptr;
+    // variant effects (tfbs_batch_effects): the same, made by the first effects call
+    tfbs::EffectsState *effects_state = nullptr;
 };
 
 namespace tfbs {
@@ -819,6 +821,8 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     ctx->hits_state = nullptr;
     tfbs::best_state_destroy(ctx->best_state);
     ctx->best_state = nullptr;
+    tfbs::effects_state_destroy(ctx->effects_state);
+    ctx->effects_state = nullptr;
     ctx->ref_count.release(); ctx->spill.release(); ctx->over.release(); ctx->spill_sorted.release();
     ctx->spill_bcnt.release(); ctx->spill_boff.release(); ctx->srcs.release();
     if (ctx->over_host) (void)hipHostFree(ctx->over_host);
@@ -2432,6 +2436,24 @@ int tfbs_batch_best(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_bes
 int tfbs_ctx_last_best_ms(const tfbs_ctx *ctx, double out[2]) {
     if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
     best_last_ms(ctx->best_state, out);
+    return TFBS_OK;
+}
+
+// Variant effects (scan_effects.hip): the batch need not be resident, only of the ctx's patterns.
+int tfbs_batch_effects(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_effect **out, size_t *n) {
+    if (!ctx || !b || !out || !n) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (b->b.pats != ctx->pats) return tfbs::fail(TFBS_E_ARG, "batch and ctx use different pattern sets");
+    if (!b->b.keep_variants) return tfbs::fail(TFBS_E_STATE, "batch built without tfbs_batch_keep_variants");
+    if (b->b.open) return tfbs::fail(TFBS_E_STATE, "region still open");
+    if (r0 > r1 || r1 > b->b.rh.size()) return tfbs::fail(TFBS_E_ARG, "bad region range");
+    std::vector<tfbs_effect> v;
+    if (int rc = effects_run(&ctx->effects_state, ctx->device, ctx->stream, *ctx->pats, b->b, r0, r1, &v)) return rc;
+    return hand_out(v, out, n);
+}
+
+int tfbs_ctx_last_effects_ms(const tfbs_ctx *ctx, double out[3]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    effects_last_ms(ctx->effects_state, out);
     return TFBS_OK;
 }
 

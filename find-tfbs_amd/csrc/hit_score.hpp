@@ -1,4 +1,5 @@
-// What the brute-force kernels (scan_hits.hip, scan_best.hip) and their drivers share.  A HIP
+// What the brute-force kernels (scan_hits.hip, scan_best.hip), the variant-effect kernel
+// (scan_effects.hip: pair_head, the scoring, the drivers' base) and their drivers share.  A HIP
 // header: only .hip sources include it.
 //  * Device: the exact scoring code (bases16, score_mono, score_dinuc), the kernels' prologue
 //    in two steps (pair_head, PAIR_OPEN), what a wave knows of its pair (PairScan) and the walk
@@ -234,7 +235,7 @@ struct Buf {  // a device buffer that only grows
     }
 };
 
-// What both drivers keep on a ctx: the pattern set's tables on the device (build_hit_tables),
+// What the drivers keep on a ctx: the pattern set's tables on the device (build_hit_tables),
 // the chunk's haplotype list, the pinned buffer of the copy-back and the events.
 struct PairState {
     Buf<DevHitStrand> strands;

@@ -1,6 +1,7 @@
-// Hit lists (tfbs_batch_hits) and best sites (tfbs_batch_best): the interfaces of
-// scan_hits.hip and scan_best.hip to device.hip, what the two share on the host (the tables,
-// ScanImage, site_range, text_out) and the host-only helpers of hits.cpp and best.cpp.
+// Hit lists (tfbs_batch_hits), best sites (tfbs_batch_best) and variant effects
+// (tfbs_batch_effects): the interfaces of scan_hits.hip, scan_best.hip and scan_effects.hip to
+// device.hip, what they share on the host (the tables, ScanImage, site_range, text_out) and the
+// host-only helpers of hits.cpp, best.cpp and effects.cpp.
 #pragma once
 
 #include <cstdint>
@@ -101,5 +102,35 @@ int best_run(BestState **state, int device, void *stream, const Patterns &P, con
 void best_last_ms(const BestState *s, double out[2]);
 // tfbs_batch_best_tsv's text appended to out (no header line); the records are whole regions.
 int best_tsv(const Batch &B, const tfbs_best *best, size_t n, const std::string &chrom, int mode, std::string &out);
+
+// ---- variant effects (tfbs_batch_effects): scan_effects.hip's interface to device.hip, effects.cpp's formatter
+// One scored record of a chunk as the kernel reads it: R and A packed into one run of the
+// chunk's words (and N-mask words, has_n), A from base a_base (a multiple of 32) of the run.
+struct DevEffVar {
+    uint32_t word_off, nmask_off;  // the run's first word / N-mask word
+    uint32_t len_r, len_a;         // bases of R and of A
+    uint32_t a, z;                 // common prefix and suffix columns
+    uint32_t a_base;               // A's first base in the run
+    uint32_t has_n;
+};
+// One (scored record, strand) as the kernel writes it: 32 bytes, two vector stores.
+struct alignas(16) DevEffRec {
+    int32_t ref_score;
+    uint32_t ref_window, n_ref, zero0;
+    int32_t alt_score;
+    uint32_t alt_window, n_alt, zero1;
+};
+struct EffectsState;
+void effects_state_destroy(EffectsState *s);
+// The dense effect records of regions [r0, r1) of B (built with keep_variants) appended to
+// *out, sorted by (region, variant, pattern).  Reads no resident image.  *state is made on
+// the first call.  Synchronises `stream` (a hipStream_t).
+int effects_run(EffectsState **state, int device, void *stream, const Patterns &P, const Batch &B, size_t r0,
+                size_t r1, std::vector<tfbs_effect> *out);
+// The last effects_run's times (ms): host prep (wall), the kernel (HIP events, summed over
+// the chunks), copy-back + host part (wall).
+void effects_last_ms(const EffectsState *s, double out[3]);
+// tfbs_batch_effects_tsv's text appended to out (no header line); the records are whole regions.
+int effects_tsv(const Batch &B, const tfbs_effect *e, size_t n, const std::string &chrom, int mode, std::string &out);
 
 }  // namespace tfbs

@@ -8,6 +8,7 @@
 // (the reference spreads 50-peak chunks over threads and emits rows in thread
 // interleaving / HashMap order); rows within a region are sorted (D2); the
 // POS counter is therefore deterministic.
+#include <cstddef>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -96,8 +97,8 @@ struct Shard {
     double t_setup = 0, t_boot = 0, t_end = 0;  // readers + ctx + grouper; the first batches' stages; flush + ctx release
 };
 
-// --hits_output, --best_output: the batches' texts (tfbs_batch_hits_tsv, tfbs_batch_best_tsv)
-// written in batch order by the host BGZF writer, whichever shard hands them in first.
+// --hits_output, --best_output, --effects_output: the batches' texts (tfbs_batch_hits_tsv,
+// tfbs_batch_best_tsv, tfbs_batch_effects_tsv) written in batch order by the host BGZF writer, whichever shard hands them in first.
 struct TextOut {
     std::mutex mu;
     tfbs::BgzfWriter w;
@@ -129,11 +130,15 @@ struct TextOut {
 // Best records (48 bytes each) the run flow holds at once: whole regions up to this many, one
 // region at least (the text does not depend on the split: tfbs_batch_best_tsv takes whole regions).
 constexpr size_t kBestRunRecords = 1u << 20;
+// The same for effect records (72 bytes each; tfbs_batch_effects_tsv takes whole regions too).
+constexpr size_t kEffectsRunRecords = 1u << 20;
 
 struct RunSetup {
     const tfbs_run_args *a;
     TextOut *hits = nullptr;  // null without --hits_output: the run does nothing more
     TextOut *best = nullptr;  // null without --best_output: the same
+    TextOut *effects = nullptr;  // null without --effects_output: the same (the batches keep no variants)
+    int effects_mode = TFBS_EFFECTS_SITES;
     std::string chrom;
     tfbs_patterns *pp;
     std::vector<std::pair<std::string, std::vector<std::pair<uint64_t, uint64_t>>>> beds;
@@ -232,6 +237,7 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
         if (rc) return err = tfbs_last_error(), rc;
         p.bp = BatchPtr(bb, tfbs_batch_destroy);
         Batch &B = bb->b;
+        B.keep_variants = S.effects != nullptr;
         for (auto &b : S.beds) B.beds.push_back(b.first);
         p.ins.clear();
         p.ins.reserve(b1 - b0);
@@ -392,6 +398,22 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
                 q0 = q1;
             }
             if ((rc = S.best->submit(g, std::move(text)))) return rc;
+        }
+        if (S.effects) {  // the batch's variant effects: dense records too, whole regions at a time
+            std::string text;
+            const size_t np = B.pats->pats.size();
+            auto records_of = [&](size_t r) { return (size_t)B.kept[r].vars.size() * np; };
+            for (size_t q0 = 0; q0 < B.rh.size();) {
+                size_t q1 = q0 + 1, recs = records_of(q0);  // regions [q0, q1): one at least
+                while (q1 < B.rh.size() && recs + records_of(q1) <= kEffectsRunRecords) recs += records_of(q1++);
+                tfbs_effect *eff = nullptr;
+                size_t neff = 0;
+                if ((rc = tfbs_batch_effects(ctx, bb, q0, q1, &eff, &neff))) return rc;
+                std::unique_ptr<tfbs_effect, void (*)(void *)> eguard(eff, free);
+                if ((rc = effects_tsv(B, eff, neff, strip_chr(S.chrom), S.effects_mode, text))) return rc;
+                q0 = q1;
+            }
+            if ((rc = S.effects->submit(g, std::move(text)))) return rc;
         }
         if (a->verbose) {
             for (size_t r = 0; r < B.rh.size(); r++)
@@ -577,8 +599,18 @@ std::vector<int> parse_devices(const tfbs_run_args *a) {
 
 extern "C" {
 
-int tfbs_run(const tfbs_run_args *a) {
+int tfbs_run(const tfbs_run_args *a) { return tfbs_run_ex(a, nullptr); }
+
+int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     using namespace tfbs;
+    // only what the caller's `size` covers is read
+    const char *effects_output = nullptr;
+    int effects_mode = TFBS_EFFECTS_SITES;
+    if (ext) {
+        if (ext->size >= offsetof(tfbs_run_ext, effects_output) + sizeof ext->effects_output)
+            effects_output = ext->effects_output;
+        if (ext->size >= offsetof(tfbs_run_ext, effects_mode) + sizeof ext->effects_mode) effects_mode = ext->effects_mode;
+    }
     if (!a || !a->chromosome || !a->bcf || !a->bed_files || !a->reference || (!a->pwm_file && !a->dipwm_file) ||
         !a->pwm_threshold_dir || !a->pwm_names || !a->output)
         return fail(TFBS_E_ARG, "missing required argument");
@@ -674,7 +706,7 @@ int tfbs_run(const tfbs_run_args *a) {
     header += "\n";
     rc = w.write(header.data(), header.size());
     if (rc) return rc;
-    TextOut hits_out, best_out;
+    TextOut hits_out, best_out, effects_out;
     if (a->hits_output) {
         if (a->hits_mode != TFBS_HITS_ALL && a->hits_mode != TFBS_HITS_DIFF)
             return fail(TFBS_E_ARG, "hits_mode is TFBS_HITS_ALL or TFBS_HITS_DIFF");
@@ -686,6 +718,13 @@ int tfbs_run(const tfbs_run_args *a) {
             return fail(TFBS_E_ARG, "best_mode is TFBS_BEST_ALL or TFBS_BEST_DIFF");
         if ((rc = best_out.open(a->best_output, threads, TFBS_BEST_HEADER))) return rc;
         S.best = &best_out;
+    }
+    if (effects_output) {
+        if (effects_mode != TFBS_EFFECTS_SITES && effects_mode != TFBS_EFFECTS_ALL)
+            return fail(TFBS_E_ARG, "effects_mode is TFBS_EFFECTS_SITES or TFBS_EFFECTS_ALL");
+        if ((rc = effects_out.open(effects_output, threads, TFBS_EFFECTS_HEADER))) return rc;
+        S.effects = &effects_out;
+        S.effects_mode = effects_mode;
     }
 
     // shards: batch g of merged regions on device g % n (one device:
@@ -845,6 +884,7 @@ int tfbs_run(const tfbs_run_args *a) {
     if ((rc = w.flush()) || (rc = w.flush()) || (rc = w.close())) return rc;
     if (S.hits && (rc = hits_out.finish())) return rc;
     if (S.best && (rc = best_out.finish())) return rc;
+    if (S.effects && (rc = effects_out.finish())) return rc;
     const double t_close = now() - t0;
     if (timing)
         for (size_t k = 0; k < n_sh; k++)

@@ -575,6 +575,98 @@ int tfbs_ctx_last_best_ms(const tfbs_ctx *ctx, double out[2]);
 int tfbs_batch_best_tsv(const tfbs_batch *b, const tfbs_best *best, size_t n, const char *chromosome, int mode,
                         char **text, size_t *len);
 
+/* ------------------------------------------------------------------ */
+/* Variant effects: per record the best site touching it on the REF and */
+/* on the ALT allele, per pattern strand                                */
+/* ------------------------------------------------------------------ */
+/* Before the batch's first region: on != 0 makes every region keep its fetched reference
+ * codes and a compact copy of each record (pos, REF and ALT codes, n_alleles, the number of
+ * carrier ids, the status below), on every build path.  Default off: the batch is then
+ * byte for byte what it was (memory, digests, device bytes) and the effects calls return
+ * TFBS_E_STATE.  TFBS_E_STATE once a region is open or added. */
+int tfbs_batch_keep_variants(tfbs_batch *b, int on);
+/* A record's status, tested in this order: n_alleles != 2 (load_diffs counts it and never
+ * applies it); no selected haplotype id carries ALT; patching this record alone into the
+ * window is refused (TFBS_E_REFMISMATCH / TFBS_E_MNP -- reachable in a region that builds:
+ * an overlapping diff truncates a haplotype without a REF check, so a bad-REF SNV inside a
+ * deletion that all its carriers also carry builds fine and fails alone); else scored. */
+#define TFBS_VAR_SCORED 0
+#define TFBS_VAR_MULTIALLELIC 1
+#define TFBS_VAR_NO_CARRIER 2
+#define TFBS_VAR_UNPATCHED 3
+/* Host only.  Record v (BCF order, v < the n_variants of tfbs_batch_region_stats) of a region
+ * of a batch that keeps its variants: REF / ALT as nucleotide codes 0-4 into ref / alt (cap
+ * entries each).  *n_ref / *n_alt are always set: TFBS_E_ARG on a short cap tells the need,
+ * as tfbs_batch_region_haplotype does.  TFBS_E_STATE without tfbs_batch_keep_variants. */
+int tfbs_batch_region_variant(const tfbs_batch *b, size_t region, size_t v, uint64_t *pos, uint8_t *ref, uint8_t *alt,
+                              size_t cap, size_t *n_ref, size_t *n_alt, uint32_t *n_alleles, uint32_t *carriers,
+                              uint32_t *status);
+/* One effect record: region, record v of it, pattern strand p in creation order (L bases).
+ * For a scored record let R = patch_haplotype((es, ee), [], ref) and A = patch_haplotype((es,
+ * ee), [v], ref), both sequences of (code, pos) columns; a = the length of their longest
+ * common prefix (code and pos equal), z = that of their longest common suffix with
+ * z <= min(len R, len A) - a.  Window i of side X (n = len X) is *affected* iff i + L <= n,
+ * i + L > a and i < n - z: it exists and lies neither wholly in the common prefix nor wholly
+ * in the common suffix.  (An SNV: the L windows covering the site, clipped at the ends; an
+ * insertion: the reference windows spanning the junction; a deletion: the alt windows
+ * spanning it; a record outside the window, A == R: none; a deletion running to the
+ * window's end, A a prefix of R: none on the alt side.)
+ *   n_ref, ref_score, ref_window   the affected windows of R, the maximum of their scores
+ *                                  (signed int32), the lowest i attaining it
+ *   n_alt, alt_score, alt_window   the same on A
+ *   ref_start .. alt_end           pos_X[i] and pos_X[i] + L - 1 of the two best windows
+ * Scores are the hit list's and the best sites' (wrapping int32 column sum, an N column
+ * adding 0, any L; wrapping int32 pair sum, a pair holding an N adding 0).  A side without an
+ * affected window (TFBS_KIND_OTHER, a side shorter than L, an unscored record) holds
+ * score = INT32_MIN, window = UINT32_MAX, start = end = 0; n_ref / n_alt tell that from a
+ * genuine INT32_MIN.  min_score, the inner ranges and the bed multiplicity play no part.
+ * Dense and sorted by (region, variant, pattern): regions [r0, r1) give
+ * sum_r n_variants(r) * n_patterns records, a region's block reshapes to [v][p]. */
+typedef struct tfbs_effect {
+    uint32_t region, variant, pattern, status;
+    uint32_t n_ref;
+    int32_t ref_score;
+    uint32_t ref_window;
+    uint32_t n_alt;
+    int32_t alt_score;
+    uint32_t alt_window;
+    uint64_t ref_start, ref_end, alt_start, alt_end;
+} tfbs_effect; /* 72 bytes */
+/* The effect records of regions [r0, r1) of a batch that keeps its variants, on a ctx made
+ * from the batch's pattern set (needs neither upload nor scan; leaves every scan / reduce /
+ * encode / rows result and the step graph untouched).  *out is malloc'd (tfbs_free).  The
+ * host patches R once per region and A per scored record and packs both; its own kernel
+ * (scan_effects.hip) scores only the affected windows with the hit list's scoring code, one
+ * wave per (scored record, strand).  It works in chunks of whole records whose packed image
+ * and device records fit TFBS_EFFECTS_SCRATCH_MB (default 256, fractions allowed; at least
+ * one record; read at the call) and the result does not depend on it.  TFBS_E_STATE without
+ * tfbs_batch_keep_variants, TFBS_E_ARG for r0 > r1 or r1 > num_regions; an empty range of
+ * regions or an empty pattern set gives *n = 0. */
+int tfbs_batch_effects(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_effect **out, size_t *n);
+/* The last tfbs_batch_effects' times (ms): out[0] the host's patching and packing (wall),
+ * out[1] the kernel (HIP events on the ctx stream, summed over the scratch chunks), out[2]
+ * the copy-back and the host's expansion (wall). */
+int tfbs_ctx_last_effects_ms(const tfbs_ctx *ctx, double out[3]);
+/* Host only.  Formats effect records (whole regions, ascending) as TSV, tab-separated, under
+ * the header
+ *   #chrom region variant pos ref alt carriers kind name pattern_id strand ref_start ref_end ref_score alt_start alt_end alt_score delta
+ * chrom and region are the hit TSV's.  Per region and record in order first one `var` line:
+ * pos, ref, alt, the carrier count, in `name` the status as scored|multiallelic|no_carrier|
+ * unpatched, every other field ".".  Then, for a scored record, one line per pattern strand
+ * in creation order (name, pattern_id, strand + or -).  A side passes iff n > 0 and
+ * score > the strand's min_score; kind is gain (only alt passes), loss (only ref passes),
+ * change (both, scores differ), same (both, scores equal), none (neither).
+ * TFBS_EFFECTS_SITES writes gain, loss and change lines; TFBS_EFFECTS_ALL all five kinds,
+ * for every strand with n_ref + n_alt > 0.  A side with n == 0 writes "." for its three
+ * fields; delta is alt_score - ref_score as a signed 64-bit difference, "." when either side
+ * has no window.  A batch's text is the concatenation of its regions' texts.
+ * The header line is not part of *text (malloc'd, tfbs_free). */
+#define TFBS_EFFECTS_SITES 0
+#define TFBS_EFFECTS_ALL 1
+#define TFBS_EFFECTS_HEADER "#chrom\tregion\tvariant\tpos\tref\talt\tcarriers\tkind\tname\tpattern_id\tstrand\tref_start\tref_end\tref_score\talt_start\talt_end\talt_score\tdelta\n"
+int tfbs_batch_effects_tsv(const tfbs_batch *b, const tfbs_effect *e, size_t n, const char *chromosome, int mode,
+                           char **text, size_t *len);
+
 void tfbs_free(void *p);
 
 /* counts_as_genotypes alone (main.rs:439-498): 1 = row (strings written), 0 = no variation. */
@@ -626,6 +718,17 @@ typedef struct tfbs_run_args {
  * either deflates) and the batches' blocks are written in order, so the output
  * text is identical for any device list. */
 int tfbs_run(const tfbs_run_args *args);
+/* What later versions add to a run: tfbs_run_args keeps its layout, so a caller built
+ * against an older header goes on working.  Only the first `size` bytes are read; a field
+ * beyond them counts as 0 / NULL.  tfbs_run(args) is tfbs_run_ex(args, NULL). */
+typedef struct tfbs_run_ext {
+    uint32_t size;                  /* sizeof(tfbs_run_ext) of the caller */
+    const char *effects_output;     /* --effects_output: the batches' variant effects as BGZF TSV
+                                       (tfbs_batch_effects_tsv under TFBS_EFFECTS_HEADER), NULL = none: the run
+                                       does nothing more than without it (its batches keep no variants) */
+    int effects_mode;               /* --effects_mode: TFBS_EFFECTS_SITES / TFBS_EFFECTS_ALL */
+} tfbs_run_ext;
+int tfbs_run_ex(const tfbs_run_args *args, const tfbs_run_ext *ext);
 
 typedef struct tfbs_bcf tfbs_bcf;
 /* Replaces rust-htslib IndexedReader::from_path / header().samples() (main.rs:46-52, 255). */
