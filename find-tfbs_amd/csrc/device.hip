@@ -138,6 +138,10 @@ struct tfbs_ctx {
     uint32_t mfma_lds = 44 * 1024;  // LDS image budget of one MFMA super tile
     uint32_t mfma_hpb = 64;         // haplotypes per MFMA workgroup
     uint32_t mfma_group_words = 0;  // packed words of the largest haplotype group (LDS staging)
+    // the merged scan's unit, groups per workgroup (ScanArgs::unit): TFBS_SCAN_UNIT = 1, 2, 4
+    // forces it, 0 / unset: chosen per batch (scan_unit_for); scan_unit: the resident batch's
+    uint32_t scan_unit_env = 0, scan_unit = 1;
+    uint32_t n_cus = 256;           // the device's compute units
     // batch image
     DevBuf<uint32_t> words, nmask, counts;  // counts: dense, for the LUT/generic slots (and tfbs_batch_download)
     bool counts_live = false;             // counts allocated for the resident batch
@@ -334,6 +338,26 @@ static int env_int(const char *name, int dflt) {
     return atoi(v);
 }
 
+// The merged scan's unit for a batch of n_groups haplotype groups (ScanArgs::unit): a
+// unit pays a super tile image's staging once for its G groups, but G times fewer
+// workgroups fill the chip worse -- the largest G of 4, 2, 1 whose units still give
+// each of the chip's workgroup slots (two per CU) kUnitRounds workgroups in turn
+// ("Units": the measurements behind the number).  And only where the image's
+// staging is a large part of a group's work: a group's list of either depth class holds
+// at most kUnitPairs pairs of window tiles on average, two per wave (C5's groups hold 38:
+// their waves scan for longer than an image takes to stage, and units of four made its
+// step 2.5 % slower -- the per-group barriers and the longer candidate lists).
+constexpr uint32_t kUnitRounds = 4, kUnitPairs = 2 * kMBlockWaves;
+static uint32_t scan_unit_for(const tfbs_ctx *ctx, uint32_t n_groups) {
+    if (!ctx->mfma_merged) return 1;
+    if (ctx->scan_unit_env) return ctx->scan_unit_env;
+    for (int c = 0; c < 2; c++)
+        if (ctx->wl_entries[c] > (uint64_t)kUnitPairs * 64 * n_groups) return 1;
+    for (uint32_t G = kMMaxUnit; G > 1; G /= 2)
+        if ((n_groups + G - 1) / G >= (uint64_t)kUnitRounds * 2 * ctx->n_cus) return G;
+    return 1;
+}
+
 // The matrix-core window lists of the haplotypes just put on the device (one
 // per depth class the plan has; scan.hpp build_window_lists).
 // B: the batch whose haplotypes they are -- its windows are shared among the region's
@@ -441,6 +465,7 @@ static int build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t
     // per-pair MFMAs + rounds of each depth class's super tiles), so that the launch
     // ends on its smallest groups instead of a late large one (LPT).
     ctx->gorder.release();
+    ctx->scan_unit = scan_unit_for(ctx, (n_haps + ctx->mfma_hpb - 1) / ctx->mfma_hpb);
     if (env_int("TFBS_SCAN_LPT", 1) && n_haps) {
         uint32_t w[2] = {0, 0};
         for (const DevMSuper &S : P.m_supers) {
@@ -456,11 +481,15 @@ static int build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t
             (rc = group_costs(lmin[0] ? ctx->wl_off[0].p : nullptr, lmin[1] ? ctx->wl_off[1].p : nullptr, n_haps, hpb,
                               w[0], w[1], ctx->gcost.p, ctx->stream)))
             return rc;
-        std::vector<uint32_t> cost(ng), order(ng);
+        // (the order holds units: a unit's cost is the sum of its groups')
+        const uint32_t G = ctx->scan_unit, nu = (ng + G - 1) / G;
+        std::vector<uint32_t> cost(ng), order(nu);
         HIP_TRY(hipMemcpyAsync(cost.data(), ctx->gcost.p, (size_t)ng * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for (uint32_t g = 0; g < ng; g++) order[g] = g;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
+        std::vector<uint64_t> ucost(nu, 0);
+        for (uint32_t g = 0; g < ng; g++) ucost[g / G] += cost[g];
+        for (uint32_t u = 0; u < nu; u++) order[u] = u;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ucost[a] > ucost[b]; });
         if ((rc = ctx->gorder.put(order, ctx->stream))) return rc;
         HIP_TRY(hipStreamSynchronize(ctx->stream));  // (order is copied from the host's stack)
     }
@@ -545,6 +574,7 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
         m.dedup = 1;
         m.gnarrow = ctx->gnarrow.n ? ctx->gnarrow.p : nullptr;
         m.gorder = ctx->mfma_merged && ctx->gorder.n ? ctx->gorder.p : nullptr;
+        m.unit = ctx->mfma_merged ? ctx->scan_unit : 1;  // (gorder holds units of as many groups)
         m.hd = ctx->hd.p;
         m.hd2 = ctx->hd2.p;
         m.druns = ctx->druns.p;
@@ -900,6 +930,10 @@ int tfbs_ctx_create(int device, const tfbs_patterns *p, tfbs_ctx **out) {
     ctx->mfma_hpb = (uint32_t)std::min((int)kMMaxHapsPerBlock, std::max(4, env_int("TFBS_MFMA_HAPS_PER_BLOCK", 64)));  // 6 bits in a window list entry
     ctx->cand_cap = (uint32_t)std::min(1 << 16, std::max(64, env_int("TFBS_CAND_CAP", 1024)));
     ctx->mfma_merged = env_int("TFBS_SCAN_MERGED", 1) != 0;
+    {
+        const int u = env_int("TFBS_SCAN_UNIT", 0);
+        ctx->scan_unit_env = u == 1 || u == 2 || u == 4 ? (uint32_t)u : 0u;
+    }
     ctx->debug_over = env_int("TFBS_DEBUG_OVER", 0) != 0;
     ctx->kf_prof_on = env_int("TFBS_KF_PROF", 0) != 0;
     ctx->kf_persistent = env_int("TFBS_KF_PERSIST", 1) != 0;
@@ -943,10 +977,13 @@ int tfbs_ctx_create(int device, const tfbs_patterns *p, tfbs_ctx **out) {
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->join[i], hipEventDisableTiming);
     }
+    int n_cus = 0;
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) {
         tfbs_ctx_destroy(ctx);
         return tfbs::fail(TFBS_E_HIP, std::string("HIP init: ") + hipGetErrorString(e));
     }
+    ctx->n_cus = (uint32_t)std::max(1, n_cus);
     const Plan &P = ctx->plan;
     ctx->cfg.lds_bytes = (size_t)P.max_tile_blocks * kBlockBytes;
     if (ctx->cfg.lds_bytes > 160 * 1024) {
@@ -1037,13 +1074,23 @@ int tfbs_ctx_scan_counters(tfbs_ctx *ctx, uint64_t out[5]) {
     HIP_TRY(hipMemcpy(hn.data(), ctx->hitn.p, nw * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(cn.data(), ctx->candn.p, nw * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ov, ctx->over.p, sizeof ov, hipMemcpyDeviceToHost));
-    const uint64_t cap = ctx->scan_cand_cap / kMBlockWaves, lcap = std::min<uint64_t>(cap, kMWaveCands);
     out[0] = ov[0];
     out[1] = ov[1];
-    for (size_t i = 0; i < nw; i++) {  // (the waves of every workgroup the last scan launched)
-        out[2] += cn[i];
-        out[3] += cn[i] > lcap ? std::min<uint64_t>(cn[i], lcap + cap) - lcap : 0;
-        out[4] += hn[i];
+    // (the waves of every slot the last scan launched; a unit's groups share each wave's
+    // candidate lists: the LDS list's room once, the global list's once per group)
+    const size_t G = ctx->mfma_merged ? std::max<size_t>(1, ctx->last_margs.unit) : 1, ns = nw / kMBlockWaves;
+    for (size_t s0 = 0; s0 < ns; s0 += G) {
+        const size_t ngu = std::min(G, ns - s0);
+        const uint64_t cap = (uint64_t)ngu * (ctx->scan_cand_cap / kMBlockWaves), lcap = std::min<uint64_t>(cap, kMWaveCands);
+        for (size_t w = 0; w < kMBlockWaves; w++) {
+            uint64_t c = 0;
+            for (size_t s = s0; s < s0 + ngu; s++) {
+                c += cn[s * kMBlockWaves + w];
+                out[4] += hn[s * kMBlockWaves + w];
+            }
+            out[2] += c;
+            out[3] += c > lcap ? std::min<uint64_t>(c, lcap + cap) - lcap : 0;
+        }
     }
     return TFBS_OK;
 }

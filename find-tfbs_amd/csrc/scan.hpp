@@ -44,7 +44,8 @@ struct ScanArgs {
     // matrix-core candidates (scan_mfma.hip): one region of cand_cap (strand |
     // haplotype in the group << 24, window) pairs per scan workgroup (region
     // region_base + blockIdx.x), an equal share per wave, each wave's filled and
-    // rescored by the wave
+    // rescored by the wave (a unit of n groups: the n regions of its groups' slots as
+    // one, the haplotype counted from the unit's first)
     uint32_t *cands;  // kCandWords per entry
     uint32_t cand_cap;
     uint32_t region_base;
@@ -71,9 +72,13 @@ struct ScanArgs {
     const uint4 *hd;   // matrix-core scan: per haplotype (word_off, len, flags, nmask_off) of haps (build_window_lists)
     const uint4 *hd2;  // and (region, pos_off, drun_off, n_druns): the rescoring's
     const uint8_t *gnarrow;
-    // scan_mfma_all_kernel: workgroup b scans haplotype group gorder[b] (the groups in
-    // descending order of work, so the launch ends on the small ones); null: group b
+    // scan_mfma_all_kernel: a workgroup scans one *unit*, `unit` (1, 2 or 4; 0 as 1)
+    // consecutive haplotype groups (the last unit may be short) against each staged
+    // super tile image; every group keeps its own list slot (region_base + group).
+    // Workgroup b scans unit gorder[b] (the units in descending order of work, so the
+    // launch ends on the small ones); null: unit b
     const uint32_t *gorder;
+    uint32_t unit;
     const uint64_t *wlist_off[2];
     // shared windows (build_window_lists, share != 0), per depth class: a window listed
     // for its donor haplotype only stands for the same window of the region's other
@@ -122,7 +127,8 @@ struct ScanArgs {
 constexpr uint32_t kScanProfWords = 16;
 constexpr uint32_t kRefPerRegion = 64;
 constexpr uint32_t kMBlockWaves = 8;  // waves per matrix-core workgroup (hit list parts per workgroup)
-constexpr uint32_t kCandWords = 2;  // candidate list entry: strand | haplotype in the group << 24, window
+constexpr uint32_t kCandWords = 2;  // candidate list entry: strand | haplotype in the group (unit) << 24, window
+constexpr uint32_t kMMaxUnit = 4;   // groups per unit: kMMaxUnit x kMMaxHapsPerBlock haplotypes fit the entry's 8 bits
 
 struct LaunchConfig {
     int minw = 2;               // __launch_bounds__ min waves per SIMD of the fast kernel
@@ -154,8 +160,9 @@ constexpr uint32_t kMWaveCands = 48;  // a scan wave's candidates kept in LDS be
 // HitSrc per launch (*n_srcs of kMaxHitSrcs).
 int launch_mfma(const ScanArgs &a, const DevMSuper *supers, uint32_t n_supers, uint32_t group_words, uint32_t n_haps,
                 const hipStream_t *streams, uint32_t n_streams, HitSrc *srcs, uint32_t *n_srcs);
-// The same in one launch on `stream`: one workgroup per haplotype group scans it
-// against every super tile in turn (scan_mfma_all_kernel); one HitSrc with ns = 1.
+// The same in one launch on `stream`: one workgroup per unit of a.unit haplotype groups
+// scans them against every super tile in turn (scan_mfma_all_kernel); one HitSrc with
+// ns = 1 (a list slot per group, whatever the unit).
 int launch_mfma_all(const ScanArgs &a, const DevMSuper *supers, uint32_t n_supers, uint32_t group_words, uint32_t n_haps,
                     hipStream_t stream, HitSrc *srcs, uint32_t *n_srcs);
 // Rescores the candidates past the waves' lists (after launch_mfma on the same stream).
@@ -209,7 +216,8 @@ size_t scan_tmp_words(size_t n);
 int exclusive_scan(uint64_t *x, uint64_t n, uint64_t *tmp, hipStream_t stream);
 // Per haplotype group of hpb (n_groups): the window tiles of its lists, cost[g] =
 // pairs of class 2 x w[0] + pairs of class 4 x w[1] (w: the per-pair work of each
-// depth class's super tiles), for the scan's workgroup order.
+// depth class's super tiles), for the scan's workgroup order (a unit's cost: the sum
+// of its groups').
 int group_costs(const uint64_t *off0, const uint64_t *off1, uint32_t n_haps, uint32_t hpb, uint32_t w0, uint32_t w1,
                 uint32_t *cost, hipStream_t stream);
 // share != 0: shared windows (ScanArgs::share) -- regions / words: the batch's; a

@@ -192,8 +192,20 @@ struct GroupCtx {
     const uint32_t *wl;
     const uint16_t *wl16;  // a narrow group's list (16-bit entries), else null
     uint32_t nw, tile0, h0, slot;
+    uint32_t ub;  // the group's place in its unit (unit_place)
     __device__ __forceinline__ uint32_t at(uint32_t q) const { return wl16 ? (uint32_t)wl16[q] : wl[q]; }
 };
+
+// Where a wave lists its candidates past the LDS list: ccap entries at clist (a unit's
+// groups share the wave's list: the groups' regions of A.cands taken as one).
+struct WaveCands {
+    uint32_t ccap;
+    uint2 *clist;
+};
+// A group's place in its unit, one word: the group's first haplotype counted from the
+// unit's first (a candidate's haplotype = that + its index in the group) | the unit's
+// groups << 16.  One group per workgroup: unit_place(0, 1).
+__device__ __forceinline__ uint32_t unit_place(uint32_t bias, uint32_t ngu) { return bias | (ngu << 16); }
 
 // What the rescoring reads of a haplotype: DevHap's fields, from the scan
 // workgroup's LDS descriptors (s_hd, s_hd2) or from a DevHap.
@@ -344,96 +356,118 @@ __device__ __forceinline__ uint32_t score_candidate(const ScanArgs &A, const uin
 // A.hit_cap, rescore_list): the LDS list's (at most kWaveCands) followed by the wave's
 // region of the global list (TFBS_CAND_CAP makes all of them small in the spill tests).
 __device__ __forceinline__ uint32_t wave_cand_cap(const ScanArgs &A) { return A.cand_cap / (kMBlock / 64); }
-__device__ __forceinline__ uint32_t wave_lds_cap(const ScanArgs &A) { return min(wave_cand_cap(A), kWaveCands); }
 // slot: the workgroup's place in the per-workgroup lists (region_base + its
-// haplotype group in the merged kernel's ordered launch, ScanArgs::gorder; else +
-// its index).
-__device__ __forceinline__ uint2 *cand_list(const ScanArgs &A, uint32_t slot, uint32_t wave) {
-    return reinterpret_cast<uint2 *>(A.cands) + (size_t)slot * A.cand_cap +
-           (size_t)wave * wave_cand_cap(A);
+// haplotype group in the merged kernel's launch; else + its index).  The wave's
+// global list in a unit of ngu groups whose first slot is `slot`: the groups' regions
+// are consecutive, each wave takes ngu x its share of one (ngu = 1: one workgroup's
+// region in eight parts).
+__device__ __forceinline__ WaveCands unit_cands(const ScanArgs &A, uint32_t slot, uint32_t ngu, uint32_t wave) {
+    const uint32_t ccap = ngu * wave_cand_cap(A);
+    return WaveCands{ccap, reinterpret_cast<uint2 *>(A.cands) + (size_t)slot * A.cand_cap + (size_t)wave * ccap};
 }
 
 // The wave's listed candidates, one per lane (after its scan: no accumulator
 // is live, and the other waves keep the matrix cores busy); each hit's
-// (haplotype, key) pairs are appended to the wave's part of the workgroup's hit
+// (haplotype, key) pairs are appended to the wave's part of its group's hit
 // list in lane order (ballot prefix: no atomics), the excess spilled.
-__device__ __forceinline__ void rescore_list(const ScanArgs &A, const uint32_t *words, uint32_t h0, uint32_t slot, uint32_t wave,
-                                             uint32_t lane, uint32_t cn) {
+// UNIT: the candidates of a unit of ngu groups (first haplotype h0, first slot `slot`),
+// rescored once -- the descriptors and words from global memory (A.hd, A.hd2, words =
+// A.words: the LDS copies are the last group's), one more load in the chain but one
+// chain per unit --; a hit goes to the wave list of its haplotype's group (slot + the
+// group in the unit), the ballot prefix taken over that group's lanes, one count per
+// group (hnv: lane u holds group u's).  candn likewise: a group's are its candidates
+// in the lists; those past the lists (cn - n) are counted at the unit's first slot.
+template <bool UNIT>
+__device__ __forceinline__ void rescore_list(const ScanArgs &A, const uint32_t *words, uint32_t h0, uint32_t slot,
+                                             uint32_t ngu, uint32_t wave, uint32_t lane, uint32_t cn) {
     const uint32_t cap = A.hit_cap / (kMBlock / 64);  // the hit list's room per wave
-    const size_t part = (size_t)slot * A.hit_cap + (size_t)wave * cap;
-    uint2 *out = reinterpret_cast<uint2 *>(A.hitl) + part;
-    uint32_t hn = 0;  // wave-uniform
-    const uint32_t lcap = wave_lds_cap(A), n = min(cn, lcap + wave_cand_cap(A));
-    const uint2 *glist = cand_list(A, slot, wave);
+    const WaveCands W = unit_cands(A, slot, ngu, wave);
+    const uint32_t lcap = min(W.ccap, kWaveCands), n = min(cn, lcap + W.ccap);
+    const uint2 *glist = W.clist;
     const bool shared = A.share_off[0] || A.share_off[1];
+    uint32_t hnv = 0, cnv = lane == 0 ? cn - n : 0u;
     for (uint32_t k0 = 0; k0 < n; k0 += 64) {
         const uint32_t k = k0 + lane;
-        uint32_t mask = 0, key0 = 0, hap = h0, g = 0, win = 0;
+        uint32_t mask = 0, key0 = 0, hap = h0, g = 0, win = 0, gi = 0, flags = 0, region = 0;
         if (k < n) {
             const uint2 c = k < lcap ? s_cand[wave][k] : glist[k - lcap];
-            hap = h0 + (c.x >> 24);
-            const uint32_t hl = c.x >> 24;  // the haplotype's descriptors, staged in LDS
+            const uint32_t hl = c.x >> 24;  // the haplotype in the group (unit)
+            hap = h0 + hl;
             g = c.x & 0xFFFFFFu;
             win = c.y;
-            mask = score_candidate(A, words, CandHap::of(s_hd[hl], s_hd2[hl]), hap, g, win, &key0);
+            // the haplotype's descriptors: staged in LDS, a unit's from global memory
+            const CandHap hp = UNIT ? CandHap::of(A.hd[hap], A.hd2[hap]) : CandHap::of(s_hd[hl], s_hd2[hl]);
+            if (UNIT)  // its group in the unit (no division: its reciprocal would live across the scan)
+                for (uint32_t u = 1; u < kMMaxUnit; u++) gi += hl >= u * A.haps_per_block ? 1u : 0u;
+            flags = hp.flags;
+            region = hp.region;
+            mask = score_candidate(A, words, hp, hap, g, win, &key0);
         }
         // a donor's hit is its sharers' too (shared windows): the lane's class and entries
         uint32_t sc = 0, sn = 0;
         uint64_t se = 0;
-        if (shared && mask && (s_hd[hap - h0].z & HAP_DEDUP)) {
+        if (shared && mask && (flags & HAP_DEDUP)) {
             sc = strand_class(A, g);
             if (A.share_off[sc]) {
                 se = A.share_off[sc][hap];
                 sn = (uint32_t)(A.share_off[sc][hap + 1] - se);
             }
         }
-        const uint32_t mask0 = mask;
-        uint64_t act;
-        while ((act = __ballot(mask != 0)) != 0) {
-            if (mask) {
-                const uint32_t at = hn + __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32),
-                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0));
-                const uint32_t key = key0 + __builtin_ctz(mask);
-                mask &= mask - 1;
-                if (at < cap) out[at] = make_uint2(A.hap_base + hap, key);
-                else spill_record(A, s_hd2[hap - h0].x, A.hap_base + hap, key);
+        for (uint32_t u = 0; u < ngu; u++) {  // the lanes of group u (wave-uniform loop)
+            const bool in = !UNIT || gi == u;
+            uint2 *out = reinterpret_cast<uint2 *>(A.hitl) + (size_t)(slot + u) * A.hit_cap + (size_t)wave * cap;
+            uint32_t hn = (uint32_t)__builtin_amdgcn_readlane((int)hnv, (int)u);  // wave-uniform
+            const uint32_t listed = (uint32_t)__popcll(__ballot(k < n && in));  // (by the whole wave)
+            if (lane == u) cnv += listed;
+            uint32_t m = in ? mask : 0u;
+            uint64_t act;
+            while ((act = __ballot(m != 0)) != 0) {
+                if (m) {
+                    const uint32_t at = hn + __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32),
+                                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0));
+                    const uint32_t key = key0 + __builtin_ctz(m);
+                    m &= m - 1;
+                    if (at < cap) out[at] = make_uint2(A.hap_base + hap, key);
+                    else spill_record(A, region, A.hap_base + hap, key);
+                }
+                hn += (uint32_t)__popcll(act);
             }
-            hn += (uint32_t)__popcll(act);
-        }
-        // expansion, one hit at a time: 64 lanes test 64 of the donor's entries, each
-        // covering entry's sharer gets the hit's pairs (the same ballot-prefix append)
-        for (uint64_t todo = __ballot(sn != 0); todo; todo &= todo - 1) {
-            const int src = __builtin_ctzll(todo);
-            const uint32_t d_c = (uint32_t)__shfl((int)sc, src), d_n = (uint32_t)__shfl((int)sn, src);
-            const uint64_t d_e = (uint64_t)(uint32_t)__shfl((int)(uint32_t)se, src) |
-                                 ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(se >> 32), src) << 32);
-            const uint32_t d_i = (uint32_t)__shfl((int)win, src), d_key0 = (uint32_t)__shfl((int)key0, src);
-            const uint32_t d_mask = (uint32_t)__shfl((int)mask0, src);
-            const uint32_t d_region = s_hd2[(uint32_t)__shfl((int)hap, src) - h0].x;
-            for (uint32_t e0 = 0; e0 < d_n; e0 += 64) {
-                uint2 s = make_uint2(0, 0);
-                if (e0 + lane < d_n) s = A.share[d_c][d_e + e0 + lane];
-                const bool mine = d_i >= (s.y & 0xFFFFu) && d_i < (s.y >> 16);  // (no entry: [0, 0))
-                const uint64_t cov = __ballot(mine);
-                if (!cov) continue;
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(cov >> 32),
-                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)cov, 0));
-                for (uint32_t m = d_mask; m; m &= m - 1) {
-                    if (mine) {
-                        const uint32_t at = hn + rank, key = d_key0 + __builtin_ctz(m);
-                        if (at < cap) out[at] = make_uint2(A.hap_base + s.x, key);
-                        else spill_record(A, d_region, A.hap_base + s.x, key);
+            // expansion, one hit at a time: 64 lanes test 64 of the donor's entries, each
+            // covering entry's sharer gets the hit's pairs (the same ballot-prefix append)
+            for (uint64_t todo = __ballot(in && sn != 0); todo; todo &= todo - 1) {
+                const int src = __builtin_ctzll(todo);
+                const uint32_t d_c = (uint32_t)__shfl((int)sc, src), d_n = (uint32_t)__shfl((int)sn, src);
+                const uint64_t d_e = (uint64_t)(uint32_t)__shfl((int)(uint32_t)se, src) |
+                                     ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(se >> 32), src) << 32);
+                const uint32_t d_i = (uint32_t)__shfl((int)win, src), d_key0 = (uint32_t)__shfl((int)key0, src);
+                const uint32_t d_mask = (uint32_t)__shfl((int)mask, src);
+                const uint32_t d_region = (uint32_t)__shfl((int)region, src);
+                for (uint32_t e0 = 0; e0 < d_n; e0 += 64) {
+                    uint2 s = make_uint2(0, 0);
+                    if (e0 + lane < d_n) s = A.share[d_c][d_e + e0 + lane];
+                    const bool mine = d_i >= (s.y & 0xFFFFu) && d_i < (s.y >> 16);  // (no entry: [0, 0))
+                    const uint64_t cov = __ballot(mine);
+                    if (!cov) continue;
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(cov >> 32),
+                                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)cov, 0));
+                    for (uint32_t dm = d_mask; dm; dm &= dm - 1) {
+                        if (mine) {
+                            const uint32_t at = hn + rank, key = d_key0 + __builtin_ctz(dm);
+                            if (at < cap) out[at] = make_uint2(A.hap_base + s.x, key);
+                            else spill_record(A, d_region, A.hap_base + s.x, key);
+                        }
+                        hn += (uint32_t)__popcll(cov);
                     }
-                    hn += (uint32_t)__popcll(cov);
                 }
             }
+            if (lane == u) hnv = hn;
         }
     }
-    if (lane == 0) {
-        A.hitn[(size_t)slot * kMBlockWaves + wave] = min(hn, cap);
+    if (lane < ngu) {  // every slot of the unit, also a group's without a window
+        A.hitn[(size_t)(slot + lane) * kMBlockWaves + wave] = min(hnv, cap);
         // (the list counters: per-wave stores summed on the host -- one atomic per wave on a
         // shared counter serialises at L2, ~10 ns each, and doubled the C3 step)
-        A.candn[(size_t)slot * kMBlockWaves + wave] = cn;
+        A.candn[(size_t)(slot + lane) * kMBlockWaves + wave] = cnv;
     }
 }
 
@@ -499,8 +533,9 @@ __device__ __forceinline__ void record_bits(const v16f &acc, uint32_t (&x)[4]) {
 // per lane per pass.
 __device__ __forceinline__ void list_mask(const ScanArgs &A, const GroupCtx &G, uint32_t wave, uint32_t m, uint32_t gl,
                                           uint32_t ent, uint32_t &cn) {
-    const uint32_t lcap = wave_lds_cap(A), cap = lcap + wave_cand_cap(A);
-    uint2 *glist = cand_list(A, G.slot, wave);
+    const WaveCands W = unit_cands(A, G.slot, G.ub >> 16, wave);  // (G.slot: the unit's first)
+    const uint32_t lcap = min(W.ccap, kWaveCands), cap = lcap + W.ccap;
+    uint2 *glist = W.clist;
     const uint32_t hl = ent & (kMMaxHapsPerBlock - 1), i = ent >> 6;
     const uint32_t gbase = (gl & ~63u) + 8 * ((gl >> 5) & 1u);  // the tile's first strand; lanes 32-63: pairs + 4
     uint64_t act;
@@ -512,7 +547,7 @@ __device__ __forceinline__ void list_mask(const ScanArgs &A, const GroupCtx &G, 
             const uint32_t g = gbase + 2 * ((r & 3u) + 8 * (r >> 2)) + (b >> 4);
             const uint32_t slot = cn + __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32),
                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0));
-            const uint2 c = make_uint2(g | (hl << 24), i);
+            const uint2 c = make_uint2(g | (((G.ub & 0xFFFFu) + hl) << 24), i);
             if (slot < lcap) {
                 s_cand[wave][slot] = c;
             } else if (slot < cap) {
@@ -636,9 +671,10 @@ __device__ __forceinline__ void load_frag0(const char *tile, uint32_t lane, BFra
 // shader cycles from a two-tile round's top to its first MFMA's issue (the chunk-0 B
 // fragment and the matrix pipe), first to last MFMA issued, last MFMA to the test's
 // decision, the firing path; rounds, fired rounds; the super tiles' restaging; the
-// pairs' own work (next pair, list entries, A fragments).  s_memtime between
+// pairs' own work (next pair, list entries, A fragments); [8] (stamp word 3) a unit's
+// per-group restaging inside the super tiles.  s_memtime between
 // scheduling barriers: the stamps order the round but add their own latency.
-__shared__ unsigned long long s_rprof[kMBlock / 64][8];
+__shared__ unsigned long long s_rprof[kMBlock / 64][9];
 #define RPROF_T() ({ __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
                      __builtin_amdgcn_sched_barrier(0); t_; })
 #define RPROF_ADD(wave, k, v) do { if ((threadIdx.x & 63) == 0) s_rprof[wave][k] += (v); } while (0)
@@ -777,8 +813,9 @@ __device__ __forceinline__ void entry_onehot(const ScanArgs &A, const uint32_t *
 // together however the windows fall -- and the next pair's list entries are
 // loaded while the current pair is scored.
 #ifdef TFBS_SCAN_PROF
-// per wave: [0] s_memtime at the kernel's start, [1] after the staging barrier, [2]
-// after the scan loops, [3] (the same), [4] after the rescoring, [5] / [6]
+// per wave of the workgroup's (unit's) first slot: [0] s_memtime at the kernel's start,
+// [1] after the staging barrier, [2] after the scan loops, [3] cycles of the per-group
+// restaging (TFBS_ROUND_PROF, else 0), [4] after the rescoring, [5] / [6]
 // s_memrealtime (100 MHz, one clock for the chip) at the start and the end, [7] pairs
 // scored | candidates << 32; [8, 16) TFBS_ROUND_PROF's split
 #define SCAN_STAMP(k, v) \
@@ -792,7 +829,7 @@ __device__ __forceinline__ void entry_onehot(const ScanArgs &A, const uint32_t *
 // candidates, carried over super tiles).  Returns the pairs this wave scored.
 template <int NK>
 __device__ __forceinline__ uint32_t scan_loop(const ScanArgs &A, const DevMSuper &S, const char *s_img,
-                                              const uint32_t *words, uint32_t hg, uint32_t slot, uint32_t lane,
+                                              const uint32_t *words, uint32_t hg, uint32_t slot, uint32_t ub, uint32_t lane,
                                               uint32_t wave, uint32_t &qn, uint32_t &cn) {
     const uint32_t h0 = hg * A.haps_per_block;
     const uint32_t h1 = min(h0 + A.haps_per_block, A.n_haps);
@@ -804,6 +841,7 @@ __device__ __forceinline__ uint32_t scan_loop(const ScanArgs &A, const DevMSuper
     G.tile0 = S.tile0;
     G.h0 = h0;
     G.slot = slot;
+    G.ub = ub;
     const uint32_t ntile = (G.nw + kMWindows - 1) / kMWindows, npair = (ntile + 1) / 2;
     const float a0f = __uint_as_float(S.acc0);
     v16f cb = {a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f};
@@ -863,19 +901,24 @@ __device__ __forceinline__ void stage_image(const ScanArgs &A, const DevMSuper &
 }
 
 // The one-hot table (4-mer code -> 64 bits, column t (16 bits) holds FP4 1.0 (0x2)
-// in the nibble of its base), the group's descriptors and (STAGED) its packed
-// words after the image budget; returns the words' base for DevHap::word_off.
-template <bool STAGED>
-__device__ __forceinline__ const uint32_t *stage_group(const ScanArgs &A, int32_t *smem, uint32_t h0, uint32_t hn) {
+// in the nibble of its base): once per workgroup.
+__device__ __forceinline__ void stage_onehot(int32_t *smem) {
     uint2 *tab = reinterpret_cast<uint2 *>(smem);
     for (uint32_t k = threadIdx.x; k < 256; k += kMBlock) {
         uint32_t h[4];
         for (int t = 0; t < 4; t++) h[t] = 2u << (4 * ((k >> (2 * t)) & 3));
         tab[k] = make_uint2(h[0] | (h[1] << 16), h[2] | (h[3] << 16));
     }
-    if (threadIdx.x < hn) {  // (32 of DevHap's 48 bytes)
+}
+
+// A group's descriptors and (STAGED) its packed words after the image budget; returns
+// the words' base for DevHap::word_off.  (A unit restages them per group inside each
+// super tile: ~2 KB of descriptors and ~5 KB of words at C3, against the image's 36-44.)
+template <bool STAGED, bool HD2 = true>
+__device__ __forceinline__ const uint32_t *stage_group(const ScanArgs &A, int32_t *smem, uint32_t h0, uint32_t hn) {
+    if (threadIdx.x < hn) {  // (32 of DevHap's 48 bytes; HD2: the rescoring's half)
         s_hd[threadIdx.x] = A.hd[h0 + threadIdx.x];
-        s_hd2[threadIdx.x] = A.hd2[h0 + threadIdx.x];
+        if (HD2) s_hd2[threadIdx.x] = A.hd2[h0 + threadIdx.x];
     }
     if (!STAGED) return A.words;
     const uint4 f = A.hd[h0], l = A.hd[h0 + hn - 1];
@@ -903,6 +946,7 @@ __global__ __launch_bounds__(kMBlock, kMfmaMinWaves[NK]) void scan_mfma_kernel(S
     const uint32_t hn = min(h0 + A.haps_per_block, A.n_haps) - h0;
     stage_image(A, S, reinterpret_cast<uint4 *>(smem));
     if (threadIdx.x == 0) s_hnext = 0;
+    stage_onehot(smem);
     const uint32_t *words = stage_group<STAGED>(A, smem, h0, hn);
     __syncthreads();
     const char *s_img = reinterpret_cast<const char *>(smem) + kMOnehotBytes;
@@ -914,11 +958,10 @@ __global__ __launch_bounds__(kMBlock, kMfmaMinWaves[NK]) void scan_mfma_kernel(S
     SCAN_STAMP(1, __builtin_amdgcn_s_memtime());
 #endif
     uint32_t qn = 0, cn = 0;
-    const uint32_t n_pairs = scan_loop<NK>(A, S, s_img, words, hg, slot, lane, wave, qn, cn);
+    const uint32_t n_pairs = scan_loop<NK>(A, S, s_img, words, hg, slot, unit_place(0, 1), lane, wave, qn, cn);
     (void)n_pairs;
     SCAN_STAMP(2, __builtin_amdgcn_s_memtime());
-    SCAN_STAMP(3, __builtin_amdgcn_s_memtime());
-    rescore_list(A, words, h0, slot, wave, lane, cn);
+    rescore_list<false>(A, words, h0, slot, 1, wave, lane, cn);
     SCAN_STAMP(4, __builtin_amdgcn_s_memtime());
     SCAN_STAMP(6, __builtin_amdgcn_s_memrealtime());
     SCAN_STAMP(7, (unsigned long long)n_pairs | ((unsigned long long)cn << 32));
@@ -939,17 +982,29 @@ __device__ void post_one_block(const ScanArgs &A, uint32_t tid, uint32_t n_regio
                                uint32_t *__restrict__ report, uint32_t *__restrict__ need_wide, uint32_t *s_sum);
 namespace {
 
-template <bool STAGED>
+// UNIT: the workgroup's haplotypes are a unit of A.unit consecutive groups (the
+// last unit may be short).  The one-hot table is built and each super tile's image
+// staged once per unit; inside a super tile the unit's groups follow one another --
+// per group only the descriptors and packed words are restaged and the pair counter
+// reset, between two barriers (the first group's with the image) -- and scan_loop runs
+// per group as it is.  The wave's candidates of all groups and super tiles share one
+// list and are rescored once (rescore_list<true>); every group keeps its own slot for
+// the hit lists and counts.  !UNIT is the kernel of one group per workgroup.
+template <bool STAGED, bool UNIT>
 __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
 #ifdef TFBS_SCAN_PROF
     const unsigned long long t_start = __builtin_amdgcn_s_memtime(), r_start = __builtin_amdgcn_s_memrealtime();
 #endif
     int32_t *smem = s_mdyn;
-    const uint32_t hg = A.gorder ? A.gorder[blockIdx.x] : blockIdx.x;  // (its lists and stamps at slot hg)
-    const uint32_t slot = A.region_base + hg;
-    const uint32_t h0 = hg * A.haps_per_block;
-    const uint32_t hn = min(h0 + A.haps_per_block, A.n_haps) - h0;
-    const uint32_t *words = stage_group<STAGED>(A, smem, h0, hn);
+    const uint32_t hpb = A.haps_per_block;
+    const uint32_t un = A.gorder ? A.gorder[blockIdx.x] : blockIdx.x;  // (its lists and stamps at its first slot)
+    const uint32_t hg0 = UNIT ? un * A.unit : un;
+    const uint32_t ngu = UNIT ? min(A.unit, (A.n_haps + hpb - 1) / hpb - hg0) : 1u;  // the unit's groups
+    const uint32_t slot = A.region_base + hg0;
+    const uint32_t h0 = hg0 * hpb;
+    stage_onehot(smem);
+    const uint32_t *words = nullptr;
+    if (!UNIT) words = stage_group<STAGED>(A, smem, h0, min(h0 + hpb, A.n_haps) - h0);
     const char *s_img = reinterpret_cast<const char *>(smem) + kMOnehotBytes;
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #ifdef TFBS_SETPRIO
@@ -960,7 +1015,7 @@ __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
     bool first = true;
 #endif
 #ifdef TFBS_ROUND_PROF
-    if (threadIdx.x < kMBlockWaves * 8) (&s_rprof[0][0])[threadIdx.x] = 0;
+    if (threadIdx.x < kMBlockWaves * 9) (&s_rprof[0][0])[threadIdx.x] = 0;
 #endif
     for (uint32_t si = 0; si < A.n_msupers; si++) {
         const DevMSuper S = A.msupers[si];
@@ -972,33 +1027,46 @@ __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
         if (si == 0)
 #endif
         stage_image(A, S, reinterpret_cast<uint4 *>(smem));
-        if (threadIdx.x == 0) s_hnext = 0;
-        __syncthreads();
+        for (uint32_t gi = 0; gi < ngu; gi++) {
 #ifdef TFBS_ROUND_PROF
-        if (si) RPROF_ADD(wave, 6, RPROF_T() - ts0);
+            const unsigned long long tg0 = RPROF_T();
+#endif
+            if (UNIT) {
+                if (gi) __syncthreads();  // the previous group's readers are done
+                const uint32_t gh0 = h0 + gi * hpb;
+                words = stage_group<STAGED, false>(A, smem, gh0, min(gh0 + hpb, A.n_haps) - gh0);
+            }
+            if (threadIdx.x == 0) s_hnext = 0;
+            __syncthreads();
+#ifdef TFBS_ROUND_PROF
+            if (gi) RPROF_ADD(wave, 8, RPROF_T() - tg0);
+            else if (si) RPROF_ADD(wave, 6, RPROF_T() - ts0);
 #endif
 #ifdef TFBS_SCAN_PROF
-        if (first) {
-            SCAN_STAMP(0, t_start);
-            SCAN_STAMP(5, r_start);
-            SCAN_STAMP(1, __builtin_amdgcn_s_memtime());
-            first = false;
-        }
+            if (first) {
+                SCAN_STAMP(0, t_start);
+                SCAN_STAMP(5, r_start);
+                SCAN_STAMP(1, __builtin_amdgcn_s_memtime());
+                first = false;
+            }
 #endif
-        n_pairs += S.nk > 2 ? scan_loop<4>(A, S, s_img, words, hg, slot, lane, wave, qn, cn)
-                            : scan_loop<2>(A, S, s_img, words, hg, slot, lane, wave, qn, cn);
+            const uint32_t ub = unit_place(gi * hpb, ngu);
+            n_pairs += S.nk > 2 ? scan_loop<4>(A, S, s_img, words, hg0 + gi, slot, ub, lane, wave, qn, cn)
+                                : scan_loop<2>(A, S, s_img, words, hg0 + gi, slot, ub, lane, wave, qn, cn);
+        }
     }
     (void)n_pairs;
     SCAN_STAMP(2, __builtin_amdgcn_s_memtime());
-    SCAN_STAMP(3, __builtin_amdgcn_s_memtime());
 #ifndef TFBS_AB_NORESCORE  // timing ablation (wrong results): no rescoring
-    rescore_list(A, words, h0, slot, wave, lane, cn);
+    if (UNIT) rescore_list<true>(A, A.words, h0, slot, ngu, wave, lane, cn);
+    else rescore_list<false>(A, words, h0, slot, 1, wave, lane, cn);
 #endif
     SCAN_STAMP(4, __builtin_amdgcn_s_memtime());
     SCAN_STAMP(6, __builtin_amdgcn_s_memrealtime());
     SCAN_STAMP(7, (unsigned long long)n_pairs | ((unsigned long long)cn << 32));
 #ifdef TFBS_ROUND_PROF
     for (int k = 0; k < 8; k++) SCAN_STAMP(8 + k, s_rprof[wave][k]);
+    SCAN_STAMP(3, s_rprof[wave][8]);  // the per-group restaging inside the super tiles
 #endif
     if (A.post_done) {  // fused post-scan: the last workgroup to finish does it
         __syncthreads();  // every wave's lists and spill records are written
@@ -1375,7 +1443,10 @@ template <int NK> MfmaKernel mfma_nk(bool staged) {
 MfmaKernel mfma_variant(bool staged, uint32_t nk) {  // depth classes (mfma_depth_class)
     return nk <= 2 ? mfma_nk<2>(staged) : mfma_nk<4>(staged);
 }
-MfmaKernel mfma_all_variant(bool staged) { return staged ? scan_mfma_all_kernel<true> : scan_mfma_all_kernel<false>; }
+MfmaKernel mfma_all_variant(bool staged, bool unit) {
+    if (unit) return staged ? scan_mfma_all_kernel<true, true> : scan_mfma_all_kernel<false, true>;
+    return staged ? scan_mfma_all_kernel<true, false> : scan_mfma_all_kernel<false, false>;
+}
 
 }  // namespace
 
@@ -1710,17 +1781,20 @@ int launch_mfma_all(const ScanArgs &a0, const DevMSuper *supers, uint32_t n_supe
     // (TFBS_SCAN_LDS_MIN: an occupancy A/B -- more LDS per workgroup, fewer per CU)
     static const size_t lds_min = getenv("TFBS_SCAN_LDS_MIN") ? (size_t)atol(getenv("TFBS_SCAN_LDS_MIN")) : 0;
     const size_t lds = std::max(staged ? staged_bytes : base, lds_min);
-    const MfmaKernel kern = mfma_all_variant(staged);
+    // a unit of G groups per workgroup (ScanArgs::unit); G = 1: the kernel of one group
+    const uint32_t G = std::min(std::max(a0.unit, 1u), kMMaxUnit);
+    const MfmaKernel kern = mfma_all_variant(staged, G > 1);
     hipError_t e = hipSuccess;
     if (lds > 64 * 1024)
         e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("MFMA LDS attribute: ") + hipGetErrorString(e));
     int launches = 0;
-    const uint64_t max_hg = (1ull << 31) - 1;
+    const uint64_t max_hg = ((1ull << 31) - 1) / kMMaxUnit * kMMaxUnit;  // whole units per launch
     for (uint64_t g0 = 0; g0 < n_hg; g0 += max_hg) {
         const uint32_t ng = (uint32_t)std::min<uint64_t>(max_hg, n_hg - g0);
         const uint32_t h0 = (uint32_t)(g0 * hpb);
         ScanArgs a = a0;
+        a.unit = G;
         a.haps = a0.haps + h0;
         a.hd = a0.hd + h0;
         a.hd2 = a0.hd2 + h0;
@@ -1733,7 +1807,7 @@ int launch_mfma_all(const ScanArgs &a0, const DevMSuper *supers, uint32_t n_supe
         if (*n_srcs >= (uint32_t)kMaxHitSrcs) return fail(TFBS_E_ARG, "matrix-core scan: too many launches");
         srcs[(*n_srcs)++] = HitSrc{(uint32_t)g0, 1, (uint32_t)g0, ng};
         a.mimg_max = (uint32_t)img_bytes;
-        hipLaunchKernelGGL(kern, dim3(ng), dim3(kMBlock), lds, stream, a);
+        hipLaunchKernelGGL(kern, dim3((ng + G - 1) / G), dim3(kMBlock), lds, stream, a);
         launches++;
     }
     e = hipGetLastError();

@@ -2,10 +2,15 @@
 """Summarise a TFBS_SCAN_PROF dump (a TFBS_SCAN_PROF build of scan_mfma.hip,
 tools/variant_build.sh scan_mfma NAME:-DTFBS_SCAN_PROF, run with
 TFBS_SCAN_PROF=<file>): per launch (depth class), the waves' time in each phase --
-staging (kernel start to the staging barrier), the scan loop, the last queue drain,
-the rescoring -- in shader cycles, pairs of window tiles per wave, candidates per
-wave, and from the chip-wide 100 MHz clock the launch's span and its tail (the
-time after 90 / 99 % of its workgroups ended).  The last scan in the file is read.
+staging (kernel start to the first staging barrier), the scan loop, the rescoring --
+in shader cycles, pairs of window tiles per wave, candidates per wave, and from the
+chip-wide 100 MHz clock the launch's span and its tail (the time after 90 / 99 % of
+its workgroups ended).  The merged kernel's stamps are per (unit, wave), at the unit's
+first slot (a unit: the haplotype groups one workgroup scans, TFBS_SCAN_UNIT): pairs
+and phases are per wave of a unit.  A TFBS_ROUND_PROF build adds the rounds' clock
+split and, as shares of the loop, the super tiles' restaging and the per-group
+restaging inside a super tile (a unit's groups after its first: descriptors, words,
+two barriers).  The last scan in the file is read.
 
 Usage: python tools/scan_prof.py FILE [OUT_JSON]
 """
@@ -37,8 +42,7 @@ def main():
         ph = {
             "staging": w[:, :, 1] - w[:, :, 0],
             "loop": w[:, :, 2] - w[:, :, 1],
-            "drain": w[:, :, 3] - w[:, :, 2],
-            "rescore": w[:, :, 4] - w[:, :, 3],
+            "rescore": w[:, :, 4] - w[:, :, 2],
         }
         tot = sum(ph.values())
         pairs = (w[:, :, 7] & 0xFFFFFFFF)[live]
@@ -64,6 +68,7 @@ def main():
         }
         if w[:, :, 12].sum() > 0:  # TFBS_ROUND_PROF build: the two-tile rounds' clock split
             rb, rm, rt, rf, nr, nf, rs, pp = (w[:, :, 8 + k][live].sum() for k in range(8))
+            gr = w[:, :, 3][live].sum()  # the per-group restaging (stamp word 3)
             loop = ph["loop"][live].sum()
             rec["round_split"] = {
                 "rounds_per_wave": float(nr / live.sum()), "fired_share": float(nf / max(1, nr)),
@@ -71,8 +76,11 @@ def main():
                                      "last_mfma_to_test": float(rt / nr), "firing_path": float(rf / nr)},
                 "loop_share": {"to_first_mfma": float(rb / loop), "first_to_last_mfma": float(rm / loop),
                                "last_mfma_to_test": float(rt / loop), "firing_path": float(rf / loop),
-                               "restaging": float(rs / loop), "pair_setup": float(pp / loop),
-                               "other": float(1 - (rb + rm + rt + rf + rs + pp) / loop)},
+                               "restaging": float(rs / loop), "group_restaging": float(gr / loop),
+                               "pair_setup": float(pp / loop),
+                               "other": float(1 - (rb + rm + rt + rf + rs + gr + pp) / loop)},
+                "cycles_mean_per_wave": {"restaging": float(rs / live.sum()),
+                                         "group_restaging": float(gr / live.sum())},
             }
         out["launches"].append(rec)
     if len(sys.argv) > 2:
