@@ -288,6 +288,19 @@ def counts_as_genotypes(v1, v2, verbose=False):
     return counts, maf.value, f0, f1, f2, gts.value.decode()
 
 
+# tfbs_batch_assembly_paths' bits (tfbs_amd.h TFBS_PATH_*)
+PATH_BITS = {"FAST": 1 << 0, "BIG": 1 << 1, "WALK": 1 << 2, "STEPBITS": 1 << 3, "DIRTY_LISTED": 1 << 4,
+             "COR_ARENA": 1 << 5, "LISTS_SLICED": 1 << 6, "RUNS_L2": 1 << 7, "HAP_GLOBAL": 1 << 8, "U32": 1 << 9,
+             "CNT_ARENA": 1 << 10, "TICKET": 1 << 11, "GIVEUP": 1 << 12, "ASM": 1 << 16, "ASM_HAPS": 1 << 17,
+             "ASM_RUNS": 1 << 18, "ASM_HITS": 1 << 19, "ASM_REFS": 1 << 20, "ASM_SCRATCH": 1 << 21}
+PATH_WHY_SHIFT = 13
+
+
+def path_why(word):
+    """TFBS_PATH_WHY: key_fast_kernel's give-up reason of a word with GIVEUP set."""
+    return (word >> PATH_WHY_SHIFT) & 7
+
+
 class Scanner:
     """A device context: the pattern tables resident on one GPU (one per host thread)."""
 
@@ -311,6 +324,22 @@ class Scanner:
         out = (C.c_uint64 * 3)()
         check(lib().tfbs_ctx_rows_bgzf_blocks(self.h, out))
         return dict(zip(("blocks", "wave", "stored"), (int(x) for x in out)))
+
+    def assembly_trace(self, on=True):
+        """tfbs_ctx_assembly_trace: the assemblies enqueued from now on report each region's path
+        (RegionBatch.assembly_paths)."""
+        check(lib().tfbs_ctx_assembly_trace(self.h, 1 if on else 0))
+
+    def assembly_figures(self):
+        """tfbs_ctx_assembly_figures of the last checked assembly: {"left" (regions left to
+        key_asm_kernel), "arena" (arena words asked for), "spill" (spill records), "wide" /
+        "leftover" (it launched the wide spill kernels / the leftover pass), and since the scanner
+        was made "reruns" (lean assemblies run again in full), "reruns_wide" / "reruns_leftover"
+        (those that needed the wide kernels / the leftover pass)}."""
+        out = (C.c_uint64 * 8)()
+        check(lib().tfbs_ctx_assembly_figures(self.h, out))
+        return dict(zip(("left", "arena", "spill", "wide", "leftover", "reruns", "reruns_wide", "reruns_leftover"),
+                        (int(x) for x in out)))
 
     def matches_all(self, haplotype):
         """pattern.rs:141-171 for every pattern: list (per pattern, creation order) of [(start, end)]."""
@@ -513,6 +542,28 @@ class RegionBatch:
         out = (C.c_uint64 * 7)()
         check(lib().tfbs_batch_encode_stats(self.h, out))
         return dict(zip(("keys", "w2", "w4", "w8", "no_pairs", "range", "values"), (int(x) for x in out)))
+
+    def assembly_paths(self, scanner):
+        """tfbs_batch_assembly_paths: the TFBS_PATH_* word of every region from the last checked
+        assembly on a scanner with assembly_trace() on."""
+        n = self.num_regions
+        out = (C.c_uint32 * max(1, n))()
+        check(lib().tfbs_batch_assembly_paths(scanner.h, self.h, out, n))
+        return [int(x) for x in out[:n]]
+
+    def layout(self, region):
+        """tfbs_batch_region_layout: (hap_begin, hap_count, ref_hap or None, n_inner)."""
+        out = (C.c_uint32 * 4)()
+        check(lib().tfbs_batch_region_layout(self.h, region, out))
+        return out[0], out[1], (None if out[2] == 0xFFFFFFFF else out[2]), out[3]
+
+    def hap_runs(self, region, h):
+        """tfbs_batch_region_hap_runs: (reuses the reference's hits, offset of its runs in the
+        batch's run array, [(a, b)] its diff runs in the reference's columns)."""
+        reuses, off, n = C.c_int(), C.c_uint32(), C.c_uint32()
+        ab = (C.c_uint32 * 64)()
+        check(lib().tfbs_batch_region_hap_runs(self.h, region, h, C.byref(reuses), C.byref(off), C.byref(n), ab, 32))
+        return bool(reuses.value), off.value, [(ab[2 * k], ab[2 * k + 1]) for k in range(n.value)]
 
     def keys(self, region):
         """count_matches_by_sample for one region: {(bed, (s, e), pattern_id): (L, R)}."""

@@ -140,6 +140,12 @@ SIGNATURES = [
     ("tfbs_batch_assemble_wait", C.c_int, [vp, vp]),
     ("tfbs_step", C.c_int, [vp, vp]),
     ("tfbs_ctx_last_assemble_ms", C.c_float, [vp]),
+    ("tfbs_ctx_assembly_trace", C.c_int, [vp, C.c_int]),
+    ("tfbs_batch_assembly_paths", C.c_int, [vp, vp, u32p, C.c_uint32]),
+    ("tfbs_ctx_assembly_figures", C.c_int, [vp, u64p]),
+    ("tfbs_batch_region_layout", C.c_int, [vp, C.c_size_t, u32p]),
+    ("tfbs_batch_region_hap_runs", C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(C.c_int), u32p, u32p, u32p,
+                                            C.c_uint32]),
     ("tfbs_batch_encode", C.c_int, [vp, vp, C.c_size_t, C.c_size_t]),
     ("tfbs_batch_encode_flags", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_int]),
     ("tfbs_batch_encode_stats", C.c_int, [vp, u64p]),

@@ -223,6 +223,15 @@ struct tfbs_ctx {
     uint32_t asm_order_big = 0;       // the first of them with more than key_fast_big_u() haplotypes
     bool kf_prof_on = false;
     bool kf_persistent = true;        // TFBS_KF_PERSIST=0: one workgroup per region
+    uint32_t kf_grid = 0;             // TFBS_KF_GRID=n: at most n persistent workgroups per shape (0: what fits)
+    int kf_big_u = 0;                 // TFBS_KF_BIGU: regions of more haplotypes take the big shape (0: none)
+    // tfbs_ctx_assembly_trace: the assembly kernels' path word per region (AsmArgs::path)
+    bool asm_trace = false;
+    bool asm_traced = false;          // the last enqueued assembly wrote asm_path
+    DevBuf<uint32_t> asm_path;
+    // lean assemblies assembly_wait ran again in full: all, those that needed the wide spill
+    // kernels, those that needed the leftover pass
+    uint64_t asm_reruns = 0, asm_reruns_wide = 0, asm_reruns_left = 0;
     // two slots of block batches (one being made, one copied back and written)
     static constexpr int kBgSlots = 3;  // batches of blocks in flight: two queued while one is written out
     DevBuf<uint8_t> bg_out[kBgSlots], bg_packed[kBgSlots];
@@ -882,7 +891,7 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     ctx->enc_vals_c.release(); ctx->enc_hist_c.release(); ctx->enc_val_off.release();
     ctx->bg_rows.release(); ctx->bg_heads.release(); ctx->bg_tok_text.release(); ctx->bg_tok_len.release();
     ctx->bg_tok_lit.release(); ctx->bg_tok_litn.release();
-    ctx->bg_cum.release(); ctx->bg_crc.release(); ctx->bg_plans.release(); ctx->bg_prof.release(); ctx->kf_prof.release(); ctx->asm_order.release();
+    ctx->bg_cum.release(); ctx->bg_crc.release(); ctx->bg_plans.release(); ctx->bg_prof.release(); ctx->kf_prof.release(); ctx->asm_path.release(); ctx->asm_order.release();
     for (int k = 0; k < tfbs_ctx::kBgSlots; k++) {
         ctx->bg_out[k].release(); ctx->bg_packed[k].release(); ctx->bg_out_len[k].release(); ctx->bg_off[k].release();
         ctx->bg_host[k].release();
@@ -937,6 +946,8 @@ int tfbs_ctx_create(int device, const tfbs_patterns *p, tfbs_ctx **out) {
     ctx->debug_over = env_int("TFBS_DEBUG_OVER", 0) != 0;
     ctx->kf_prof_on = env_int("TFBS_KF_PROF", 0) != 0;
     ctx->kf_persistent = env_int("TFBS_KF_PERSIST", 1) != 0;
+    ctx->kf_grid = (uint32_t)std::max(0, env_int("TFBS_KF_GRID", 0));
+    ctx->kf_big_u = env_int("TFBS_KF_BIGU", (int)key_fast_big_u());  // (0: every region on one shape)
     ctx->asm_lean_mode = env_int("TFBS_ASM_LEAN", 1);
     ctx->post_fuse_env = env_int("TFBS_POST_FUSE", 0) != 0;  // (measured: C2 0.083 vs 0.068 ms -- a ticket atomic per scan workgroup)
     ctx->step_graphs = env_int("TFBS_STEP_GRAPH", 1) != 0 && !getenv("TFBS_SCAN_PROF") && !ctx->kf_prof_on &&
@@ -1141,7 +1152,7 @@ int tfbs_batch_upload(tfbs_ctx *ctx, tfbs_batch *b) {
         if ((rc = ctx->asm_order.put(order, ctx->stream))) return rc;
         ctx->asm_order_n = (uint32_t)order.size();
         ctx->asm_order_big = 0;
-        static const int big_u = env_int("TFBS_KF_BIGU", (int)key_fast_big_u());  // (0: every region on one shape)
+        const int big_u = ctx->kf_big_u;
         while (big_u > 0 && ctx->asm_order_big < order.size() &&
                B.regions[order[ctx->asm_order_big]].hap_count > (uint32_t)big_u)
             ctx->asm_order_big++;
@@ -1289,6 +1300,13 @@ static int enqueue_assembly(tfbs_ctx *ctx, Batch &B, bool post) {
     a.order = ctx->asm_order_n == nr ? ctx->asm_order.p : nullptr;
     a.persist = ctx->kf_persistent ? 1u : 0u;
     a.next = ctx->asm_ctr.p + 16;
+    a.grid_cap = ctx->kf_grid;
+    ctx->asm_traced = ctx->asm_trace;
+    if (ctx->asm_trace && nr) {
+        if ((rc = ctx->asm_path.ensure(nr))) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->asm_path.p, 0, (size_t)nr * 4, ctx->stream));
+        a.path = ctx->asm_path.p;
+    }
     if (ctx->kf_prof_on && nr) {
         if ((rc = ctx->kf_prof.ensure((size_t)nr * 16))) return rc;
         HIP_TRY(hipMemsetAsync(ctx->kf_prof.p, 0, (size_t)nr * 128, ctx->stream));
@@ -1443,8 +1461,12 @@ static int assembly_wait(tfbs_ctx *ctx, Batch &B) {
         int rc;
         // a lean assembly that needed what it left out (more spill records than post_scan_kernel
         // buckets, or regions key_fast_kernel gave up): again with everything
-        if ((!ctx->asm_wide && ctx->asm_host[20]) || (!ctx->asm_leftover && ctx->asm_host[2])) {
+        const bool need_wide = !ctx->asm_wide && ctx->asm_host[20], need_left = !ctx->asm_leftover && ctx->asm_host[2];
+        if (need_wide || need_left) {
             ctx->asm_full = true;
+            ctx->asm_reruns++;
+            ctx->asm_reruns_wide += need_wide ? 1 : 0;
+            ctx->asm_reruns_left += need_left ? 1 : 0;
             rc = enqueue_assembly(ctx, B, true);
             ctx->asm_full = false;
             if (rc) return rc;
@@ -1580,7 +1602,7 @@ int tfbs_step(tfbs_ctx *ctx, tfbs_batch *b) {
         ctx->step_graph = nullptr;
     };
     // (another batch's varying counts in var_counts: tfbs_batch_assemble hands them over first)
-    const bool eligible = ctx->step_graphs && (!ctx->var_owner || ctx->var_owner == &B);
+    const bool eligible = ctx->step_graphs && !ctx->asm_trace && (!ctx->var_owner || ctx->var_owner == &B);
     const uint64_t sig = step_signature(ctx, b);
     int rc;
     if (eligible && ctx->step_exec && sig == ctx->step_sig) {  // replay
@@ -1631,6 +1653,39 @@ int tfbs_batch_assemble_wait(tfbs_ctx *ctx, tfbs_batch *b) {
         return tfbs::fail(TFBS_E_STATE, "no assembly of this batch on this ctx (tfbs_batch_assemble)");
     HIP_TRY(hipSetDevice(ctx->device));
     return assembly_wait(ctx, b->b);
+}
+
+int tfbs_ctx_assembly_trace(tfbs_ctx *ctx, int on) {
+    if (!ctx) return tfbs::fail(TFBS_E_ARG, "null argument");
+    ctx->asm_trace = on != 0;
+    return TFBS_OK;
+}
+
+int tfbs_batch_assembly_paths(tfbs_ctx *ctx, const tfbs_batch *b, uint32_t *mask, uint32_t n) {
+    if (!ctx || !b || (!mask && n)) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (!ctx->asm_trace) return tfbs::fail(TFBS_E_STATE, "the assembly trace is off (tfbs_ctx_assembly_trace)");
+    if (!ctx->asm_traced) return tfbs::fail(TFBS_E_STATE, "the last assembly ran before the assembly trace was turned on");
+    if (ctx->resident != b || ctx->asm_state != 2 || ctx->asm_batch != &b->b)
+        return tfbs::fail(TFBS_E_STATE, "no checked assembly of this batch on this ctx");
+    if (n != b->b.regions.size() || ctx->asm_path.n < n) return tfbs::fail(TFBS_E_ARG, "n is not the batch's regions");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n) HIP_TRY(hipMemcpyAsync(mask, ctx->asm_path.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return TFBS_OK;
+}
+
+int tfbs_ctx_assembly_figures(tfbs_ctx *ctx, uint64_t out[8]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (ctx->asm_state != 2 || !ctx->asm_host) return tfbs::fail(TFBS_E_STATE, "no checked assembly on this ctx");
+    out[0] = ctx->asm_host[2];
+    out[1] = ctx->asm_host[3];
+    out[2] = ctx->asm_host[0];
+    out[3] = ctx->asm_wide ? 1 : 0;
+    out[4] = ctx->asm_leftover ? 1 : 0;
+    out[5] = ctx->asm_reruns;
+    out[6] = ctx->asm_reruns_wide;
+    out[7] = ctx->asm_reruns_left;
+    return TFBS_OK;
 }
 
 float tfbs_ctx_last_assemble_ms(const tfbs_ctx *ctx) {

@@ -139,7 +139,12 @@ __global__ __launch_bounds__(kAsmBlock) void key_asm_kernel(AsmArgs A, const uin
     const uint32_t U = rg.hap_count, n_inner = rg.n_inner;
     const uint32_t K = A.n_slots * n_inner;
     const uint64_t ko = (uint64_t)rg.inner_off * A.n_slots;
+    // tfbs_ctx_assembly_trace: this kernel's bits (the list pass keeps key_fast_kernel's)
+    auto trace = [&](uint32_t pw) {
+        if (A.path && tid == 0) A.path[r] = (list ? A.path[r] : 0u) | TFBS_PATH_ASM | pw;
+    };
     if (U == 0 || K == 0) {  // no samples: no haplotype, no match, no key
+        trace(0);
         if (A.mode == 0)
             for (uint32_t j = tid; j < K; j += kAsmBlock) {
                 A.key_first[ko + j] = 0;
@@ -188,6 +193,9 @@ __global__ __launch_bounds__(kAsmBlock) void key_asm_kernel(AsmArgs A, const uin
     __syncthreads();
     const uint32_t nhit = s_nhit, nref = s_nref;
     const bool hits_lds = nhit <= kAsmHits, refs_lds = nref <= kAsmRefs;
+    trace((U > kAsmHaps ? TFBS_PATH_ASM_HAPS : 0u) | (run1 - run0 > kAsmRuns ? TFBS_PATH_ASM_RUNS : 0u) |
+          (hits_lds ? 0u : TFBS_PATH_ASM_HITS) | (refs_lds ? 0u : TFBS_PATH_ASM_REFS) |
+          (U > kAsmCounters ? TFBS_PATH_ASM_SCRATCH : 0u));
     auto each_hit = [&](auto &&f) {
         if (!A.mfma) return;
         if (hits_lds) {
@@ -532,7 +540,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     __shared__ uint32_t s_ncor, s_nref, s_run0, s_run1, s_nvar, s_arena, s_ndirty, s_lmax;
     __shared__ unsigned long long s_vbase, s_obase;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    auto process = [&](const uint32_t r) {  // one region (every exit is workgroup-uniform)
+    auto process = [&](const uint32_t r, const uint32_t by_ticket) {  // one region (every exit is workgroup-uniform)
     // TFBS_KF_PROF: phase times 0-7 (wall_clock64: 100 MHz), then sizes (U, entries, dirty reference hits, rows, chunks)
     auto stamp = [&](uint32_t k, uint64_t v) {
         if (A.prof && tid == 0) A.prof[16 * (size_t)r + k] = v;
@@ -541,7 +549,13 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     const DevRegion rg = A.regions[r];
     const uint32_t U = rg.hap_count, n_inner = rg.n_inner, K = A.n_slots * n_inner;
     const uint64_t ko = (uint64_t)rg.inner_off * A.n_slots;
+    // tfbs_ctx_assembly_trace: the region's path word, stored once where the region leaves
+    uint32_t pw = TFBS_PATH_FAST | (kFBlock == 1024 ? TFBS_PATH_BIG : 0u) | by_ticket;
+    auto trace = [&](uint32_t w) {
+        if (A.path && tid == 0) A.path[r] = w;
+    };
     if (U == 0 || K == 0) {  // no samples: no haplotype, no match, no key
+        trace(pw);
         for (uint32_t j = tid; j < K; j += kFBlock) {
             A.key_first[ko + j] = 0;
             A.key_flags[ko + j] = 0;
@@ -553,6 +567,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             A.redo[atomicAdd(A.redo_n, 1u)] = r;
             if (A.why) atomicAdd(A.why + why, 1u);  // (TFBS_DEBUG_OVER: the reasons)
         }
+        trace(pw | TFBS_PATH_GIVEUP | (why << TFBS_PATH_WHY_SHIFT));
     };
     if (U > (kFMaxU < A.fast_max_u ? kFMaxU : A.fast_max_u) || K > 32 * kFKeyWords || n_inner > 32) return give_up(0);
     const uint32_t hb = rg.hap_begin;
@@ -624,7 +639,9 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     if (lists_staged && tid == 0) s_loff[nl] = n_ent;
     stamp(1, wall_clock64());
     const uint32_t run0 = s_run0, nruns = s_run0 == kFNone ? 0u : s_run1 - s_run0;
+    if (!lists_staged) pw |= TFBS_PATH_LISTS_SLICED;
     if (nruns >= 65536) return give_up(2);
+    if (nruns > kFRuns) pw |= TFBS_PATH_RUNS_L2;
 #pragma unroll
     for (uint32_t q = 0; q < kFHapLds / kFBlock; q++) {
         const uint32_t l = tid + q * kFBlock;
@@ -670,6 +687,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     // f(l, ref hit, dirty): in pairwise mode called by every lane of the wave together
     // (uniform = true), else only for dirty pairs.
     const bool pairwise = (uint64_t)U * nref <= 65536;
+    if (!pairwise) pw |= TFBS_PATH_WALK;
     if (!pairwise) {  // the reference hits by window (rank sort; ties by list position)
         uint4 mine = make_uint4(0, 0, 0, 0);
         uint32_t rank = 0;
@@ -792,6 +810,8 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     // ones at the top), else a share of the launch's arena (the dirty ones first)
     const uint32_t need = n_ent + (sp.y - sp.x) + nD;  // (an upper bound: entries of other regions' haplotypes)
     const bool in_lds = need <= (kFCor < A.cor_lds ? kFCor : A.cor_lds);
+    pw |= (stepbits ? TFBS_PATH_STEPBITS : 0u) | (dirty_listed ? TFBS_PATH_DIRTY_LISTED : 0u) |
+          (in_lds ? 0u : TFBS_PATH_COR_ARENA);
     if (tid == 0) {
         s_arena = kFNone;
         if (!in_lds) {
@@ -925,6 +945,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     bool h16 = half;
     if ((T + rows_per - 1) / rows_per > 32 || A.cor_lds == 0) {  // (cor_lds 0: the tests' all-global path)
         h16 = false;
+        pw |= TFBS_PATH_CNT_ARENA;
         rows_per = min(T, kFRows);
         if (tid == 0) {
             s_arena = kFNone;
@@ -935,6 +956,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         if (s_arena == kFNone) return give_up(5);  // the host grows the arena for the next call
         cnt = A.cor_arena + s_arena;
     }
+    pw |= (h16 ? 0u : TFBS_PATH_U32) | (U > kFHapLds ? TFBS_PATH_HAP_GLOBAL : 0u);
     // untouched keys: no match -- no key in the reference's HashMap
     for (uint32_t j = tid; j < K; j += kFBlock)
         if (!((s_bits[j >> 5] >> (j & 31)) & 1u)) {
@@ -1041,6 +1063,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     stamp(13, (T + rows_per - 1) / rows_per);
     stamp(14, blockIdx.x | (which << 24));  // (the workgroup: its timeline in the report)
     stamp(15, nref);
+    trace(pw);
     };
     // regions [first, first + count) in A.order's order (most haplotypes first): with
     // A.persist a grid of a few workgroups per CU takes them -- its first region by
@@ -1054,7 +1077,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     while (i < count) {
         uint32_t tk = 0;
         if (tickets && tid == 0) tk = gridDim.x + atomicAdd(A.next + which, 1u);
-        process(A.order ? A.order[first + i] : first + i);
+        process(A.order ? A.order[first + i] : first + i, i == blockIdx.x ? 0u : (uint32_t)TFBS_PATH_TICKET);
         if (!tickets) break;
         if (tid == 0) s_tk = tk;
         __syncthreads();
@@ -1496,7 +1519,10 @@ int launch_key_fast(const AsmArgs &a, uint32_t n_regions, uint32_t n_big, hipStr
     });
     const Fit &fit = fits[dev];
     const int n_cu = fit.n_cu, per_small = fit.per_small, per_big = fit.per_big;
-    auto grid = [&](uint32_t n, int per) { return a.persist ? std::min<uint32_t>(n, (uint32_t)(n_cu * per)) : n; };
+    auto grid = [&](uint32_t n, int per) {  // (a.grid_cap: TFBS_KF_GRID, so that a few regions take tickets)
+        const uint32_t fit_wg = (uint32_t)(n_cu * per);
+        return a.persist ? std::min<uint32_t>(n, a.grid_cap ? std::min(a.grid_cap, fit_wg) : fit_wg) : n;
+    };
     hipError_t e = hipSuccess;
     // two shapes at once: the regions of many haplotypes (order[0, n_big), whole-CU
     // workgroups) go first on `stream` -- queued ahead, they take their CUs before the

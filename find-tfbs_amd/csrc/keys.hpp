@@ -72,6 +72,11 @@ struct AsmArgs {
     uint32_t persist;
     uint32_t *next;
     uint64_t *prof;  // debug (TFBS_KF_PROF): key_fast_kernel's phase clocks and sizes, 16 per region, or null
+    // tfbs_ctx_assembly_trace: one word per region (TFBS_PATH_* of tfbs_amd.h), written once by
+    // thread 0 of the workgroup that takes the region (key_asm_kernel's list pass adds its
+    // bits to key_fast_kernel's), or null
+    uint32_t *path;
+    uint32_t grid_cap;  // TFBS_KF_GRID: at most this many persistent workgroups per shape (0: what fits)
 };
 
 // key_asm_kernel over every region (mode 0 or 1).

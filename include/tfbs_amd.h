@@ -333,6 +333,106 @@ int tfbs_batch_assemble_wait(tfbs_ctx *ctx, tfbs_batch *b);
 int tfbs_step(tfbs_ctx *ctx, tfbs_batch *b);
 /* Device time (ms, HIP events on the ctx stream) of the last assembly, -1 if none ran. */
 float tfbs_ctx_last_assemble_ms(const tfbs_ctx *ctx);
+/* The assembly's path report (read-only; the tests' proof that a case took the branch it
+ * was built for).  tfbs_ctx_assembly_trace(ctx, 1): every assembly enqueued from now on
+ * writes one word per region -- thread 0 of the workgroup that takes the region, one plain
+ * store -- and tfbs_step runs its launches plainly (no graph).  Off (the default) the
+ * kernels get a null pointer and the step is unchanged.
+ * tfbs_batch_assembly_paths: the words of the last checked assembly of b (after
+ * tfbs_batch_reduce / tfbs_batch_assemble_wait / tfbs_step), n = the batch's regions, in
+ * region order; zeros for a region no kernel took; an error if that assembly was enqueued
+ * before the trace was turned on.  A rerun overwrites a region's word; a
+ * region key_fast_kernel gave up keeps its word (the bits decided before the give-up and
+ * the reason) and gains key_asm_kernel's TFBS_PATH_ASM* bits.
+ *   key_fast_kernel (branches listed in key_kernels.hip; a bit below the point of a give-up
+ *   is left clear):
+ *   FAST          key_fast_kernel took the region
+ *   BIG           the 1 024-thread shape (regions of more than TFBS_KF_BIGU haplotypes), else the small one
+ *   WALK          dirty reference hits by the sorted walk (U x nref > 65 536), else pairwise
+ *   STEPBITS      wave 0 kept a bit per pairwise step and reserved its slots once
+ *   DIRTY_LISTED  the dirty corrections were listed in the first pass (pairwise, nD <= the shape's list)
+ *   COR_ARENA     the corrections went to the launch arena, else LDS
+ *   LISTS_SLICED  the hit lists were taken a slice at a time (more lists than the shape stages)
+ *   RUNS_L2       the diff runs were read from global memory, else LDS
+ *   HAP_GLOBAL    more haplotypes than descriptors in LDS: the others were read again
+ *   U32           u32 counters, else packed u16
+ *   CNT_ARENA     counter chunks in the arena (more than 32 LDS chunks), else LDS
+ *   TICKET        a persistent workgroup took the region with a ticket (not its first)
+ *   GIVEUP        key_fast_kernel left the region to key_asm_kernel; TFBS_PATH_WHY(word) is the
+ *                 reason: 0 shape (haplotypes, keys, inner ranges), 2 diff runs (no input, see
+ *                 below), 3 reference hits, 4 arena full (corrections), 5 arena full (counters)
+ *   key_asm_kernel (the reduction's list pass):
+ *   ASM           key_asm_kernel took the region
+ *   ASM_HAPS      more haplotypes than its LDS descriptors (1 024)
+ *   ASM_RUNS      more diff runs than it stages (2 048)
+ *   ASM_HITS      more own hits than it stages (2 048): re-read per pass
+ *   ASM_REFS      more reference hits than it stages (256): re-read
+ *   ASM_SCRATCH   counters in the batch's scratch (more than 6 144 haplotypes)
+ * The limits behind the bits, small | big shape (U distinct haplotypes, nref reference hits,
+ * nD dirty (haplotype, reference hit, range < 32) triples, T touched keys): 256 | 1 024
+ * threads; descriptors of 512 | 2 048 haplotypes in LDS; 1 536 | 12 288 staged runs (the span
+ * of the region's run lists); 128 | 256 hit lists staged at once (8 per haplotype group and
+ * super tile); pairwise while U x nref <= 65 536; a wave's lanes are 64 / rpl haplotypes x rpl
+ * hits (rpl: nref rounded up to a power of two, 64 at most), its steps ceil(U / (waves x 64 /
+ * rpl)) x ceil(nref / rpl): step bits up to 64 steps; dirty corrections listed in the first pass
+ * while pairwise and nD <= 3 584 | 8 192; corrections in LDS while listed own hits + the
+ * region's spill records (the reference hits past its list of 64 among them) + nD <= min(3 584 |
+ * 8 192, TFBS_KEY_COR_LDS), else a share of the arena of TFBS_KEY_COR_CAP words (full: give-up
+ * 4); packed u16 counters while 4 x (longest haplotype + 64) < 65 536 and TFBS_KEY_COR_LDS != 0;
+ * rows per chunk min(3 072 | 24 576 x (2 if packed) / U, 256 | 1 024); more than 32 chunks, or
+ * TFBS_KEY_COR_LDS = 0: u32 counters of min(T, 256 | 1 024) rows in the arena (full: give-up
+ * 5).  Give-up 0: U > min(2 048, TFBS_KEY_FAST_MAXU), more than 16 384 keys or 32 inner ranges;
+ * 3: nref > 256.  Give-up 2 (65 536 or more staged runs) has no input: at most 2 048 haplotypes
+ * of at most 16 runs in their own and 16 in the reference's columns, and the span starts at the
+ * first haplotype's reference-column list, behind its own: at most 2 048 x 32 - 16 = 65 520. */
+enum {
+    TFBS_PATH_FAST = 1u << 0,
+    TFBS_PATH_BIG = 1u << 1,
+    TFBS_PATH_WALK = 1u << 2,
+    TFBS_PATH_STEPBITS = 1u << 3,
+    TFBS_PATH_DIRTY_LISTED = 1u << 4,
+    TFBS_PATH_COR_ARENA = 1u << 5,
+    TFBS_PATH_LISTS_SLICED = 1u << 6,
+    TFBS_PATH_RUNS_L2 = 1u << 7,
+    TFBS_PATH_HAP_GLOBAL = 1u << 8,
+    TFBS_PATH_U32 = 1u << 9,
+    TFBS_PATH_CNT_ARENA = 1u << 10,
+    TFBS_PATH_TICKET = 1u << 11,
+    TFBS_PATH_GIVEUP = 1u << 12,
+    TFBS_PATH_WHY_SHIFT = 13, /* 3 bits */
+    TFBS_PATH_ASM = 1u << 16,
+    TFBS_PATH_ASM_HAPS = 1u << 17,
+    TFBS_PATH_ASM_RUNS = 1u << 18,
+    TFBS_PATH_ASM_HITS = 1u << 19,
+    TFBS_PATH_ASM_REFS = 1u << 20,
+    TFBS_PATH_ASM_SCRATCH = 1u << 21
+};
+#define TFBS_PATH_WHY(word) (((word) >> TFBS_PATH_WHY_SHIFT) & 7u)
+int tfbs_ctx_assembly_trace(tfbs_ctx *ctx, int on);
+int tfbs_batch_assembly_paths(tfbs_ctx *ctx, const tfbs_batch *b, uint32_t *mask, uint32_t n);
+/* The figures of the last checked assembly (any ctx, trace on or off): out[0] regions left to
+ * key_asm_kernel, out[1] arena words asked for, out[2] spill records, out[3] / out[4] 1 if it
+ * launched the wide spill bucketing kernels / the leftover pass (a lean assembly leaves out
+ * what the batch's last one did not need, TFBS_ASM_LEAN), and since the ctx was made: out[5]
+ * lean assemblies run again in full, out[6] those of them that needed the wide kernels (more
+ * than 8 192 spill records; the device flag a lean post_scan_kernel sets, cleared by the rerun),
+ * out[7] those that needed the leftover pass. */
+int tfbs_ctx_assembly_figures(tfbs_ctx *ctx, uint64_t out[8]);
+/* What the key assembly branches on, from the host batch (no device; the tests' proofs).
+ * tfbs_batch_region_layout: out[0] the region's first distinct haplotype in the batch (the
+ * scan groups haplotypes TFBS_MFMA_HAPS_PER_BLOCK at a time from 0), out[1] its distinct
+ * haplotypes, out[2] the batch index of its reference haplotype (out[0] + out[1]: a helper
+ * copy; UINT32_MAX: no haplotype reuses the reference's hits, none are listed), out[3] its
+ * distinct inner ranges.
+ * tfbs_batch_region_hap_runs: distinct haplotype h of the region -- *reuses 1 if it inherits
+ * the reference's hits outside its dirty windows; its diff runs in the reference's columns
+ * (window w of a strand of length L is dirty iff some run [a, b] has a <= w + L - 1 and
+ * b >= w; b = UINT32_MAX: to the end; [a, a - 1]: two touching segments): *n_runs of them at
+ * *run_off of the batch's run array (key_fast_kernel stages the span from the region's lowest
+ * offset to its highest end), the first cap as (a, b) pairs in ab. */
+int tfbs_batch_region_layout(const tfbs_batch *b, size_t region, uint32_t out[4]);
+int tfbs_batch_region_hap_runs(const tfbs_batch *b, size_t region, uint32_t h, int *reuses, uint32_t *run_off,
+                               uint32_t *n_runs, uint32_t *ab, uint32_t cap);
 /* counts_as_genotypes' per-sample half on the device (main.rs:439-534, SURVEY.md
  * 8(f) f1) for the varying keys of regions [r0, r1) after tfbs_batch_reduce:
  * per key v[s] = C[hap(2s)] + C[hap(2s+1)] over the samples, min / max, the
