@@ -19,6 +19,7 @@ argument meaning, error behaviour) over the C ABI of include/tfbs_amd.h:
 The reference panics where TfbsError is raised.  The scan always runs on a HIP
 device; without one, Scanner() raises TfbsError(TFBS_E_NODEVICE).
 """
+import contextlib
 import ctypes as C
 from collections import namedtuple
 
@@ -396,6 +397,56 @@ def matches(pattern, haplotype, haplotype_ids=(), verbose=False):
         sc.close()
 
 
+GROUPER_HOST = -2  # TFBS_GROUPER_HOST: the host grouper (Grouper, RegionBatch(build_device=...))
+GroupedRegion = namedtuple("GroupedRegion", "n_groups masks counts row")  # n_groups None: overflow
+
+
+class Grouper:
+    """tfbs_grouper_*: the haplotype grouper of RegionBatch(build_device=...) driven alone."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        check(lib().tfbs_grouper_create(device, C.byref(self.h)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().tfbs_grouper_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def group(self, H, regions):
+        """One launch.  regions: per region its records, each the ascending haplotype ids
+        (< H) carrying it; a record's rank is its index.  -> one GroupedRegion per region:
+        the distinct masks in the grouper's order, their carrier counts and the membership
+        row (H entries)."""
+        n_rec = [len(r) for r in regions]
+        n_car = [len(c) for r in regions for c in r]
+        ids = [h for r in regions for c in r for h in c]
+        nr = len(regions)
+        cap = 2047 * nr
+        ng = (C.c_uint32 * max(1, nr))()
+        masks = (C.c_uint64 * max(1, cap))()
+        counts = (C.c_uint32 * max(1, cap))()
+        rows = (C.c_uint16 * max(1, nr * H))()
+        n = C.c_size_t()
+        check(lib().tfbs_grouper_group(self.h, H, nr, (C.c_uint32 * max(1, nr))(*n_rec),
+                                       (C.c_uint32 * max(1, len(n_car)))(*n_car),
+                                       (C.c_uint32 * max(1, len(ids)))(*ids), ng, masks, counts, cap, C.byref(n),
+                                       rows))
+        out, at = [], 0
+        for j in range(nr):
+            row = list(rows[j * H:(j + 1) * H])
+            if ng[j] == 0xFFFFFFFF:
+                out.append(GroupedRegion(None, [], [], row))
+                continue
+            out.append(GroupedRegion(ng[j], list(masks[at:at + ng[j]]), list(counts[at:at + ng[j]]), row))
+            at += ng[j]
+        assert at == n.value
+        return out
+
+
 class RegionBatch:
     """load_haplotypes + find_all_matches + count_matches_by_sample over many merged regions."""
 
@@ -424,6 +475,12 @@ class RegionBatch:
         d, h = C.c_uint64(), C.c_uint64()
         check(lib().tfbs_batch_build_stats(self.h, C.byref(d), C.byref(h)))
         return d.value, h.value
+
+    def group_calls(self):
+        """Chunks of regions handed to the grouper so far (one launch each)."""
+        n = C.c_uint64()
+        check(lib().tfbs_batch_group_calls(self.h, C.byref(n)))
+        return n.value
 
     def patch_stats(self):
         """Regions grouped on the device whose distinct groups the host patched."""
@@ -464,6 +521,17 @@ class RegionBatch:
 
     def end(self):
         check(lib().tfbs_batch_region_end(self.h))
+
+    @contextlib.contextmanager
+    def hold(self):
+        """tfbs_batch_hold: the regions ended inside the block are built together when it
+        ends (several host threads, one grouper launch per chunk); until then they are
+        not part of the batch."""
+        check(lib().tfbs_batch_hold(self.h, 1))
+        try:
+            yield self
+        finally:
+            check(lib().tfbs_batch_hold(self.h, 0))
 
     def synth_fill(self, seed, first, count, indel_pct=0):
         check(lib().tfbs_synth_fill_batch(self.h, seed, first, count, indel_pct))

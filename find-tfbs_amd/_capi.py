@@ -115,7 +115,13 @@ SIGNATURES = [
     ("tfbs_batch_add_bed", C.c_int, [vp, C.c_char_p]),
     ("tfbs_batch_set_window_lmax", C.c_int, [vp, C.c_uint32]),
     ("tfbs_batch_set_build_device", C.c_int, [vp, C.c_int]),
+    ("tfbs_batch_hold", C.c_int, [vp, C.c_int]),
+    ("tfbs_batch_group_calls", C.c_int, [vp, u64p]),
     ("tfbs_batch_build_stats", C.c_int, [vp, u64p, u64p]),
+    ("tfbs_grouper_create", C.c_int, [C.c_int, C.POINTER(vp)]),
+    ("tfbs_grouper_destroy", None, [vp]),
+    ("tfbs_grouper_group", C.c_int, [vp, C.c_uint32, C.c_size_t, u32p, u32p, u32p, u32p, u64p, u32p, C.c_size_t,
+                                     C.POINTER(C.c_size_t), u16p]),
     ("tfbs_batch_patch_stats", C.c_int, [vp, u64p]),
     ("tfbs_batch_region_ext", C.c_int, [vp, C.c_uint64, C.c_uint64, u64p, u64p]),
     ("tfbs_batch_region_begin", C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_char_p, C.c_size_t]),

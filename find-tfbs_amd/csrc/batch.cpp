@@ -728,7 +728,10 @@ int build_regions(Batch &B, std::vector<RegionInput> &ins, uint32_t threads, std
             if (where[j] == 1 || where[j] == 3) dj.push_back(j);
         const uint32_t H = 2 * B.n_samples;
         // chunks: the masks scratch (8 bytes per haplotype id and region) within 1 GiB
-        const size_t max_regions = std::max<size_t>(1, std::min<size_t>(1024, (1ull << 30) / (8ull * H)));
+        size_t max_regions = std::max<size_t>(1, std::min<size_t>(1024, (1ull << 30) / (8ull * H)));
+        // TFBS_GROUP_REGIONS (1..1024, read at each call): fewer regions per chunk
+        if (const char *e = getenv("TFBS_GROUP_REGIONS"); e && *e)
+            max_regions = std::min<size_t>(max_regions, (size_t)std::max(1, std::min(1024, atoi(e))));
         for (size_t c0 = 0; c0 < dj.size();) {
             size_t c1 = c0;
             uint64_t ncar = 0;
@@ -764,6 +767,7 @@ int build_regions(Batch &B, std::vector<RegionInput> &ins, uint32_t threads, std
             });
             lap(1);
             GroupOut go;
+            B.group_calls++;
             if (int rc = B.grouper->group(ncar, recs, regs, H, go)) return rc;
             lap(2);
             if (go.memb_alloc) B.memb_allocs.push_back(go.memb_alloc);
@@ -1309,8 +1313,12 @@ int tfbs_batch_region_variant(const tfbs_batch *b, size_t region, size_t v, uint
 int tfbs_batch_set_build_device(tfbs_batch *b, int device) {
     if (!b) return tfbs::fail(TFBS_E_ARG, "null argument");
     Batch &B = b->b;
-    if (!B.rh.empty() || B.open) return tfbs::fail(TFBS_E_STATE, "regions already added");
+    if (!B.rh.empty() || B.open || !B.held.empty()) return tfbs::fail(TFBS_E_STATE, "regions already added");
     B.grouper.reset();
+    if (device == TFBS_GROUPER_HOST) {
+        B.grouper.reset(tfbs::make_host_grouper());
+        return TFBS_OK;
+    }
     if (device < 0) return TFBS_OK;
     tfbs::DevGrouper *g = tfbs::make_gpu_grouper(device);
     if (!g) return TFBS_E_NODEVICE;
@@ -1318,10 +1326,42 @@ int tfbs_batch_set_build_device(tfbs_batch *b, int device) {
     return TFBS_OK;
 }
 
+int tfbs_batch_hold(tfbs_batch *b, int on) {
+    if (!b) return tfbs::fail(TFBS_E_ARG, "null argument");
+    Batch &B = b->b;
+    if (B.open) return tfbs::fail(TFBS_E_STATE, "region open");
+    if (on) {
+        B.hold = true;
+        return TFBS_OK;
+    }
+    B.hold = false;
+    if (B.held.empty()) return TFBS_OK;
+    std::vector<tfbs::RegionInput> ins;
+    ins.swap(B.held);
+    const char *env = getenv("TFBS_HOST_THREADS");  // (as tfbs_synth_fill_batch)
+    uint32_t T = env && *env ? (uint32_t)atoi(env) : std::thread::hardware_concurrency();
+    T = std::max(1u, std::min(16u, T));
+    // a failing region: none of the held regions is committed, and none is counted
+    const uint64_t nd = B.dev_regions, nh = B.host_regions, np = B.patched_regions;
+    const int rc = tfbs::add_regions(B, ins, T);
+    if (rc) {
+        B.dev_regions = nd;
+        B.host_regions = nh;
+        B.patched_regions = np;
+    }
+    return rc;
+}
+
 int tfbs_batch_build_stats(const tfbs_batch *b, uint64_t *dev_regions, uint64_t *host_regions) {
     if (!b) return tfbs::fail(TFBS_E_ARG, "null argument");
     if (dev_regions) *dev_regions = b->b.dev_regions;
     if (host_regions) *host_regions = b->b.host_regions;
+    return TFBS_OK;
+}
+
+int tfbs_batch_group_calls(const tfbs_batch *b, uint64_t *calls) {
+    if (!b || !calls) return tfbs::fail(TFBS_E_ARG, "null argument");
+    *calls = b->b.group_calls;
     return TFBS_OK;
 }
 
@@ -1500,7 +1540,7 @@ int tfbs_batch_region_end(tfbs_batch *b) {
     Batch &B = b->b;
     B.open = false;
     if (B.status) return B.status;
-    B.counts_valid = B.reduced = false;
+    if (!B.hold) B.counts_valid = B.reduced = false;
     tfbs::RegionInput in;
     in.R = std::move(B.cur);
     in.ref = std::move(B.cur_ref);
@@ -1508,6 +1548,10 @@ int tfbs_batch_region_end(tfbs_batch *b) {
     in.inner = std::move(B.cur_inner);
     B.cur_rec.clear();
     B.cur_inner.clear();
+    if (B.hold) {  // built at the release (tfbs_batch_hold)
+        B.held.push_back(std::move(in));
+        return TFBS_OK;
+    }
     std::vector<tfbs::RegionInput> ins(1);
     ins[0] = std::move(in);
     return tfbs::add_regions(B, ins, 1);

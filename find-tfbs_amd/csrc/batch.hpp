@@ -134,9 +134,17 @@ struct DevGrouper {
     virtual void recycle(std::vector<void *> &allocs) = 0;
 };
 DevGrouper *make_gpu_grouper(int device);  // build_gpu.hip
+DevGrouper *make_host_grouper();           // group_host.cpp: the same grouping in host memory, device() == -1
 // The HIP runtime and these devices' contexts initialised (0.1-0.4 s in a fresh process):
 // tfbs_run starts it on a thread before it parses its inputs.  build_gpu.hip
 void warm_devices(const std::vector<int> &devices);
+
+struct RegionInput {  // one merged region as the reader hands it over
+    RegionH R;                        // ms, me, es, ee set
+    std::vector<uint8_t> ref;         // nucleotide codes from es
+    std::vector<Record> recs;         // records in BCF order
+    std::vector<std::pair<uint32_t, std::pair<uint64_t, uint64_t>>> inner;  // (bed, (s, e))
+};
 
 struct Batch {
     const Patterns *pats = nullptr;
@@ -223,6 +231,10 @@ struct Batch {
     std::vector<Record> cur_rec;
     std::vector<std::pair<uint32_t, std::pair<uint64_t, uint64_t>>> cur_inner;
     int status = TFBS_OK;
+    // tfbs_batch_hold: regions ended while held wait here, outside the batch, until the
+    // release builds them with one add_regions call
+    bool hold = false;
+    std::vector<RegionInput> held;
 
     // L_max of the halo-extended window (main.rs:404-407): the pattern set's
     // longest strand unless set wider (tfbs_batch_set_window_lmax: a shard of
@@ -241,18 +253,12 @@ struct Batch {
     }
     uint64_t dev_regions = 0, host_regions = 0;  // regions grouped on the device / built on the host
     uint64_t patched_regions = 0;                // of dev_regions: distinct groups patched on the host
+    uint64_t group_calls = 0;                    // chunks handed to the grouper (written by build_regions)
 
     uint64_t device_bytes() const;
 };
 
 enum KeyFlags : uint8_t { KEY_ANY = 1, KEY_VARIES = 2 };
-
-struct RegionInput {  // one merged region as the reader hands it over
-    RegionH R;                        // ms, me, es, ee set
-    std::vector<uint8_t> ref;         // nucleotide codes from es
-    std::vector<Record> recs;         // records in BCF order
-    std::vector<std::pair<uint32_t, std::pair<uint64_t, uint64_t>>> inner;  // (bed, (s, e))
-};
 
 // A haplotype's positions (haplotype.rs's pos vector) as maximal runs of consecutive
 // positions: run k covers bases [r[k].at, r[k + 1].at) (the last to n) at positions

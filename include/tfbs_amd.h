@@ -239,13 +239,57 @@ int tfbs_batch_set_window_lmax(tfbs_batch *b, uint32_t lmax);
  * the O(haplotypes x records) part) and the host patches only its distinct groups
  * (TFBS_DEV_PATCH=0: built on the host).  Every other region, and one of more than
  * 2 047 distinct diff masks, is built on the host.  The batch is the same either
- * way (tfbs_batch_region_input_digest). */
+ * way (tfbs_batch_region_input_digest).
+ *
+ * device == TFBS_GROUPER_HOST: the same grouping in plain C++ on the host (the device
+ * path of the build -- qualification, chunks, the finish of every group, membership
+ * rows fetched where a device would read them in place -- without a device; for tests
+ * and for comparing the two).  TFBS_GROUP_REGIONS (1..1024, read at every build) caps
+ * the regions grouped by one launch; unset: 1024, or what 1 GiB of masks holds. */
+#define TFBS_GROUPER_HOST (-2)
 int tfbs_batch_set_build_device(tfbs_batch *b, int device);
+/* on != 0: regions ended from now on are queued, not built; until the release they are
+ * not part of the batch (tfbs_batch_num_regions and every reader see the batch without
+ * them).  on == 0 releases: the queued regions are built by one call on the host's
+ * threads (TFBS_HOST_THREADS, at most 16) and appended in the order they were ended --
+ * with a build device one grouper launch per chunk of regions instead of one per
+ * region.  A region that fails to build fails the release with its error; then none
+ * of the queued regions is added and all are dropped.  tfbs_batch_destroy drops queued
+ * regions unbuilt.  TFBS_E_STATE while a region is open. */
+int tfbs_batch_hold(tfbs_batch *b, int on);
 /* Regions grouped on the device / built on the host so far. */
 int tfbs_batch_build_stats(const tfbs_batch *b, uint64_t *dev_regions, uint64_t *host_regions);
+/* Chunks of regions handed to the grouper so far, one launch each. */
+int tfbs_batch_group_calls(const tfbs_batch *b, uint64_t *calls);
 /* Of the regions grouped on the device, those whose distinct groups the host
  * patched (indels / N). */
 int tfbs_batch_patch_stats(const tfbs_batch *b, uint64_t *patched_regions);
+
+/* The grouper of tfbs_batch_set_build_device driven alone: raw carrier lists in, what
+ * the grouper produced out.  device >= 0: the HIP grouper of that device;
+ * TFBS_GROUPER_HOST: the host grouper.  Calls on one handle reuse its scratch and its
+ * membership rows, as the batches of a run do.
+ *
+ * One call is one launch over n_regions regions of H haplotype ids.  Region j has
+ * n_records[j] records (a record's rank is its index in its region); n_carriers holds
+ * every record's carrier count, regions back to back, and ids every record's carrier
+ * ids, back to back in the same order.  Per region: n_groups[j] = its distinct
+ * non-empty masks (UINT32_MAX: more than 2 047, the region a batch builds on the
+ * host); its masks and their carrier counts in the grouper's order, regions back to
+ * back in masks / counts (cap entries each; *n_masks = the entries, TFBS_E_ARG when
+ * cap is short); rows + j * H = its membership row as the grouper's fetch hands it
+ * out (a mask's index per id, n_groups[j] for an id without one; 0xFFFF throughout for
+ * an overflowing region, whose row the grouper leaves unwritten).
+ *
+ * Refused with TFBS_E_ARG before anything is launched: H == 0, more than 64 records in
+ * a region, a record without a carrier, an id >= H, ids not strictly ascending, more
+ * than 1 024 regions or n_regions * H > 2^27 (a batch's chunk rule). */
+typedef struct tfbs_grouper tfbs_grouper;
+int tfbs_grouper_create(int device, tfbs_grouper **out);
+void tfbs_grouper_destroy(tfbs_grouper *g);
+int tfbs_grouper_group(tfbs_grouper *g, uint32_t H, size_t n_regions, const uint32_t *n_records,
+                       const uint32_t *n_carriers, const uint32_t *ids, uint32_t *n_groups, uint64_t *masks,
+                       uint32_t *counts, size_t cap, size_t *n_masks, uint16_t *rows);
 /* main.rs:404-407: the halo-extended window of a merged region. */
 int tfbs_batch_region_ext(const tfbs_batch *b, uint64_t merged_start, uint64_t merged_end, uint64_t *ext_start,
                           uint64_t *ext_end);
