@@ -193,6 +193,22 @@ class PatternSet:
         check(lib().tfbs_patterns_mfma_bound(self.h, i, codes, C.byref(out)))
         return {n: getattr(out, n) for n, _ in out._fields_}
 
+    def mfma_plan(self, lds_kb=0):
+        """The matrix-core plan a Scanner uploads with TFBS_MFMA_LDS_KB=lds_kb (0: the default),
+        copied and not interpreted (tfbs_patterns_mfma_plan, a diagnostic): dict(image = the
+        super tiles' FP6 digit fragments as bytes, supers = [dict of tfbs_mfma_super's fields],
+        meta = the tiles' rescoring fields, 384 ints per tile)."""
+        nb, ns, nm = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        check(lib().tfbs_patterns_mfma_plan(self.h, lds_kb, None, 0, C.byref(nb), None, 0, C.byref(ns), None, 0,
+                                            C.byref(nm)))
+        img = (C.c_uint8 * max(1, nb.value))()
+        sup = (_capi.tfbs_mfma_super * max(1, ns.value))()
+        meta = (C.c_int32 * max(1, nm.value))()
+        check(lib().tfbs_patterns_mfma_plan(self.h, lds_kb, img, nb.value, C.byref(nb), sup, ns.value, C.byref(ns),
+                                            meta, nm.value, C.byref(nm)))
+        return {"image": bytes(img)[:nb.value], "meta": list(meta[:nm.value]),
+                "supers": [{n: getattr(sup[k], n) for n, _ in sup[k]._fields_} for k in range(ns.value)]}
+
     def subset(self, keep_pattern_id):
         """A new PatternSet of the patterns whose pattern_id passes keep_pattern_id (both
         strands of a PWM share an id, so they stay together): a pattern shard of SURVEY.md

@@ -43,6 +43,11 @@ class tfbs_mfma_bound(C.Structure):
                 ("c", C.c_int64)]
 
 
+class tfbs_mfma_super(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("tile_count", "nk", "img_off", "img_bytes", "seg")] + \
+        [("t0", C.c_int32)] + [(n, C.c_uint32) for n in ("acc0", "lmin", "lmax", "tile0")]
+
+
 class tfbs_run_args(C.Structure):
     _fields_ = [
         ("chromosome", C.c_char_p), ("bcf", C.c_char_p), ("bed_files", C.c_char_p), ("reference", C.c_char_p),
@@ -95,6 +100,9 @@ SIGNATURES = [
     ("tfbs_patterns_dinuc_stats", C.c_int, [vp, u32p, u32p, u64p]),
     ("tfbs_patterns_dinuc_lut_scores", C.c_int, [vp, C.c_size_t, u8p, C.c_size_t, i32p]),
     ("tfbs_patterns_mfma_bound", C.c_int, [vp, C.c_size_t, C.POINTER(C.c_uint8), C.POINTER(tfbs_mfma_bound)]),
+    ("tfbs_patterns_mfma_plan", C.c_int, [vp, C.c_uint32, u8p, C.c_size_t, C.POINTER(C.c_size_t),
+                                          C.POINTER(tfbs_mfma_super), C.c_size_t, C.POINTER(C.c_size_t), i32p,
+                                          C.c_size_t, C.POINTER(C.c_size_t)]),
     ("tfbs_parse_weight", C.c_int, [C.c_char_p, i32p]),
     ("tfbs_parse_threshold_file", C.c_int, [C.c_char_p, C.c_float, i32p]),
     ("tfbs_device_count", C.c_int, [C.POINTER(C.c_int)]),

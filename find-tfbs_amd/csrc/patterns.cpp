@@ -607,6 +607,32 @@ int tfbs_patterns_mfma_bound(const tfbs_patterns *p, size_t i, const uint8_t *ba
     return TFBS_OK;
 }
 
+int tfbs_patterns_mfma_plan(const tfbs_patterns *p, uint32_t lds_kb, uint8_t *image, size_t image_cap,
+                            size_t *image_bytes, tfbs_mfma_super *supers, size_t supers_cap, size_t *n_supers,
+                            int32_t *meta, size_t meta_cap, size_t *meta_ints) {
+    if (!p || !image_bytes || !n_supers || !meta_ints) return tfbs::fail(TFBS_E_ARG, "null argument");
+    tfbs::Plan plan;
+    tfbs::PlanOptions opt;  // as tfbs_ctx_create sets them (TFBS_MFMA=1, TFBS_MFMA_LDS_KB=lds_kb)
+    opt.mfma = true;
+    opt.mfma_lds_bytes = std::min<uint32_t>(144, std::max<uint32_t>(8, lds_kb ? lds_kb : 44)) * 1024u;
+    int rc = p->p.build_plan(opt, &plan);
+    if (rc) return rc;
+    *image_bytes = plan.m_image.size() * 4;
+    *n_supers = plan.m_supers.size();
+    *meta_ints = plan.m_meta.size();
+    if ((image && image_cap < *image_bytes) || (supers && supers_cap < *n_supers) || (meta && meta_cap < *meta_ints))
+        return tfbs::fail(TFBS_E_ARG, "output capacity too small");
+    if (image && *image_bytes) std::memcpy(image, plan.m_image.data(), *image_bytes);
+    if (meta && *meta_ints) std::memcpy(meta, plan.m_meta.data(), *meta_ints * 4);
+    if (supers)
+        for (size_t k = 0; k < plan.m_supers.size(); k++) {
+            const tfbs::DevMSuper &S = plan.m_supers[k];
+            supers[k] = tfbs_mfma_super{S.tile_count, S.nk, S.img_off, S.img_bytes, S.seg, S.t0, S.acc0, S.lmin,
+                                        S.lmax, S.tile0};
+        }
+    return TFBS_OK;
+}
+
 }  // extern "C"
 
 namespace tfbs {

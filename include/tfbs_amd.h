@@ -154,6 +154,28 @@ typedef struct tfbs_mfma_bound {
     int64_t q8, t8, scale, c;
 } tfbs_mfma_bound;
 int tfbs_patterns_mfma_bound(const tfbs_patterns *p, size_t i, const uint8_t *bases, tfbs_mfma_bound *out);
+/* Host-only, read-only diagnostic of the matrix-core plan: copies of the arrays a
+ * device context uploads for the matrix-core scan and nothing derived from them.  The
+ * plan is built once per call exactly as tfbs_ctx_create builds it with TFBS_MFMA=1,
+ * TFBS_MFMA_LDS_KB=lds_kb (0: the default, 44; clamped to 8..144 as there) and
+ * TFBS_MFMA_LDS_BY_DEPTH unset.  image: the FP6 digit fragments of every super tile
+ * (lane layout: mfma.cpp, scan_mfma.hip); supers: per super tile its tile count, depth
+ * class nk (2 or 4), the byte offset and size of its image, the depth segment ends
+ * (byte d - 1: the first tile deeper than d), the common candidate threshold t0, the
+ * accumulator's start value acc0 (f32 bits), its shortest and longest strand and the
+ * global index of its first tile; meta: per tile 384 ints, strand sn's min_score,
+ * weight offset, length and slot at 4 sn .. 4 sn + 3, its pattern index at 256 + sn
+ * (-1: a padding strand), the tile's depth class at 320.  *image_bytes, *n_supers and
+ * *meta_ints always receive the sizes; each array may be NULL (sizes only) and is
+ * TFBS_E_ARG if its capacity (bytes, entries, ints) is too small. */
+typedef struct tfbs_mfma_super {
+    uint32_t tile_count, nk, img_off, img_bytes, seg;
+    int32_t t0;
+    uint32_t acc0, lmin, lmax, tile0;
+} tfbs_mfma_super;
+int tfbs_patterns_mfma_plan(const tfbs_patterns *p, uint32_t lds_kb, uint8_t *image, size_t image_cap,
+                            size_t *image_bytes, tfbs_mfma_super *supers, size_t supers_cap, size_t *n_supers,
+                            int32_t *meta, size_t meta_cap, size_t *meta_ints);
 
 /* pattern.rs:13-16 parse_weight: (f32(s) * 1000f32).round() as i32. */
 int tfbs_parse_weight(const char *s, int32_t *out);

@@ -210,7 +210,12 @@ def test_mfma_bound_is_sound():
     (weight spans 1 .. 2^20, mixed / all-negative / all-positive columns, thresholds at,
     below and above real scores) and random windows with N, 8 * score <= 8 c + scale * q8,
     every window with score > min_score (pattern.rs:151) is a candidate (q8 > t8), and the
-    window's 11-bit field q8 + 1023 - t8 neither borrows nor carries."""
+    window's 11-bit field q8 + 1023 - t8 neither borrows nor carries.
+
+    This goes through tfbs_patterns_mfma_bound, which uses the strand's own best T0 from a
+    one-pattern set: it checks a strand's best split, not the image a context uploads (the
+    super tile's common T0, the scale that follows from it, the clipped digits, the padding
+    strands, acc0).  tests/test_filter_cases_cpu.py checks those, from the uploaded bytes."""
     rnd = random.Random(21)
     checked = hits = 0
     for trial in range(160):
