@@ -305,6 +305,21 @@ def counts_as_genotypes(v1, v2, verbose=False):
     return counts, maf.value, f0, f1, f2, gts.value.decode()
 
 
+def scores_as_genotypes(left, right, min_spread=1):
+    """tfbs_scores_as_genotypes (host only): the score rows' definition on one candidate row's
+    per-sample values (the two haplotypes' best scores, int32) -> (maf, info, genotypes), info =
+    "SCORES=<lo>,<hi>;freqs=<zero>/<one>/<two>", or None when there is no row."""
+    n = len(left)
+    maf = C.c_uint32()
+    info = C.create_string_buffer(128)
+    gts = C.create_string_buffer(16 + 11 * n)
+    r = check(lib().tfbs_scores_as_genotypes((C.c_int32 * max(1, n))(*left), (C.c_int32 * max(1, n))(*right), n,
+                                             min_spread, C.byref(maf), info, len(info), gts, len(gts)))
+    if r != 1:
+        return None
+    return maf.value, info.value.decode(), gts.value.decode()
+
+
 # tfbs_batch_assembly_paths' bits (tfbs_amd.h TFBS_PATH_*)
 PATH_BITS = {"FAST": 1 << 0, "BIG": 1 << 1, "WALK": 1 << 2, "STEPBITS": 1 << 3, "DIRTY_LISTED": 1 << 4,
              "COR_ARENA": 1 << 5, "LISTS_SLICED": 1 << 6, "RUNS_L2": 1 << 7, "HAP_GLOBAL": 1 << 8, "U32": 1 << 9,
@@ -395,6 +410,13 @@ class Scanner:
         out = (C.c_double * 2)()
         check(lib().tfbs_ctx_last_best_ms(self.h, out))
         return out[0], out[1]
+
+    def last_scores_ms(self):
+        """tfbs_ctx_last_scores_ms: (best kernel, fold + statistics, text kernel ms from HIP events,
+        copy-back + host ms) of the last score_rows()."""
+        out = (C.c_double * 4)()
+        check(lib().tfbs_ctx_last_scores_ms(self.h, out))
+        return tuple(out)
 
     def last_effects_ms(self):
         """tfbs_ctx_last_effects_ms: (host prep ms, kernel ms from HIP events, copy-back + host ms)
@@ -848,6 +870,27 @@ class RegionBatch:
             lib().tfbs_free(p)
         return out
 
+    def score_rows(self, scanner, chromosome, min_maf=0, min_spread=1, fake_position=1, r0=None, r1=None):
+        """tfbs_batch_score_rows: the score rows of regions [r0, r1) of this batch, resident on the
+        scanner (after an upload; no scan needed; the batch keeps its membership) -> (text, n_rows,
+        next_position).  fake_position None: counted only -> ("", n_rows, None)."""
+        p = C.c_void_p()
+        n = C.c_size_t()
+        rows = C.c_uint64()
+        a, z = 0 if r0 is None else r0, self.num_regions if r1 is None else r1
+        if fake_position is None:
+            check(lib().tfbs_batch_score_rows(scanner.h, self.h, a, z, _u(chromosome), min_maf, min_spread, None, None,
+                                              None, C.byref(rows)))
+            return "", rows.value, None
+        fp = C.c_uint32(fake_position)
+        check(lib().tfbs_batch_score_rows(scanner.h, self.h, a, z, _u(chromosome), min_maf, min_spread, C.byref(fp),
+                                          C.byref(p), C.byref(n), C.byref(rows)))
+        try:
+            text = C.string_at(p, n.value).decode()
+        finally:
+            lib().tfbs_free(p)
+        return text, rows.value, fp.value
+
     def ranges(self, region):
         """The region's distinct non-empty inner ranges [(start, end)] in ascending order: what
         a best record's `range` indexes."""
@@ -1013,7 +1056,7 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
         pwm_threshold, wanted_pwms, output_file, forward_only=False, run_tabix=False, min_maf=0, threads=1,
         after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None,
         hits_output=None, hits_mode="diff", best_output=None, best_mode="diff", effects_output=None,
-        effects_mode="sites"):
+        effects_mode="sites", scores_output=None, scores_min_spread=1):
     """main.rs:234-393 `run` with the reference's argument order; writes the BGZF VCF.
     devices: list of HIP devices; batch g of merged regions runs on devices[g % n] (same
     text for any list; a device may repeat).  hits_output: also write every region's hit
@@ -1021,6 +1064,8 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     or "diff"); best_output: the same for every region's best sites (BEST_HEADER, then
     RegionBatch.best_tsv's lines in best_mode); effects_output: the same for every region's variant
     effects (EFFECTS_HEADER, then RegionBatch.effects_tsv's lines in effects_mode "sites" or "all");
+    scores_output: also write the score rows (RegionBatch.score_rows with min_maf and
+    scores_min_spread, POS from 1) there as a second BGZF VCF under the main output's #CHROM line;
     the main output does not change."""
     a = _capi.tfbs_run_args()
     keep = [_u(x) if x is not None else None for x in (chromosome, bcf, ",".join(bed_files), reference_genome_file,
@@ -1047,8 +1092,11 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     bo = _u(best_output) if best_output is not None else None
     a.best_output = bo
     a.best_mode = BEST_MODES[best_mode]
-    x = _capi.tfbs_run_ext()
-    x.size = C.sizeof(_capi.tfbs_run_ext)
+    x = _capi.tfbs_run_ext_scores()
+    x.size = C.sizeof(_capi.tfbs_run_ext_scores)
+    so = _u(scores_output) if scores_output is not None else None
+    x.scores_output = so
+    x.scores_min_spread = scores_min_spread
     eo = _u(effects_output) if effects_output is not None else None
     x.effects_output = eo
     x.effects_mode = EFFECT_MODES[effects_mode]

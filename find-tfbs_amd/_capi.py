@@ -82,6 +82,12 @@ class tfbs_run_ext(C.Structure):
     _fields_ = [("size", C.c_uint32), ("effects_output", C.c_char_p), ("effects_mode", C.c_int)]
 
 
+class tfbs_run_ext_scores(C.Structure):
+    """tfbs_run_ext as the header has it since the score rows: the fields above, then the new ones
+    at the end (tfbs_run_ex reads `size` bytes, so either layout is a valid argument)."""
+    _fields_ = tfbs_run_ext._fields_ + [("scores_output", C.c_char_p), ("scores_min_spread", C.c_uint64)]
+
+
 # (name, restype, argtypes) for every symbol in include/tfbs_amd.h
 SIGNATURES = [
     ("tfbs_strerror", C.c_char_p, [C.c_int]),
@@ -201,6 +207,11 @@ SIGNATURES = [
     ("tfbs_ctx_last_effects_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
     ("tfbs_batch_effects_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_size_t)]),
+    ("tfbs_scores_as_genotypes", C.c_int, [i32p, i32p, C.c_size_t, C.c_uint64, u32p, C.c_char_p, C.c_size_t,
+                                           C.c_char_p, C.c_size_t]),
+    ("tfbs_batch_score_rows", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint64, u32p,
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), u64p]),
+    ("tfbs_ctx_last_scores_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
     ("tfbs_free", None, [C.c_void_p]),
     ("tfbs_counts_as_genotypes", C.c_int, [u32p, u32p, C.c_size_t, u32p, C.c_char_p, C.c_size_t, C.c_char_p,
                                            C.c_size_t]),

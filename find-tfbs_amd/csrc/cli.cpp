@@ -16,6 +16,7 @@ static void usage() {
             "       [--dipwm_file DIPWM] [--hits_output FILE [--hits_mode all|diff]]\n"
             "       [--best_output FILE [--best_mode all|diff]]\n"
             "       [--effects_output FILE [--effects_mode sites|all]]\n"
+            "       [--scores_output FILE [--scores_min_spread N]]\n"
             "       [--forward_only] [--threads N] [--min_maf N] [--after_position P] [--samples FILE]\n"
             "       [--tabix] [--verbose] [--device D | --devices D1,D2,.. | --gpus N] [--regions_per_batch N]\n"
             "  --devices: one contiguous block of merged regions per listed HIP device (a device may repeat);\n"
@@ -33,7 +34,11 @@ static void usage() {
             "  --effects_output FILE: also write which variant does it, as BGZF TSV: per merged region and record a\n"
             "  `var` line, then per pattern strand the best site touching the record on the REF and on the ALT allele\n"
             "  (range, score) and the score's delta.  --effects_mode sites (default): the `gain`, `loss` and `change`\n"
-            "  lines (a side passes above the strand's threshold); all: `same` and `none` lines too.\n");
+            "  lines (a side passes above the strand's threshold); all: `same` and `none` lines too.\n"
+            "  --scores_output FILE: also write how strongly each sample binds, as a second BGZF VCF: per (bed, inner\n"
+            "  range) and pattern_id one row whose per-sample GT:DS comes from the sum of the sample's two haplotypes'\n"
+            "  best scores (INFO SCORES=<lowest>,<highest>), whatever the threshold; rows whose sums span less than\n"
+            "  --scores_min_spread N (milli-log-odds, default 1) are left out.  --min_maf applies to both files.\n");
 }
 
 int main(int argc, char **argv) {
@@ -92,6 +97,8 @@ int main(int argc, char **argv) {
             }
             x.effects_mode = m == "all" ? TFBS_EFFECTS_ALL : TFBS_EFFECTS_SITES;
         }
+        else if (k == "--scores_output") x.scores_output = val("--scores_output");
+        else if (k == "--scores_min_spread") x.scores_min_spread = strtoull(val("--scores_min_spread"), nullptr, 10);
         else if (k == "--pwm_threshold_directory") a.pwm_threshold_dir = val(k.c_str());
         else if (k == "--pwm_threshold" || k == "-t") {
             a.pwm_threshold = strtof(val(k.c_str()), nullptr);

@@ -28,6 +28,7 @@
 #include "keys.hpp"
 #include "rows.hpp"
 #include "scan.hpp"
+#include "scores.hpp"
 #include "tfbs_internal.hpp"
 
 using namespace tfbs;
@@ -300,6 +301,8 @@ struct tfbs_ctx {
     tfbs::HitsState *hits_state = nullptr;
     // best sites (tfbs_batch_best): the same, made by the first best call
     tfbs::BestState *best_state = nullptr;
+    // score rows (tfbs_batch_score_rows): the same, made by the first score-rows call
+    tfbs::ScoresState *scores_state = nullptr;
     // variant effects (tfbs_batch_effects): the same, made by the first effects call
     tfbs::EffectsState *effects_state = nullptr;
 };
@@ -860,6 +863,8 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     ctx->hits_state = nullptr;
     tfbs::best_state_destroy(ctx->best_state);
     ctx->best_state = nullptr;
+    tfbs::scores_state_destroy(ctx->scores_state);
+    ctx->scores_state = nullptr;
     tfbs::effects_state_destroy(ctx->effects_state);
     ctx->effects_state = nullptr;
     ctx->ref_count.release(); ctx->spill.release(); ctx->over.release(); ctx->spill_sorted.release();
@@ -2538,6 +2543,31 @@ int tfbs_batch_best(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_bes
 int tfbs_ctx_last_best_ms(const tfbs_ctx *ctx, double out[2]) {
     if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
     best_last_ms(ctx->best_state, out);
+    return TFBS_OK;
+}
+
+// Score rows (score_rows.hip): the batch resident here and made with membership; no scan needed.
+int tfbs_batch_score_rows(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, const char *chromosome,
+                          uint32_t min_maf, uint64_t min_spread, uint32_t *fake_position, char **text, size_t *len,
+                          uint64_t *n_rows) {
+    ScanImage img;
+    if (int rc = resident_image(ctx, b, r0, r1, !chromosome || !n_rows || (text && (!len || !fake_position)), &img))
+        return rc;
+    if (!b->b.keep_membership) return tfbs::fail(TFBS_E_STATE, "batch created without membership");
+    std::string out;
+    uint32_t fake = fake_position ? *fake_position : 1;
+    if (int rc = scores_run(&ctx->scores_state, &ctx->best_state, ctx->device, ctx->stream, *ctx->pats, img, b->b, r0, r1,
+                            tfbs::strip_chr(chromosome), min_maf, min_spread, &fake, text ? &out : nullptr, n_rows))
+        return rc;
+    if (!text) return TFBS_OK;
+    if (int rc = tfbs::text_out(out, text, len)) return rc;
+    *fake_position = fake;
+    return TFBS_OK;
+}
+
+int tfbs_ctx_last_scores_ms(const tfbs_ctx *ctx, double out[4]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    scores_last_ms(ctx->scores_state, out);
     return TFBS_OK;
 }
 

@@ -127,6 +127,36 @@ struct TextOut {
     }
 };
 
+// --scores_output: the batches' score rows (tfbs_batch_score_rows), a second VCF.  Batch g's
+// first POS is batch g - 1's plus its rows: a second chain as Ordered::chain, fed by the
+// count-only call as soon as a batch has counted its rows; the texts go out in batch order.
+struct ScoresOut {
+    TextOut out;
+    uint64_t min_spread = 1;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<int64_t> base;  // POS of batch g's first row, -1 unknown
+    bool failed = false;
+    void batches(size_t n) {
+        base.assign(n + 1, -1);
+        base[0] = 1;
+    }
+    int chain(size_t g, uint64_t n_rows, uint32_t *fake) {
+        std::unique_lock<std::mutex> l(mu);
+        cv.wait(l, [&] { return failed || base[g] >= 0; });
+        if (failed) return tfbs::fail(TFBS_E_STATE, "another device's shard failed");
+        *fake = (uint32_t)base[g];
+        base[g + 1] = base[g] + (int64_t)n_rows;
+        cv.notify_all();
+        return TFBS_OK;
+    }
+    void abort() {
+        std::lock_guard<std::mutex> l(mu);
+        failed = true;
+        cv.notify_all();
+    }
+};
+
 // Best records (48 bytes each) the run flow holds at once: whole regions up to this many, one
 // region at least (the text does not depend on the split: tfbs_batch_best_tsv takes whole regions).
 constexpr size_t kBestRunRecords = 1u << 20;
@@ -139,6 +169,7 @@ struct RunSetup {
     TextOut *best = nullptr;  // null without --best_output: the same
     TextOut *effects = nullptr;  // null without --effects_output: the same (the batches keep no variants)
     int effects_mode = TFBS_EFFECTS_SITES;
+    ScoresOut *scores = nullptr;  // null without --scores_output: the same
     std::string chrom;
     tfbs_patterns *pp;
     std::vector<std::pair<std::string, std::vector<std::pair<uint64_t, uint64_t>>>> beds;
@@ -415,6 +446,21 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
             }
             if ((rc = S.effects->submit(g, std::move(text)))) return rc;
         }
+        if (S.scores) {  // the batch's score rows: counted, then numbered from the chain and written as text
+            uint64_t n_rows = 0, n_text = 0;
+            uint32_t fk = 0;
+            char *text = nullptr;
+            size_t len = 0;
+            if ((rc = tfbs_batch_score_rows(ctx, bb, 0, B.rh.size(), S.chrom.c_str(), a->min_maf, S.scores->min_spread,
+                                            nullptr, nullptr, nullptr, &n_rows)) ||
+                (rc = S.scores->chain(g, n_rows, &fk)) ||
+                (rc = tfbs_batch_score_rows(ctx, bb, 0, B.rh.size(), S.chrom.c_str(), a->min_maf, S.scores->min_spread,
+                                            &fk, &text, &len, &n_text)))
+                return rc;
+            std::unique_ptr<char, void (*)(void *)> tguard(text, free);
+            if (n_text != n_rows) return fail(TFBS_E_STATE, "score rows: the count and the text disagree");
+            if ((rc = S.scores->out.submit(g, std::string(text, len)))) return rc;
+        }
         if (a->verbose) {
             for (size_t r = 0; r < B.rh.size(); r++)
                 fprintf(stdout, "Peak %zu/%zu\t%llu\t%llu\t%u haplotypes\t%u variants\n", g * S.per_batch + r + 1,
@@ -606,7 +652,14 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     // only what the caller's `size` covers is read
     const char *effects_output = nullptr;
     int effects_mode = TFBS_EFFECTS_SITES;
+    const char *scores_output = nullptr;
+    uint64_t scores_min_spread = 1;
     if (ext) {
+        if (ext->size >= offsetof(tfbs_run_ext, scores_output) + sizeof ext->scores_output)
+            scores_output = ext->scores_output;
+        if (ext->size >= offsetof(tfbs_run_ext, scores_min_spread) + sizeof ext->scores_min_spread &&
+            ext->scores_min_spread)
+            scores_min_spread = ext->scores_min_spread;
         if (ext->size >= offsetof(tfbs_run_ext, effects_output) + sizeof ext->effects_output)
             effects_output = ext->effects_output;
         if (ext->size >= offsetof(tfbs_run_ext, effects_mode) + sizeof ext->effects_mode) effects_mode = ext->effects_mode;
@@ -726,6 +779,12 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
         S.effects = &effects_out;
         S.effects_mode = effects_mode;
     }
+    ScoresOut scores_out;
+    if (scores_output) {
+        if ((rc = scores_out.out.open(scores_output, threads, header.c_str()))) return rc;
+        scores_out.min_spread = scores_min_spread;
+        S.scores = &scores_out;
+    }
 
     // shards: batch g of merged regions on device g % n (one device:
     // every batch); rows in merged-peak order, POS counted across the devices
@@ -739,6 +798,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
         shards[k].threads = std::max<uint32_t>(1, threads / (uint32_t)n_sh);
     }
     for (size_t g = 0; g < n_batches; g++) shards[g % n_sh].batches.push_back(g);
+    if (S.scores) S.scores->batches(n_batches);
     const std::string chr = strip_chr(S.chrom);
     uint32_t fake = 1;
     const bool timing = getenv("TFBS_RUN_TIMING") && atoi(getenv("TFBS_RUN_TIMING"));
@@ -847,6 +907,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
                 }
                 if (rc) {
                     ord.abort(rc, tfbs_last_error());
+                    if (S.scores) S.scores->abort();
                     return;
                 }
                 ord.finished(g);
@@ -860,6 +921,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
             if (shards[k].rc) {
                 shards[k].err = tfbs_last_error();
                 ord.abort(shards[k].rc, shards[k].err);
+                if (S.scores) S.scores->abort();
             }
         };
         std::vector<std::thread> ts;
@@ -885,6 +947,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     if (S.hits && (rc = hits_out.finish())) return rc;
     if (S.best && (rc = best_out.finish())) return rc;
     if (S.effects && (rc = effects_out.finish())) return rc;
+    if (S.scores && (rc = scores_out.out.finish())) return rc;
     const double t_close = now() - t0;
     if (timing)
         for (size_t k = 0; k < n_sh; k++)

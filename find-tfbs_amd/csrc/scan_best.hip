@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "hit_score.hpp"
+#include "scores.hpp"
 
 namespace tfbs {
 namespace {
@@ -154,14 +155,54 @@ void best_last_ms(const BestState *s, double out[2]) {
     for (int k = 0; k < 2; k++) out[k] = s ? s->ms[k] : 0.0;
 }
 
+int best_prepare(BestState **state, int device, void *stream, const Patterns &P, uint32_t *n_strands) {
+    HITS_TRY(hipSetDevice(device));
+    if (int rc = first_use(state, P, static_cast<hipStream_t>(stream), 2, "best-site tables")) return rc;
+    *n_strands = (*state)->n_strands;
+    return TFBS_OK;
+}
+
+int best_launch_chunk(BestState *state, void *stream_, const ScanImage &img, const uint32_t *ids,
+                      const uint64_t *hap_off, size_t nh, uint64_t nrec, const uint64_t **d_hap_off,
+                      const DevBestRec **recs, double *kernel_ms) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    BestState &S = *state;
+    int rc;
+    if ((rc = S.hap_ids.ensure(nh)) || (rc = S.hap_off.ensure(nh)) || (rc = S.recs.ensure(nrec))) return rc;
+    HITS_TRY(hipMemcpyAsync(S.hap_ids.p, ids, 4 * nh, hipMemcpyHostToDevice, stream));
+    HITS_TRY(hipMemcpyAsync(S.hap_off.p, hap_off, 8 * nh, hipMemcpyHostToDevice, stream));
+    BestArgs A{};
+    A.src = S.src(img);
+    A.posrel = img.posrel;
+    A.regions = img.regions;
+    A.inner = img.inner;
+    A.hap_ids = S.hap_ids.p;
+    A.hap_off = S.hap_off.p;
+    A.n_haps = (uint32_t)nh;
+    A.rec_cap = nrec;
+    A.recs = S.recs.p;
+    HITS_TRY(hipEventRecord(S.ev[0], stream));
+    hipLaunchKernelGGL(scan_best_kernel, dim3((uint32_t)((nh * S.n_strands + kHitWaves - 1) / kHitWaves)),
+                       dim3(kHitBlock), 0, stream, A);
+    HITS_TRY(hipGetLastError());
+    HITS_TRY(hipEventRecord(S.ev[1], stream));
+    HITS_TRY(hipEventSynchronize(S.ev[1]));  // (the host part's clock starts when the kernel is done)
+    float ms = 0;
+    HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+    *kernel_ms += ms;
+    *d_hap_off = S.hap_off.p;
+    *recs = S.recs.p;
+    return TFBS_OK;
+}
+
 int best_run(BestState **state, int device, void *stream_, const Patterns &P, const ScanImage &img, const Batch &B,
              size_t r0, size_t r1, std::vector<tfbs_best> *out) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HITS_TRY(hipSetDevice(device));
-    if (int rc = first_use(state, P, stream, 2, "best-site tables")) return rc;
+    uint32_t n_strands = 0;
+    if (int rc = best_prepare(state, device, stream_, P, &n_strands)) return rc;
     BestState &S = **state;
     S.ms[0] = S.ms[1] = 0;
-    const uint64_t ns = S.n_strands;
+    const uint64_t ns = n_strands;
     // the distinct haplotypes of [r0, r1) that have records, in order (helper reference copies
     // left out; a region without a non-empty inner range has none)
     std::vector<uint32_t> ids;
@@ -179,11 +220,6 @@ int best_run(BestState **state, int device, void *stream_, const Patterns &P, co
     const uint64_t budget = scratch_budget("TFBS_BEST_SCRATCH_MB", 256.0);  // read at the call
     auto recs_of = [&](uint32_t id) { return ns * (uint64_t)B.rh[B.haps[id].region].ranges.size(); };
 
-    BestArgs A{};
-    A.src = S.src(img);
-    A.posrel = img.posrel;
-    A.regions = img.regions;
-    A.inner = img.inner;
     int rc;
     std::vector<uint64_t> hap_off;
     for (size_t start = 0; start < ids.size();) {
@@ -199,28 +235,15 @@ int best_run(BestState **state, int device, void *stream_, const Patterns &P, co
             nrec += add;
             nh++;
         }
-        if ((rc = S.hap_ids.ensure(nh)) || (rc = S.hap_off.ensure(nh)) || (rc = S.recs.ensure(nrec)) ||
-            (rc = S.host.reserve(nrec * sizeof(DevBestRec))))
+        const uint64_t *d_hap_off;
+        const DevBestRec *d_recs;
+        if ((rc = S.host.reserve(nrec * sizeof(DevBestRec))) ||
+            (rc = best_launch_chunk(&S, stream_, img, ids.data() + start, hap_off.data(), nh, nrec, &d_hap_off, &d_recs,
+                                    &S.ms[0])))
             return rc;
-        HITS_TRY(hipMemcpyAsync(S.hap_ids.p, ids.data() + start, 4 * nh, hipMemcpyHostToDevice, stream));
-        HITS_TRY(hipMemcpyAsync(S.hap_off.p, hap_off.data(), 8 * nh, hipMemcpyHostToDevice, stream));
-        A.hap_ids = S.hap_ids.p;
-        A.hap_off = S.hap_off.p;
-        A.n_haps = (uint32_t)nh;
-        A.rec_cap = nrec;
-        A.recs = S.recs.p;
-        HITS_TRY(hipEventRecord(S.ev[0], stream));
-        hipLaunchKernelGGL(scan_best_kernel, dim3((uint32_t)((nh * ns + kHitWaves - 1) / kHitWaves)), dim3(kHitBlock),
-                           0, stream, A);
-        HITS_TRY(hipGetLastError());
-        HITS_TRY(hipEventRecord(S.ev[1], stream));
-        HITS_TRY(hipEventSynchronize(S.ev[1]));  // (the host part's clock starts when the kernel is done)
         const double t0 = now_ms();
         HITS_TRY(hipMemcpyAsync(S.host.p, S.recs.p, nrec * sizeof(DevBestRec), hipMemcpyDeviceToHost, stream));
         HITS_TRY(hipStreamSynchronize(stream));
-        float ms = 0;
-        HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
-        S.ms[0] += ms;
         const DevBestRec *rec = reinterpret_cast<const DevBestRec *>(S.host.p);
         size_t at = out->size();
         out->resize(at + nrec);

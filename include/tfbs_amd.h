@@ -833,6 +833,60 @@ int tfbs_ctx_last_effects_ms(const tfbs_ctx *ctx, double out[3]);
 int tfbs_batch_effects_tsv(const tfbs_batch *b, const tfbs_effect *e, size_t n, const char *chromosome, int mode,
                            char **text, size_t *len);
 
+/* ------------------------------------------------------------------ */
+/* Score rows: per-sample best-score genotypes as a second VCF          */
+/* ------------------------------------------------------------------ */
+/* The rows of the main output count the sites above min_score; a score row carries how
+ * strongly a sample binds.  Keys, pattern ids and values are the best TSV's: a key is a
+ * (bed, inner range) pair with a non-empty range, taken once, in the rows' order (inner
+ * start, inner end, bed as registered); under it pattern_id ascends.  B(h, q, key), the
+ * value of distinct haplotype h for pattern id q, is the best record over q's strands: the
+ * highest score, ties to the strand earlier in creation order, a strand with n_windows == 0
+ * never; "none" when all its strands have n_windows == 0.  min_score plays no part.
+ *
+ * A candidate row (key, q): sample s with haplotypes a = memb[2s], b = memb[2s + 1] has
+ * x_s = (int64)B(a) + (int64)B(b); a "none" value of a haplotype that some sample carries
+ * means no row.  lo = min x, hi = max x, spread = hi - lo (up to 2^33 - 2).  No row when
+ * n_samples == 0, spread == 0 or spread < min_spread (milli-log-odds).  With d = x_s - lo the
+ * sample's field is
+ *     d == 0             "\t0|0:0.0"      counts as zero
+ *     d == spread        "\t1|1:2.0"      counts as two
+ *     4 d < spread       "\t0|0:" DS      zero
+ *     4 d < 3 spread     "\t0|1:" DS      one
+ *     else               "\t1|1:" DS      two
+ * DS = t / 10000 "." (t % 10000 on four digits), t = round_half_even(20000 d / spread) in
+ * integers (no floating point anywhere): a field is 8 or 11 bytes.  maf is
+ * counts_as_genotypes' rule (main.rs:482-489) on the three counts; the row is written iff
+ * maf >= min_maf, as
+ *   <chr>\t<POS>\t<bed>,<name>,<start>-<end>\t.\t.\t.\tPASS\tSCORES=<lo>,<hi>;freqs=<zero>/<one>/<two>\tGT:DS<fields>\n
+ * (<chr> without any "chr", <name> tfbs_patterns_name_of, lo / hi signed decimal, POS a
+ * counter of written rows as tfbs_batch_rows' *fake_position).
+ *
+ * Host only: the definition on one candidate row's per-sample values.  1 = row (info =
+ * "SCORES=...;freqs=...", genotypes = the fields, both 0-terminated), 0 = no row;
+ * TFBS_E_ARG when a buffer is too short. */
+int tfbs_scores_as_genotypes(const int32_t *left, const int32_t *right, size_t n, uint64_t min_spread, uint32_t *maf,
+                             char *info, size_t info_cap, char *genotypes, size_t gt_cap);
+/* The score rows of regions [r0, r1) of the batch resident on ctx (after tfbs_batch_upload;
+ * needs no scan; the batch made with keep_membership, else TFBS_E_STATE as for a batch that
+ * is not resident; leaves every scan / reduce / encode / rows / hits / best result and the
+ * step graph untouched).  *text is malloc'd (tfbs_free), *len its length, *n_rows its rows;
+ * *fake_position is the first row's POS and is advanced per row.  text == NULL counts only:
+ * *n_rows is set, *fake_position left untouched (it may be NULL).  The per-sample work runs
+ * on the device (score_rows.hip): the best kernel's records are folded to values where they
+ * lie, a row's statistics come from the region's distinct haplotype pairs, and the text
+ * kernel writes the fields; the text equals tfbs_scores_as_genotypes' byte for byte.  Device
+ * scratch (records, values, tokens, the text of some rows at a time) is bounded by
+ * TFBS_SCORES_SCRATCH_MB (default 256, fractions allowed, read at the call; at least one
+ * region's records and one row's text); the result does not depend on it. */
+int tfbs_batch_score_rows(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, const char *chromosome,
+                          uint32_t min_maf, uint64_t min_spread, uint32_t *fake_position, char **text, size_t *len,
+                          uint64_t *n_rows);
+/* The last tfbs_batch_score_rows' times (ms): out[0] the best kernel, out[1] the fold and
+ * statistics kernels, out[2] the text kernel (HIP events on the ctx stream, summed over the
+ * scratch chunks), out[3] the copy-back and host part (wall). */
+int tfbs_ctx_last_scores_ms(const tfbs_ctx *ctx, double out[4]);
+
 void tfbs_free(void *p);
 
 /* counts_as_genotypes alone (main.rs:439-498): 1 = row (strings written), 0 = no variation. */
@@ -893,6 +947,10 @@ typedef struct tfbs_run_ext {
                                        (tfbs_batch_effects_tsv under TFBS_EFFECTS_HEADER), NULL = none: the run
                                        does nothing more than without it (its batches keep no variants) */
     int effects_mode;               /* --effects_mode: TFBS_EFFECTS_SITES / TFBS_EFFECTS_ALL */
+    const char *scores_output;      /* --scores_output: the batches' score rows (tfbs_batch_score_rows) as a second
+                                       BGZF VCF under the main output's #CHROM line, POS from 1, min_maf as the
+                                       main rows'; NULL = none: the run does nothing more than without it */
+    uint64_t scores_min_spread;     /* --scores_min_spread: tfbs_batch_score_rows' min_spread (0 counts as 1) */
 } tfbs_run_ext;
 int tfbs_run_ex(const tfbs_run_args *args, const tfbs_run_ext *ext);
 
