@@ -243,6 +243,7 @@ SIGNATURES = [
     ("tfbs_synth_region_record", None, [vp, C.c_size_t, u64p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p),
                                         C.POINTER(u32p), C.POINTER(C.c_size_t)]),
     ("tfbs_synth_fill_batch", C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
+    ("tfbs_ctx_group_pairs", C.c_int, [vp, C.c_int, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
 ]
 
 _lib = None

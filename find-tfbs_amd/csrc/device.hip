@@ -142,6 +142,8 @@ struct tfbs_ctx {
     // the merged scan's unit, groups per workgroup (ScanArgs::unit): TFBS_SCAN_UNIT = 1, 2, 4
     // forces it, 0 / unset: chosen per batch (scan_unit_for); scan_unit: the resident batch's
     uint32_t scan_unit_env = 0, scan_unit = 1;
+    uint32_t wl_n_haps = 0;               // haplotypes the resident window lists were built for
+    uint32_t scan_unit_words_env = 0;  // TFBS_SCAN_UNIT_WORDS: 1 lds, 2 global, 0 the host's choice (ScanArgs::unit_words)
     uint32_t n_cus = 256;           // the device's compute units
     // batch image
     DevBuf<uint32_t> words, nmask, counts;  // counts: dense, for the LUT/generic slots (and tfbs_batch_download)
@@ -351,22 +353,23 @@ static int env_int(const char *name, int dflt) {
 }
 
 // The merged scan's unit for a batch of n_groups haplotype groups (ScanArgs::unit): a
-// unit pays a super tile image's staging once for its G groups, but G times fewer
-// workgroups fill the chip worse -- the largest G of 4, 2, 1 whose units still give
-// each of the chip's workgroup slots (two per CU) kUnitRounds workgroups in turn
-// ("Units": the measurements behind the number).  And only where the image's
-// staging is a large part of a group's work: a group's list of either depth class holds
-// at most kUnitPairs pairs of window tiles on average, two per wave (C5's groups hold 38:
-// their waves scan for longer than an image takes to stage, and units of four made its
-// step 2.5 % slower -- the per-group barriers and the longer candidate lists).
-constexpr uint32_t kUnitRounds = 4, kUnitPairs = 2 * kMBlockWaves;
+// unit pays a super tile image's staging once for its G groups and hands their window
+// pairs to its waves from one pool, but G times fewer workgroups fill the chip worse --
+// the largest G of 4, 2, 1 whose units still give the chip's workgroup slots (two per
+// CU) one and a half workgroups each in turn ("Units": the sweep behind the
+// number -- units paid from 1.85 rounds up and not at 0.96 or below).  And only where a
+// group's list is short: a group's list of either depth class holds at most kUnitPairs
+// pairs of window tiles on average, two per wave (C5's groups hold 38: their waves scan
+// for longer than an image takes to stage and are balanced without the pool; units of two
+// or four neither gained nor lost there beyond the runs' spread).
+constexpr uint32_t kUnitPairs = 2 * kMBlockWaves;
 static uint32_t scan_unit_for(const tfbs_ctx *ctx, uint32_t n_groups) {
     if (!ctx->mfma_merged) return 1;
     if (ctx->scan_unit_env) return ctx->scan_unit_env;
     for (int c = 0; c < 2; c++)
         if (ctx->wl_entries[c] > (uint64_t)kUnitPairs * 64 * n_groups) return 1;
     for (uint32_t G = kMMaxUnit; G > 1; G /= 2)
-        if ((n_groups + G - 1) / G >= (uint64_t)kUnitRounds * 2 * ctx->n_cus) return G;
+        if (2 * (uint64_t)((n_groups + G - 1) / G) >= 3 * (uint64_t)(2 * ctx->n_cus)) return G;
     return 1;
 }
 
@@ -378,6 +381,7 @@ static uint32_t scan_unit_for(const tfbs_ctx *ctx, uint32_t n_groups) {
 static int build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t> &narrow, Batch *B = nullptr) {
     const Plan &P = ctx->plan;
     ctx->wl_share = false;
+    ctx->wl_n_haps = n_haps;
     for (int c = 0; c < 2; c++) ctx->sh_entries[c] = ctx->sh_listed[c][0] = ctx->sh_listed[c][1] = 0;
     if (B) B->lists_counted = false;
     if (P.m_supers.empty()) return TFBS_OK;
@@ -587,6 +591,7 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
         m.gnarrow = ctx->gnarrow.n ? ctx->gnarrow.p : nullptr;
         m.gorder = ctx->mfma_merged && ctx->gorder.n ? ctx->gorder.p : nullptr;
         m.unit = ctx->mfma_merged ? ctx->scan_unit : 1;  // (gorder holds units of as many groups)
+        m.unit_words = ctx->scan_unit_words_env;
         m.hd = ctx->hd.p;
         m.hd2 = ctx->hd2.p;
         m.druns = ctx->druns.p;
@@ -947,6 +952,8 @@ int tfbs_ctx_create(int device, const tfbs_patterns *p, tfbs_ctx **out) {
     {
         const int u = env_int("TFBS_SCAN_UNIT", 0);
         ctx->scan_unit_env = u == 1 || u == 2 || u == 4 ? (uint32_t)u : 0u;
+        const char *uw = getenv("TFBS_SCAN_UNIT_WORDS");
+        ctx->scan_unit_words_env = uw && !strcmp(uw, "lds") ? 1u : uw && !strcmp(uw, "global") ? 2u : 0u;
     }
     ctx->debug_over = env_int("TFBS_DEBUG_OVER", 0) != 0;
     ctx->kf_prof_on = env_int("TFBS_KF_PROF", 0) != 0;
@@ -1116,6 +1123,26 @@ int tfbs_ctx_window_lists(const tfbs_ctx *ctx, uint64_t entries[2], double *seco
     entries[0] = ctx->wl_entries[0];
     entries[1] = ctx->wl_entries[1];
     *seconds = ctx->wl_seconds;
+    return TFBS_OK;
+}
+
+int tfbs_ctx_group_pairs(tfbs_ctx *ctx, int cls, uint32_t *pairs, size_t cap, size_t *n_groups) {
+    if (!ctx || !n_groups || cls < 0 || cls > 1 || (cap && !pairs)) return tfbs::fail(TFBS_E_ARG, "bad argument");
+    const uint32_t n = ctx->wl_n_haps, hpb = ctx->mfma_hpb;
+    *n_groups = ((size_t)n + hpb - 1) / hpb;
+    if (*n_groups > cap) return cap ? tfbs::fail(TFBS_E_ARG, "group pairs: the array is too small") : TFBS_OK;
+    if (!ctx->wl_off[cls].p) {  // no super tile of the class: no list
+        for (size_t g = 0; g < *n_groups; g++) pairs[g] = 0;
+        return TFBS_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<uint64_t> off((size_t)n + 1);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(off.data(), ctx->wl_off[cls].p, off.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t g = 0; g < *n_groups; g++) {
+        const uint64_t nw = off[std::min<size_t>((g + 1) * hpb, n)] - off[g * hpb];
+        pairs[g] = (uint32_t)(((nw + 31) / 32 + 1) / 2);
+    }
     return TFBS_OK;
 }
 

@@ -79,6 +79,13 @@ struct ScanArgs {
     // launch ends on the small ones); null: unit b
     const uint32_t *gorder;
     uint32_t unit;
+    // a unit's packed words (TFBS_SCAN_UNIT_WORDS): unit_words 0 = the host chooses
+    // (global, as measured), 1 = "lds" (as many of the unit's first groups as fit beside
+    // the image are copied to the LDS once per workgroup), 2 = "global" (read from
+    // `words`); launch_mfma_all
+    // sets unit_lds, the groups with LDS words, and unit_lds_words, their room (a unit
+    // whose first unit_lds groups span more reads all its words from global memory)
+    uint32_t unit_words, unit_lds, unit_lds_words;
     const uint64_t *wlist_off[2];
     // shared windows (build_window_lists, share != 0), per depth class: a window listed
     // for its donor haplotype only stands for the same window of the region's other

@@ -671,8 +671,8 @@ __device__ __forceinline__ void load_frag0(const char *tile, uint32_t lane, BFra
 // shader cycles from a two-tile round's top to its first MFMA's issue (the chunk-0 B
 // fragment and the matrix pipe), first to last MFMA issued, last MFMA to the test's
 // decision, the firing path; rounds, fired rounds; the super tiles' restaging; the
-// pairs' own work (next pair, list entries, A fragments); [8] (stamp word 3) a unit's
-// per-group restaging inside the super tiles.  s_memtime between
+// pairs' own work (next pair, list entries, A fragments); [8] (stamp word 3) the wave's
+// wait at the super tiles' two barriers (every super tile).  s_memtime between
 // scheduling barriers: the stamps order the round but add their own latency.
 __shared__ unsigned long long s_rprof[kMBlock / 64][9];
 #define RPROF_T() ({ __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
@@ -805,6 +805,156 @@ __device__ __forceinline__ void entry_onehot(const ScanArgs &A, const uint32_t *
     build_onehot<NK>(hm, i, ww, tab, a);
 }
 
+// The unit kernel's pair pool (scan_pool).  A unit's descriptors stay in the LDS for the
+// whole workgroup (s_hdu: haplotype h0 + t of the unit at t, so a group's entry is found
+// at its bias + the entry's six haplotype bits), and s_pool holds, per depth class, one
+// word of four per group of the unit: x = the pairs of
+// window tiles of the groups up to and including it (a group without a window in the
+// class, or past the unit's last, adds none: x of the last entry is the pool's size),
+// y = the entries of its list | narrow << 31, (z, w) = the list's first entry in
+// wlist / wlist16.
+__shared__ uint4 s_hdu[kMMaxUnit * kMMaxHapsPerBlock];
+__shared__ uint4 s_pool[2][kMMaxUnit];
+static_assert(kMMaxUnit * kMMaxHapsPerBlock <= kMBlock, "one thread per descriptor of a unit");
+constexpr uint32_t kPoolNarrow = 1u << 31;
+
+__device__ __forceinline__ uint32_t pool_pairs(uint32_t nw) { return ((nw + kMWindows - 1) / kMWindows + 1) / 2; }
+
+// Written once by the workgroup's first wave, before the first super tile's barriers
+// (hg0 / h0: the unit's first group / haplotype; lane 4 c + g: class c, group g; a class
+// without a super tile has no list and an empty pool).
+__device__ __forceinline__ void pool_fill(const ScanArgs &A, uint32_t hg0, uint32_t h0, uint32_t ngu, uint32_t lane) {
+    uint32_t has = 0;
+    for (uint32_t si = 0; si < A.n_msupers; si++) has |= A.msupers[si].nk > 2 ? 2u : 1u;
+    const uint32_t gi = lane & (kMMaxUnit - 1), c = (lane / kMMaxUnit) & 1u;
+    const uint64_t *off = c ? A.wlist_off[1] : A.wlist_off[0];
+    uint32_t nw = 0, narrow = 0;
+    uint64_t e0 = 0;
+    if (lane < 2 * kMMaxUnit && gi < ngu && ((has >> c) & 1u) && off) {
+        const uint32_t gh0 = h0 + gi * A.haps_per_block, gh1 = min(gh0 + A.haps_per_block, A.n_haps);
+        e0 = off[gh0];
+        nw = (uint32_t)(off[gh1] - e0);
+        narrow = (A.gnarrow && A.gnarrow[hg0 + gi]) ? kPoolNarrow : 0u;
+    }
+    const uint32_t np = pool_pairs(nw);
+    uint32_t end = 0;
+    for (uint32_t j = 0; j < kMMaxUnit; j++) {  // (by the whole wave)
+        const uint32_t v = (uint32_t)__shfl((int)np, (int)(lane - gi + j));
+        end += j <= gi ? v : 0u;
+    }
+    if (lane < 2 * kMMaxUnit) s_pool[c][gi] = make_uint4(end, nw | narrow, (uint32_t)e0, (uint32_t)(e0 >> 32));
+}
+
+// entry_onehot for a group of a unit: hd its resident descriptors, the words from the
+// unit's LDS copy or global memory (two copies of the loads, no flat access).
+template <int NK>
+__device__ __forceinline__ void pool_onehot(const ScanArgs &A, const uint32_t *lwords, bool in_lds, const uint4 *hd,
+                                            uint32_t we, const char *tab, v4i (&a)[NK]) {
+    const uint4 d = hd[we & (kMMaxHapsPerBlock - 1)];
+    const LaneHap hm{d.x, d.y, d.z, d.w};
+    const uint32_t i = we >> 6;
+    WinWords ww;
+    if (in_lds) load_window(A, lwords, hm, i, ww);
+    else load_window(A, A.words, hm, i, ww);
+    build_onehot<NK>(hm, i, ww, tab, a);
+}
+
+// One super tile's window pairs over the lists of ALL the unit's groups for the tile's
+// depth class: the waves draw pair p of the pool from s_hnext, find its group by three
+// uniform compares with the running pair counts and score that group's pair p - the
+// group's first -- two consecutive tiles of one group's list, cut as scan_loop cuts
+// them.  No barrier inside a super tile: a group's descriptors are resident, its words
+// come from the unit's LDS copy (lwords, the unit's first nlds groups) or from global
+// memory (the base uniform in the wave, chosen per pair).  A queue record is labelled
+// with the group of the pair that drains it, so the wave drains its queue whenever its
+// next pair belongs to another group (wave-local), and after its last pair.
+template <int NK>
+__device__ __forceinline__ uint32_t scan_pool(const ScanArgs &A, const DevMSuper &S, const char *s_img,
+                                              const uint32_t *lwords, uint32_t nlds, uint32_t h0, uint32_t slot,
+                                              uint32_t ngu, uint32_t lane, uint32_t wave, uint32_t &qn, uint32_t &cn) {
+    constexpr int c = NK > 2;
+    const uint32_t hpb = A.haps_per_block;
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pool[c][kMMaxUnit - 1].x);
+    const float a0f = __uint_as_float(S.acc0);
+    v16f cb = {a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f, a0f};
+    asm volatile("" : "+v"(cb));  // kept in VGPRs: every round's MFMAs read it (no per-round copies)
+    const int sa = lane < 32 ? kScaleD0 : kScaleD1;
+    const char *tab = s_img - kMOnehotBytes;
+    auto next_pair = [&]() {
+        uint32_t p = 0;
+        if (lane == 0) p = atomicAdd(&s_hnext, 1u);
+        return (uint32_t)__builtin_amdgcn_readfirstlane(p);
+    };
+    // pair p's group (gi) and list (G), all wave-uniform; returns the pair's index in the list
+    auto place = [&](uint32_t p, GroupCtx &G, uint32_t &gi) {
+        gi = 0;
+        for (uint32_t u = 0; u + 1 < kMMaxUnit; u++)
+            gi += p >= (uint32_t)__builtin_amdgcn_readfirstlane((int)s_pool[c][u].x) ? 1u : 0u;
+        const uint4 t = s_pool[c][gi];
+        const uint32_t end = (uint32_t)__builtin_amdgcn_readfirstlane((int)t.x);
+        const uint32_t y = (uint32_t)__builtin_amdgcn_readfirstlane((int)t.y);
+        const uint64_t e0 = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)t.z) |
+                            ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)t.w) << 32);
+        G.wl = A.wlist[c] + e0;
+        G.wl16 = (y & kPoolNarrow) ? A.wlist16[c] + e0 : nullptr;
+        G.nw = y & ~kPoolNarrow;
+        G.tile0 = S.tile0;
+        G.h0 = h0 + gi * hpb;
+        G.slot = slot;
+        G.ub = unit_place(gi * hpb, ngu);
+        return p - (end - pool_pairs(G.nw));
+    };
+    // lane l scores window row l & 31 of each tile
+    auto entries = [&](const GroupCtx &G, uint32_t q, uint32_t &ea, uint32_t &eb) {
+        const uint32_t r = kMWindows * 2 * q + (lane & 31);
+        ea = G.at(min(r, G.nw - 1));
+        eb = G.at(min(r + kMWindows, G.nw - 1));
+    };
+    uint32_t p = next_pair(), ea = 0, eb = 0, n_pairs = 0;
+    if (p < total) {
+        GroupCtx G;
+        uint32_t gi;
+        const uint32_t q = place(p, G, gi);
+        entries(G, q, ea, eb);
+    }
+    while (p < total) {
+        n_pairs++;
+#ifdef TFBS_ROUND_PROF
+        const unsigned long long tp0 = RPROF_T();
+#endif
+        GroupCtx G;
+        uint32_t gi;
+        const uint32_t q = place(p, G, gi);
+        const uint32_t pn = next_pair();
+        const bool two = 2 * q + 1 < (G.nw + kMWindows - 1) / kMWindows;
+        v4i a0[NK], a1[NK];
+        const bool in_lds = gi < nlds;
+        const uint4 *hd = s_hdu + gi * hpb;
+        pool_onehot<NK>(A, lwords, in_lds, hd, ea, tab, a0);
+        pool_onehot<NK>(A, lwords, in_lds, hd, eb, tab, a1);  // (a copy of the last window when !two: unused)
+        const uint32_t e0 = ea, e1 = eb;  // (the firing path's entries: the lane's own)
+        uint32_t gn = gi;
+        if (pn < total) {  // the next pair's entries, maybe another group's: in flight while this pair is scored
+            GroupCtx Gn;
+            const uint32_t qnx = place(pn, Gn, gn);
+            entries(Gn, qnx, ea, eb);
+        }
+#ifdef TFBS_ROUND_PROF
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (as scan_loop: the A fragments awaited here)
+        const unsigned long long tp1 = RPROF_T();
+        RPROF_ADD(wave, 7, tp1 - tp0);
+#endif
+        if (two) scan_step<NK, true>(A, s_img, S.seg, G, lane, wave, a0, a1, 2 * q, e0, e1, cb, sa, qn, cn);
+        else scan_step<NK, false>(A, s_img, S.seg, G, lane, wave, a0, a1, 2 * q, e0, e1, cb, sa, qn, cn);
+        if (pn >= total || gn != gi) {  // the queue's records are this group's: decoded before another's join them
+            drain_queue(A, G, qn, wave, lane, cn);
+            qn = 0;
+        }
+        p = pn;
+    }
+    return n_pairs;
+}
+
 // words: the packed haplotype words, indexed by DevHap::word_off (an LDS copy
 // of this workgroup's haplotypes, biased by their first word, or global memory).
 // The group's window list (the windows of its haplotypes the class reads) is
@@ -814,8 +964,8 @@ __device__ __forceinline__ void entry_onehot(const ScanArgs &A, const uint32_t *
 // loaded while the current pair is scored.
 #ifdef TFBS_SCAN_PROF
 // per wave of the workgroup's (unit's) first slot: [0] s_memtime at the kernel's start,
-// [1] after the staging barrier, [2] after the scan loops, [3] cycles of the per-group
-// restaging (TFBS_ROUND_PROF, else 0), [4] after the rescoring, [5] / [6]
+// [1] after the staging barrier, [2] after the scan loops, [3] cycles waited at the super
+// tiles' barriers (TFBS_ROUND_PROF, else 0), [4] after the rescoring, [5] / [6]
 // s_memrealtime (100 MHz, one clock for the chip) at the start and the end, [7] pairs
 // scored | candidates << 32; [8, 16) TFBS_ROUND_PROF's split
 #define SCAN_STAMP(k, v) \
@@ -912,13 +1062,12 @@ __device__ __forceinline__ void stage_onehot(int32_t *smem) {
 }
 
 // A group's descriptors and (STAGED) its packed words after the image budget; returns
-// the words' base for DevHap::word_off.  (A unit restages them per group inside each
-// super tile: ~2 KB of descriptors and ~5 KB of words at C3, against the image's 36-44.)
-template <bool STAGED, bool HD2 = true>
+// the words' base for DevHap::word_off (the kernels of one group per workgroup).
+template <bool STAGED>
 __device__ __forceinline__ const uint32_t *stage_group(const ScanArgs &A, int32_t *smem, uint32_t h0, uint32_t hn) {
-    if (threadIdx.x < hn) {  // (32 of DevHap's 48 bytes; HD2: the rescoring's half)
+    if (threadIdx.x < hn) {  // (32 of DevHap's 48 bytes; s_hd2: the rescoring's half)
         s_hd[threadIdx.x] = A.hd[h0 + threadIdx.x];
-        if (HD2) s_hd2[threadIdx.x] = A.hd2[h0 + threadIdx.x];
+        s_hd2[threadIdx.x] = A.hd2[h0 + threadIdx.x];
     }
     if (!STAGED) return A.words;
     const uint4 f = A.hd[h0], l = A.hd[h0 + hn - 1];
@@ -926,6 +1075,26 @@ __device__ __forceinline__ const uint32_t *stage_group(const ScanArgs &A, int32_
     const uint32_t wend = l.x + (l.y + 15) / 16 + 3;
     uint32_t *s_words = reinterpret_cast<uint32_t *>(smem) + (kMOnehotBytes + A.mimg_max + kMChunkBytes) / 4;
     for (uint32_t i = threadIdx.x; i < wend - wbeg; i += kMBlock) s_words[i] = A.words[wbeg + i];
+    return s_words - wbeg;
+}
+
+// A unit's packed words, once per workgroup: its haplotypes are consecutive, so the words
+// of its first ng groups (hn: the unit's haplotypes) are one range, from the first's
+// word_off to the last's end as stage_group takes a group's, copied after the image
+// budget when it fits the room the host reserved (A.unit_lds_words); *nlds = ng then,
+// else 0 (every group of the unit reads global memory).  Returns the LDS base for
+// DevHap::word_off.
+__device__ __forceinline__ const uint32_t *stage_unit_words(const ScanArgs &A, int32_t *smem, uint32_t h0, uint32_t hn,
+                                                            uint32_t ng, uint32_t *nlds) {
+    uint32_t *s_words = reinterpret_cast<uint32_t *>(smem) + (kMOnehotBytes + A.mimg_max + kMChunkBytes) / 4;
+    *nlds = 0;
+    if (ng == 0) return s_words;
+    const uint4 f = A.hd[h0], l = A.hd[h0 + min(ng * A.haps_per_block, hn) - 1];
+    const uint32_t wbeg = f.x;
+    const uint32_t wend = l.x + (l.y + 15) / 16 + 3;
+    if (wend < wbeg || wend - wbeg > A.unit_lds_words) return s_words;
+    for (uint32_t i = threadIdx.x; i < wend - wbeg; i += kMBlock) s_words[i] = A.words[wbeg + i];
+    *nlds = ng;
     return s_words - wbeg;
 }
 
@@ -983,13 +1152,14 @@ __device__ void post_one_block(const ScanArgs &A, uint32_t tid, uint32_t n_regio
 namespace {
 
 // UNIT: the workgroup's haplotypes are a unit of A.unit consecutive groups (the
-// last unit may be short).  The one-hot table is built and each super tile's image
-// staged once per unit; inside a super tile the unit's groups follow one another --
-// per group only the descriptors and packed words are restaged and the pair counter
-// reset, between two barriers (the first group's with the image) -- and scan_loop runs
-// per group as it is.  The wave's candidates of all groups and super tiles share one
-// list and are rescored once (rescore_list<true>); every group keeps its own slot for
-// the hit lists and counts.  !UNIT is the kernel of one group per workgroup.
+// last unit may be short).  The one-hot table, the unit's descriptors (s_hdu) and, where
+// the host gave them room (STAGED, A.unit_lds groups), the packed words of the unit's
+// first groups are staged once per workgroup, each super tile's image once per unit; inside
+// a super tile the waves draw the window pairs of all the unit's groups from one pool
+// (scan_pool), with no barrier but the two around the image's staging.  The wave's
+// candidates of all groups and super tiles share one list and are rescored once
+// (rescore_list<true>); every group keeps its own slot for the hit lists and counts.
+// !UNIT is the kernel of one group per workgroup.
 template <bool STAGED, bool UNIT>
 __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
 #ifdef TFBS_SCAN_PROF
@@ -1004,16 +1174,21 @@ __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
     const uint32_t h0 = hg0 * hpb;
     stage_onehot(smem);
     const uint32_t *words = nullptr;
-    if (!UNIT) words = stage_group<STAGED>(A, smem, h0, min(h0 + hpb, A.n_haps) - h0);
+    uint32_t nlds = 0;  // UNIT: the unit's first groups whose words are in the LDS
+    if (!UNIT) {
+        words = stage_group<STAGED>(A, smem, h0, min(h0 + hpb, A.n_haps) - h0);
+    } else {
+        const uint32_t hn = min(h0 + ngu * hpb, A.n_haps) - h0;
+        if (threadIdx.x < hn) s_hdu[threadIdx.x] = A.hd[h0 + threadIdx.x];
+        if (STAGED) words = stage_unit_words(A, smem, h0, hn, min(A.unit_lds, ngu), &nlds);
+        if (threadIdx.x < 64) pool_fill(A, hg0, h0, ngu, threadIdx.x);
+    }
     const char *s_img = reinterpret_cast<const char *>(smem) + kMOnehotBytes;
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #ifdef TFBS_SETPRIO
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);  // (A/B) the workgroup's second half wins issue ties
 #endif
     uint32_t qn = 0, cn = 0, n_pairs = 0;
-#ifdef TFBS_SCAN_PROF
-    bool first = true;
-#endif
 #ifdef TFBS_ROUND_PROF
     if (threadIdx.x < kMBlockWaves * 9) (&s_rprof[0][0])[threadIdx.x] = 0;
 #endif
@@ -1022,38 +1197,39 @@ __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
 #ifdef TFBS_ROUND_PROF
         const unsigned long long ts0 = RPROF_T();
 #endif
-        __syncthreads();  // the previous image's readers are done
+        __syncthreads();  // the previous image's readers (and the pool's) are done
+#ifdef TFBS_ROUND_PROF
+        const unsigned long long ts1 = RPROF_T();
+#endif
 #ifdef TFBS_AB_NORESTAGE  // timing ablation (wrong results): the first image only
         if (si == 0)
 #endif
         stage_image(A, S, reinterpret_cast<uint4 *>(smem));
-        for (uint32_t gi = 0; gi < ngu; gi++) {
+        if (threadIdx.x == 0) s_hnext = 0;
 #ifdef TFBS_ROUND_PROF
-            const unsigned long long tg0 = RPROF_T();
+        const unsigned long long ts2 = RPROF_T();
 #endif
-            if (UNIT) {
-                if (gi) __syncthreads();  // the previous group's readers are done
-                const uint32_t gh0 = h0 + gi * hpb;
-                words = stage_group<STAGED, false>(A, smem, gh0, min(gh0 + hpb, A.n_haps) - gh0);
-            }
-            if (threadIdx.x == 0) s_hnext = 0;
-            __syncthreads();
+        __syncthreads();
 #ifdef TFBS_ROUND_PROF
-            if (gi) RPROF_ADD(wave, 8, RPROF_T() - tg0);
-            else if (si) RPROF_ADD(wave, 6, RPROF_T() - ts0);
+        {
+            const unsigned long long ts3 = RPROF_T();
+            if (si) RPROF_ADD(wave, 6, ts3 - ts0);
+            RPROF_ADD(wave, 8, (ts1 - ts0) + (ts3 - ts2));  // the wave's wait at the super tile's barriers
+        }
 #endif
 #ifdef TFBS_SCAN_PROF
-            if (first) {
-                SCAN_STAMP(0, t_start);
-                SCAN_STAMP(5, r_start);
-                SCAN_STAMP(1, __builtin_amdgcn_s_memtime());
-                first = false;
-            }
-#endif
-            const uint32_t ub = unit_place(gi * hpb, ngu);
-            n_pairs += S.nk > 2 ? scan_loop<4>(A, S, s_img, words, hg0 + gi, slot, ub, lane, wave, qn, cn)
-                                : scan_loop<2>(A, S, s_img, words, hg0 + gi, slot, ub, lane, wave, qn, cn);
+        if (si == 0) {
+            SCAN_STAMP(0, t_start);
+            SCAN_STAMP(5, r_start);
+            SCAN_STAMP(1, __builtin_amdgcn_s_memtime());
         }
+#endif
+        if (UNIT)
+            n_pairs += S.nk > 2 ? scan_pool<4>(A, S, s_img, words, nlds, h0, slot, ngu, lane, wave, qn, cn)
+                                : scan_pool<2>(A, S, s_img, words, nlds, h0, slot, ngu, lane, wave, qn, cn);
+        else
+            n_pairs += S.nk > 2 ? scan_loop<4>(A, S, s_img, words, hg0, slot, unit_place(0, 1), lane, wave, qn, cn)
+                                : scan_loop<2>(A, S, s_img, words, hg0, slot, unit_place(0, 1), lane, wave, qn, cn);
     }
     (void)n_pairs;
     SCAN_STAMP(2, __builtin_amdgcn_s_memtime());
@@ -1066,7 +1242,7 @@ __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
     SCAN_STAMP(7, (unsigned long long)n_pairs | ((unsigned long long)cn << 32));
 #ifdef TFBS_ROUND_PROF
     for (int k = 0; k < 8; k++) SCAN_STAMP(8 + k, s_rprof[wave][k]);
-    SCAN_STAMP(3, s_rprof[wave][8]);  // the per-group restaging inside the super tiles
+    SCAN_STAMP(3, s_rprof[wave][8]);  // the wait at the super tiles' barriers
 #endif
     if (A.post_done) {  // fused post-scan: the last workgroup to finish does it
         __syncthreads();  // every wave's lists and spill records are written
@@ -1777,12 +1953,30 @@ int launch_mfma_all(const ScanArgs &a0, const DevMSuper *supers, uint32_t n_supe
     for (uint32_t k = 0; k < n_supers; k++) img_bytes = std::max<size_t>(img_bytes, supers[k].img_bytes);
     const size_t base = kMOnehotBytes + img_bytes + kMChunkBytes;  // (the padding: scan_segment's B prefetch)
     const size_t staged_bytes = base + ((size_t)group_words * 4 + 15) / 16 * 16;
-    const bool staged = staged_bytes + static_lds <= kMStagedMax;
-    // (TFBS_SCAN_LDS_MIN: an occupancy A/B -- more LDS per workgroup, fewer per CU)
-    static const size_t lds_min = getenv("TFBS_SCAN_LDS_MIN") ? (size_t)atol(getenv("TFBS_SCAN_LDS_MIN")) : 0;
-    const size_t lds = std::max(staged ? staged_bytes : base, lds_min);
+    bool staged = staged_bytes + static_lds <= kMStagedMax;
     // a unit of G groups per workgroup (ScanArgs::unit); G = 1: the kernel of one group
     const uint32_t G = std::min(std::max(a0.unit, 1u), kMMaxUnit);
+    // A unit's words (ScanArgs::unit_words): k consecutive groups span at most k x
+    // group_words, so that many of a unit's first groups have LDS words as fit beside the
+    // largest image and the unit kernel's static LDS (the resident descriptors and the
+    // pool instead of s_hd) under kMStagedMax (TFBS_SCAN_UNIT_WORDS=lds); the others' --
+    // and all of a unit the room does not hold -- are read from global memory, as every
+    // unit's are with "global" or unset.
+    uint32_t unit_lds = 0;
+    size_t unit_bytes = base;
+    if (G > 1) {
+        const size_t static_unit = static_lds - sizeof(s_hd) - sizeof(s_hd2) + sizeof(s_hdu) + sizeof(s_pool) + 64;
+        const size_t gw = std::max<size_t>(((size_t)group_words * 4 + 15) / 16 * 16, 16);
+        const size_t room = kMStagedMax > base + static_unit ? kMStagedMax - base - static_unit : 0;
+        // (the host's choice is global words: measured as fast as the LDS copy or faster for every G
+        // at C3 and C2, DESIGN.md "Units"; the LDS copy only when forced)
+        if (a0.unit_words == 1) unit_lds = (uint32_t)std::min<size_t>(G, room / gw);
+        unit_bytes = base + unit_lds * gw;
+        staged = unit_lds > 0;
+    }
+    // (TFBS_SCAN_LDS_MIN: an occupancy A/B -- more LDS per workgroup, fewer per CU)
+    static const size_t lds_min = getenv("TFBS_SCAN_LDS_MIN") ? (size_t)atol(getenv("TFBS_SCAN_LDS_MIN")) : 0;
+    const size_t lds = std::max(G > 1 ? unit_bytes : staged ? staged_bytes : base, lds_min);
     const MfmaKernel kern = mfma_all_variant(staged, G > 1);
     hipError_t e = hipSuccess;
     if (lds > 64 * 1024)
@@ -1795,6 +1989,8 @@ int launch_mfma_all(const ScanArgs &a0, const DevMSuper *supers, uint32_t n_supe
         const uint32_t h0 = (uint32_t)(g0 * hpb);
         ScanArgs a = a0;
         a.unit = G;
+        a.unit_lds = unit_lds;
+        a.unit_lds_words = (uint32_t)((unit_bytes - base) / 4);
         a.haps = a0.haps + h0;
         a.hd = a0.hd + h0;
         a.hd2 = a0.hd2 + h0;

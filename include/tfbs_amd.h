@@ -1019,6 +1019,14 @@ void tfbs_synth_region_record(const tfbs_synth_region *r, size_t i, uint64_t *po
  * registered on first use; each region's inner peak is its BED row). */
 int tfbs_synth_fill_batch(tfbs_batch *b, uint64_t seed, uint64_t first, uint64_t count, uint32_t indel_pct);
 
+/* The resident batch's matrix-core window lists, per haplotype group (groups of
+ * TFBS_MFMA_HAPS_PER_BLOCK haplotypes, in batch order): pairs[g] = the pairs of window
+ * tiles (32 windows each, the last pair of an odd count holds one) of group g's list of
+ * depth class cls (0: strands of up to 16 columns' tiles, 1: the longer ones') -- what the
+ * scan's waves draw, one pair at a time.  *n_groups receives the group count; cap = 0 only
+ * asks for it.  Waits for the stream.  Zeros for a class without tiles. */
+int tfbs_ctx_group_pairs(tfbs_ctx *ctx, int cls, uint32_t *pairs, size_t cap, size_t *n_groups);
+
 #ifdef __cplusplus
 }
 #endif

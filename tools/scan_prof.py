@@ -8,9 +8,11 @@ chip-wide 100 MHz clock the launch's span and its tail (the time after 90 / 99 %
 its workgroups ended).  The merged kernel's stamps are per (unit, wave), at the unit's
 first slot (a unit: the haplotype groups one workgroup scans, TFBS_SCAN_UNIT): pairs
 and phases are per wave of a unit.  A TFBS_ROUND_PROF build adds the rounds' clock
-split and, as shares of the loop, the super tiles' restaging and the per-group
-restaging inside a super tile (a unit's groups after its first: descriptors, words,
-two barriers).  The last scan in the file is read.
+split and, as shares of the loop, the super tiles' restaging (images after the first,
+from the barrier before the copy to the barrier after it) and the wave's wait at the
+super tiles' two barriers (`barrier_wait`, every super tile: the part of the staging
+and restaging that is waiting for the workgroup's slowest wave, not copying; inside a
+super tile there is no barrier).  The last scan in the file is read.
 
 Usage: python tools/scan_prof.py FILE [OUT_JSON]
 """
@@ -68,7 +70,7 @@ def main():
         }
         if w[:, :, 12].sum() > 0:  # TFBS_ROUND_PROF build: the two-tile rounds' clock split
             rb, rm, rt, rf, nr, nf, rs, pp = (w[:, :, 8 + k][live].sum() for k in range(8))
-            gr = w[:, :, 3][live].sum()  # the per-group restaging (stamp word 3)
+            bw = w[:, :, 3][live].sum()  # the wait at the super tiles' barriers (stamp word 3)
             loop = ph["loop"][live].sum()
             rec["round_split"] = {
                 "rounds_per_wave": float(nr / live.sum()), "fired_share": float(nf / max(1, nr)),
@@ -76,11 +78,12 @@ def main():
                                      "last_mfma_to_test": float(rt / nr), "firing_path": float(rf / nr)},
                 "loop_share": {"to_first_mfma": float(rb / loop), "first_to_last_mfma": float(rm / loop),
                                "last_mfma_to_test": float(rt / loop), "firing_path": float(rf / loop),
-                               "restaging": float(rs / loop), "group_restaging": float(gr / loop),
-                               "pair_setup": float(pp / loop),
-                               "other": float(1 - (rb + rm + rt + rf + rs + gr + pp) / loop)},
-                "cycles_mean_per_wave": {"restaging": float(rs / live.sum()),
-                                         "group_restaging": float(gr / live.sum())},
+                               "restaging": float(rs / loop), "pair_setup": float(pp / loop),
+                               "other": float(1 - (rb + rm + rt + rf + rs + pp) / loop)},
+                # (the first super tile's barriers lie in the staging phase, the others' in `restaging`)
+                "barrier_wait": {"cycles_mean_per_wave": float(bw / live.sum()),
+                                 "of_staging_and_loop": float(bw / (loop + ph["staging"][live].sum()))},
+                "cycles_mean_per_wave": {"restaging": float(rs / live.sum())},
             }
         out["launches"].append(rec)
     if len(sys.argv) > 2:
