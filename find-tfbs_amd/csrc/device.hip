@@ -86,11 +86,8 @@ struct tfbs_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t evk0 = nullptr, evk1 = nullptr;  // around the dominant kernel (the MFMA launches)
-    // the per-depth MFMA launches run on kSide + 1 streams so that they overlap
-    static constexpr int kSide = 3;
-    hipStream_t side[kSide] = {};
-    hipEvent_t fork = nullptr, join[kSide] = {};
-    hipEvent_t kf_fork = nullptr, kf_join = nullptr;  // the big-region key assembly on side[0]
+    hipStream_t side = nullptr;                       // the big-region key assembly's stream,
+    hipEvent_t kf_fork = nullptr, kf_join = nullptr;  // forked from and joined to `stream`
     bool kernel_timed = false;
     float last_kernel_ms = 0.f;
     const Patterns *pats = nullptr;
@@ -122,16 +119,10 @@ struct tfbs_ctx {
     bool over_pending = false;
     bool over_copied = false;  // the last scan's overflow counters copied to over_host
     bool post_done = false;              // the last scan's overflow candidates were rescored (launch_post_scan)
-    HitSrc srcs_host[kMaxHitSrcs] = {};
-    HitSrc srcs_dev[kMaxHitSrcs] = {};   // what srcs holds (copied from here: stable while the copy runs)
-    bool srcs_on_dev = false;
     ScanArgs last_margs{};               // the last matrix-core scan's arguments (launch_post_scan)
-    uint32_t n_srcs = 0;
-    DevBuf<HitSrc> srcs;
     bool debug_over = false;  // TFBS_DEBUG_OVER: print the overflow lists' fill after each check
     uint32_t n_regions = 0;                // of the resident batch
-    uint32_t cand_cap = 1024;            // per scan workgroup (TFBS_CAND_CAP), per super tile it scans
-    bool mfma_merged = true;             // TFBS_SCAN_MERGED=0: one launch per depth class (a workgroup per super tile)
+    uint32_t cand_cap = 1024;            // per haplotype group (TFBS_CAND_CAP), per super tile it is scanned against
     uint32_t scan_cand_cap = 1024;       // the last scan's list entries per workgroup (ScanArgs::cand_cap)
     uint32_t scan_hit_cap = 1024;        // and its hit list entries per workgroup (ScanArgs::hit_cap)
     DevBuf<DevMSuper> m_supers;
@@ -139,7 +130,7 @@ struct tfbs_ctx {
     uint32_t mfma_lds = 44 * 1024;  // LDS image budget of one MFMA super tile
     uint32_t mfma_hpb = 64;         // haplotypes per MFMA workgroup
     uint32_t mfma_group_words = 0;  // packed words of the largest haplotype group (LDS staging)
-    // the merged scan's unit, groups per workgroup (ScanArgs::unit): TFBS_SCAN_UNIT = 1, 2, 4
+    // the scan's unit, groups per workgroup (ScanArgs::unit): TFBS_SCAN_UNIT = 1, 2, 4
     // forces it, 0 / unset: chosen per batch (scan_unit_for); scan_unit: the resident batch's
     uint32_t scan_unit_env = 0, scan_unit = 1;
     uint32_t wl_n_haps = 0;               // haplotypes the resident window lists were built for
@@ -156,7 +147,7 @@ struct tfbs_ctx {
     DevBuf<uint32_t> wl[2];
     DevBuf<uint16_t> wl16[2];  // the narrow groups' window lists
     DevBuf<uint8_t> gnarrow;   // per haplotype group of mfma_hpb: every haplotype <= kWlNarrowLen bases
-    DevBuf<uint32_t> gorder;   // the merged scan's group order (most work first; TFBS_SCAN_LPT=0: none)
+    DevBuf<uint32_t> gorder;   // the scan's group order (most work first; TFBS_SCAN_LPT=0: none)
     DevBuf<uint32_t> gcost;    // (its per-group work estimates)
     bool wl_any_narrow = false, wl_any_wide = false;  // the resident batch has narrow / other groups
     DevBuf<uint4> hd, hd2;     // the matrix-core scan's compact haplotype descriptors
@@ -220,7 +211,7 @@ struct tfbs_ctx {
     uint32_t bg_crc_full = 0;         // bgzf_crc_tables' full-block CRC init term
     DevBuf<uint64_t> kf_prof;         // TFBS_KF_PROF: key_fast_kernel phase clocks and sizes per region
     DevBuf<uint32_t> bg_check;  // TFBS_BGZF_CHECK=1: the checked BGZF wave kernel's violation count
-    DevBuf<unsigned long long> scan_prof;  // TFBS_SCAN_PROF=<file>: scan_mfma_kernel's per-wave stamps (prof builds)
+    DevBuf<unsigned long long> scan_prof;  // TFBS_SCAN_PROF=<file>: scan_mfma_all_kernel's per-wave stamps (prof builds)
     DevBuf<uint32_t> asm_order;       // the resident batch's regions by distinct haplotypes, most first
     uint32_t asm_order_n = 0;         // regions asm_order holds (0: none)
     uint32_t asm_order_big = 0;       // the first of them with more than key_fast_big_u() haplotypes
@@ -352,7 +343,7 @@ static int env_int(const char *name, int dflt) {
     return atoi(v);
 }
 
-// The merged scan's unit for a batch of n_groups haplotype groups (ScanArgs::unit): a
+// The scan's unit for a batch of n_groups haplotype groups (ScanArgs::unit): a
 // unit pays a super tile image's staging once for its G groups and hands their window
 // pairs to its waves from one pool, but G times fewer workgroups fill the chip worse --
 // the largest G of 4, 2, 1 whose units still give the chip's workgroup slots (two per
@@ -364,7 +355,6 @@ static int env_int(const char *name, int dflt) {
 // or four neither gained nor lost there beyond the runs' spread).
 constexpr uint32_t kUnitPairs = 2 * kMBlockWaves;
 static uint32_t scan_unit_for(const tfbs_ctx *ctx, uint32_t n_groups) {
-    if (!ctx->mfma_merged) return 1;
     if (ctx->scan_unit_env) return ctx->scan_unit_env;
     for (int c = 0; c < 2; c++)
         if (ctx->wl_entries[c] > (uint64_t)kUnitPairs * 64 * n_groups) return 1;
@@ -376,7 +366,7 @@ static uint32_t scan_unit_for(const tfbs_ctx *ctx, uint32_t n_groups) {
 // The matrix-core window lists of the haplotypes just put on the device (one
 // per depth class the plan has; scan.hpp build_window_lists).
 // B: the batch whose haplotypes they are -- its windows are shared among the region's
-// haplotypes (scan_mfma.hip "Shared windows") unless TFBS_SHARE=0, read here --, or
+// haplotypes (window_lists.hip "Shared windows") unless TFBS_SHARE=0, read here --, or
 // null (a single haplotype: nothing to share).
 static int build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t> &narrow, Batch *B = nullptr) {
     const Plan &P = ctx->plan;
@@ -477,7 +467,7 @@ static int build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t
     }
     for (int c = 0; c < 2; c++)
         if (!lmin[c]) ctx->wl_off[c].release(), ctx->wl[c].release(), ctx->wl16[c].release();
-    // The merged scan's workgroup order: groups by descending work (window pairs x the
+    // The scan's workgroup order: groups by descending work (window pairs x the
     // per-pair MFMAs + rounds of each depth class's super tiles), so that the launch
     // ends on its smallest groups instead of a late large one (LPT).
     ctx->gorder.release();
@@ -548,7 +538,6 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
     a.hits_wpp = hits_wpp;
     a.n_patterns_total = (uint32_t)ctx->pats->pats.size();
     int launches = 0;
-    ctx->n_srcs = 0;
     if (!P.m_supers.empty()) {  // sparse hits: no count matrix to zero
         ScanArgs m = a;
         m.msupers = ctx->m_supers.p;
@@ -557,20 +546,16 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
         m.mweights = ctx->m_weights.p;
         m.mmeta = ctx->m_meta.p;
         m.haps_per_block = ctx->mfma_hpb;
-        // one candidate list and one hit list per scan workgroup (super tile x haplotype
-        // group; merged: one workgroup per group scans every super tile, its lists hold
-        // their candidates)
+        // one candidate list and one hit list per haplotype group (a workgroup scans its
+        // groups against every super tile: their lists hold the candidates of all of them)
         const uint64_t n_groups = (n_haps + ctx->mfma_hpb - 1) / ctx->mfma_hpb;
-        const uint64_t n_wg = ctx->mfma_merged ? n_groups : (uint64_t)P.m_supers.size() * n_groups;
-        const uint32_t cand_cap = ctx->mfma_merged
-                                      ? (uint32_t)std::min<uint64_t>(1u << 16, (uint64_t)ctx->cand_cap * P.m_supers.size())
-                                      : ctx->cand_cap;
+        const uint32_t cand_cap = (uint32_t)std::min<uint64_t>(1u << 16, (uint64_t)ctx->cand_cap * P.m_supers.size());
         // (shared windows: a donor's wave lists its sharers' pairs too -- at C3 a per-wave share
         // of cand_cap / 8 sent 152 000 of 4.27 M pairs to the spill list)
         const uint32_t hit_cap = (uint32_t)std::min<uint64_t>(1u << 16, (uint64_t)cand_cap * (ctx->wl_share ? 4 : 1));
         int rc;
-        if ((rc = ctx->cands.ensure(n_wg * cand_cap * kCandWords)) || (rc = ctx->hitl.ensure(n_wg * hit_cap * 2)) ||
-            (rc = ctx->hitn.ensure(n_wg * (kMBlockWaves))) || (rc = ctx->candn.ensure(n_wg * (kMBlockWaves))))
+        if ((rc = ctx->cands.ensure(n_groups * cand_cap * kCandWords)) || (rc = ctx->hitl.ensure(n_groups * hit_cap * 2)) ||
+            (rc = ctx->hitn.ensure(n_groups * (kMBlockWaves))) || (rc = ctx->candn.ensure(n_groups * (kMBlockWaves))))
             return rc;
         m.cands = ctx->cands.p;
         m.cand_cap = cand_cap;
@@ -589,8 +574,8 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
             return rc;
         m.dedup = 1;
         m.gnarrow = ctx->gnarrow.n ? ctx->gnarrow.p : nullptr;
-        m.gorder = ctx->mfma_merged && ctx->gorder.n ? ctx->gorder.p : nullptr;
-        m.unit = ctx->mfma_merged ? ctx->scan_unit : 1;  // (gorder holds units of as many groups)
+        m.gorder = ctx->gorder.n ? ctx->gorder.p : nullptr;
+        m.unit = ctx->scan_unit;  // (gorder holds units of as many groups)
         m.unit_words = ctx->scan_unit_words_env;
         m.hd = ctx->hd.p;
         m.hd2 = ctx->hd2.p;
@@ -605,7 +590,7 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
         m.cand_over_cap = ctx->cand_over_cap;
         static const char *prof_path = getenv("TFBS_SCAN_PROF");
         if (prof_path && *prof_path) {
-            if ((rc = ctx->scan_prof.ensure(n_wg * kMBlockWaves * kScanProfWords))) return rc;
+            if ((rc = ctx->scan_prof.ensure(n_groups * kMBlockWaves * kScanProfWords))) return rc;
             HIP_TRY(hipMemsetAsync(ctx->scan_prof.p, 0, ctx->scan_prof.n * 8, ctx->stream));
             m.prof = ctx->scan_prof.p;
         }
@@ -629,7 +614,7 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
         // (tfbs_step) would launch it lean: neither the grid-wide bucketing nor overflow
         // candidates last time (it handles both anyway: too many spill records set
         // need_wide, and the assembly reruns with the wide kernels)
-        ctx->post_fused = ctx->post_fuse_ok && ctx->post_fuse_env && ctx->mfma_merged && ctx->asm_lean_mode != 0 &&
+        ctx->post_fused = ctx->post_fuse_ok && ctx->post_fuse_env && ctx->asm_lean_mode != 0 &&
                           !ctx->asm_full && (ctx->asm_lean_mode == 2 || ctx->prev_spill <= kPostSerial) &&
                           ctx->prev_cand == 0;
         if (ctx->post_fused) {
@@ -642,30 +627,9 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
             m.post_need_wide = ctx->asm_ctr.p + 20;
         }
         if (!ctx->capturing) HIP_TRY(hipEventRecord(ctx->evk0, ctx->stream));
-        // one stream per depth launch (launch_mfma: one per K depth), side streams
-        // forked and joined only when there is more than one (small batches: no
-        // cross-stream waits)
-        int n_depths = 0;
-        for (size_t k = 0; k < P.m_supers.size(); k++)
-            n_depths += (k == 0 || P.m_supers[k].nk != P.m_supers[k - 1].nk) ? 1 : 0;
-        if (ctx->mfma_merged) n_depths = 1;  // one launch
-        const int n_side = std::min(n_depths - 1, (int)tfbs_ctx::kSide);
-        hipStream_t streams[tfbs_ctx::kSide + 1] = {ctx->stream};
-        if (n_side > 0) HIP_TRY(hipEventRecord(ctx->fork, ctx->stream));
-        for (int i = 0; i < n_side; i++) {
-            HIP_TRY(hipStreamWaitEvent(ctx->side[i], ctx->fork, 0));
-            streams[i + 1] = ctx->side[i];
-        }
-        const int n = ctx->mfma_merged
-                          ? launch_mfma_all(m, P.m_supers.data(), (uint32_t)P.m_supers.size(), ctx->mfma_group_words,
-                                            n_haps, ctx->stream, ctx->srcs_host, &ctx->n_srcs)
-                          : launch_mfma(m, P.m_supers.data(), (uint32_t)P.m_supers.size(), ctx->mfma_group_words,
-                                        n_haps, streams, (uint32_t)n_side + 1, ctx->srcs_host, &ctx->n_srcs);
+        const int n = launch_mfma_all(m, P.m_supers.data(), (uint32_t)P.m_supers.size(), ctx->mfma_group_words, n_haps,
+                                      ctx->stream);
         if (n < 0) return n;
-        for (int i = 0; i < n_side; i++) {
-            HIP_TRY(hipEventRecord(ctx->join[i], ctx->side[i]));
-            HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->join[i], 0));
-        }
         if (!ctx->capturing) HIP_TRY(hipEventRecord(ctx->evk1, ctx->stream));
         ctx->kernel_timed = true;
         launches += n;
@@ -674,11 +638,11 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
             HIP_TRY(hipStreamSynchronize(ctx->stream));
             HIP_TRY(hipMemcpy(h.data(), ctx->scan_prof.p, h.size() * 8, hipMemcpyDeviceToHost));
             if (FILE *f = fopen(prof_path, "ab")) {
-                unsigned long long hdr[2] = {ctx->n_srcs, h.size()};
+                unsigned long long hdr[2] = {(unsigned long long)n, h.size()};
                 fwrite(hdr, 8, 2, f);
-                for (uint32_t i = 0; i < ctx->n_srcs; i++) {
-                    const HitSrc &q = ctx->srcs_host[i];
-                    unsigned long long v[5] = {q.wg_base, q.ns, q.g0, q.ng, i};  // launches: deepest class first
+                for (uint64_t i = 0, g0 = 0; g0 < n_groups; i++, g0 += kMLaunchGroups) {
+                    // one row per launch: its first list slot, lists per group, first group, groups
+                    unsigned long long v[5] = {g0, 1, g0, std::min<uint64_t>(kMLaunchGroups, n_groups - g0), i};
                     fwrite(v, 8, 5, f);
                 }
                 fwrite(h.data(), 8, h.size(), f);
@@ -687,14 +651,6 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
         }
         ctx->last_margs = m;  // the overflow candidates are rescored when the results are read (check_overflow)
         ctx->post_done = false;
-        if ((rc = ctx->srcs.ensure(kMaxHitSrcs))) return rc;
-        if (!ctx->srcs_on_dev || memcmp(ctx->srcs_dev, ctx->srcs_host, sizeof(ctx->srcs_host)) != 0) {
-            // (a rescan of the same batch launches the same workgroups: no copy)
-            memcpy(ctx->srcs_dev, ctx->srcs_host, sizeof(ctx->srcs_host));
-            HIP_TRY(hipMemcpyAsync(ctx->srcs.p, ctx->srcs_dev, sizeof(ctx->srcs_dev), hipMemcpyHostToDevice,
-                                   ctx->stream));
-            ctx->srcs_on_dev = true;
-        }
         // the overflow counters are checked before the results are read: by the
         // assembly's list pass, or by check_overflow (which copies them back first)
         ctx->over_pending = true;
@@ -810,9 +766,7 @@ static AsmArgs asm_args(tfbs_ctx *ctx, const Batch &B, int mode) {
     a.hitl = ctx->hitl.p;
     a.hitn = ctx->hitn.p;
     a.cand_cap = ctx->scan_hit_cap;  // (the hit lists' geometry)
-    a.srcs = ctx->srcs.p;
     a.mfma = ctx->plan.m_supers.empty() ? 0 : 1;
-    a.n_srcs = a.mfma ? ctx->n_srcs : 0;
     a.ref_hits = ctx->ref_hits.p;
     a.ref_count = ctx->ref_count.p;
     a.spill_sorted = ctx->spill_sorted.p;
@@ -873,7 +827,7 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     tfbs::effects_state_destroy(ctx->effects_state);
     ctx->effects_state = nullptr;
     ctx->ref_count.release(); ctx->spill.release(); ctx->over.release(); ctx->spill_sorted.release();
-    ctx->spill_bcnt.release(); ctx->spill_boff.release(); ctx->srcs.release();
+    ctx->spill_bcnt.release(); ctx->spill_boff.release();
     if (ctx->over_host) (void)hipHostFree(ctx->over_host);
     if (ctx->asm_host) (void)hipHostFree(ctx->asm_host);
     if (ctx->asm_ev) (void)hipEventDestroy(ctx->asm_ev);
@@ -918,14 +872,10 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     if (ctx->evk0) (void)hipEventDestroy(ctx->evk0);
     if (ctx->evk1) (void)hipEventDestroy(ctx->evk1);
     if (ctx->over_ev) (void)hipEventDestroy(ctx->over_ev);
-    for (int i = 0; i < tfbs_ctx::kSide; i++) {
-        if (ctx->side[i]) (void)hipStreamSynchronize(ctx->side[i]);
-        if (ctx->side[i]) (void)hipStreamDestroy(ctx->side[i]);
-        if (ctx->join[i]) (void)hipEventDestroy(ctx->join[i]);
-    }
+    if (ctx->side) (void)hipStreamSynchronize(ctx->side);
+    if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->step_exec) (void)hipGraphExecDestroy(ctx->step_exec);
     if (ctx->step_graph) (void)hipGraphDestroy(ctx->step_graph);
-    if (ctx->fork) (void)hipEventDestroy(ctx->fork);
     if (ctx->kf_fork) (void)hipEventDestroy(ctx->kf_fork);
     if (ctx->kf_join) (void)hipEventDestroy(ctx->kf_join);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -948,7 +898,6 @@ int tfbs_ctx_create(int device, const tfbs_patterns *p, tfbs_ctx **out) {
     ctx->mfma_lds = (uint32_t)std::min(144, std::max(8, env_int("TFBS_MFMA_LDS_KB", 44))) * 1024u;
     ctx->mfma_hpb = (uint32_t)std::min((int)kMMaxHapsPerBlock, std::max(4, env_int("TFBS_MFMA_HAPS_PER_BLOCK", 64)));  // 6 bits in a window list entry
     ctx->cand_cap = (uint32_t)std::min(1 << 16, std::max(64, env_int("TFBS_CAND_CAP", 1024)));
-    ctx->mfma_merged = env_int("TFBS_SCAN_MERGED", 1) != 0;
     {
         const int u = env_int("TFBS_SCAN_UNIT", 0);
         ctx->scan_unit_env = u == 1 || u == 2 || u == 4 ? (uint32_t)u : 0u;
@@ -973,7 +922,6 @@ int tfbs_ctx_create(int device, const tfbs_patterns *p, tfbs_ctx **out) {
     opt.tile_blocks = ctx->tile_blocks;
     opt.mfma = ctx->mfma;
     opt.mfma_lds_bytes = ctx->mfma_lds;
-    if (env_int("TFBS_MFMA_LDS_BY_DEPTH", 0)) mfma_depth_budgets(opt.mfma_lds_by_nk);
     rc = ctx->pats->build_plan(opt, &ctx->plan);
     if (rc) {
         delete ctx;
@@ -989,17 +937,13 @@ int tfbs_ctx_create(int device, const tfbs_patterns *p, tfbs_ctx **out) {
     if (e == hipSuccess) e = hipEventCreate(&ctx->ev1);
     if (e == hipSuccess) e = hipEventCreate(&ctx->evk0);
     if (e == hipSuccess) e = hipEventCreate(&ctx->evk1);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->kf_fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->kf_join, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->over_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->asm_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreate(&ctx->asm_t0);
     if (e == hipSuccess) e = hipEventCreate(&ctx->asm_t1);
-    for (int i = 0; i < tfbs_ctx::kSide; i++) {
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->side[i], hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->join[i], hipEventDisableTiming);
-    }
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking);
     int n_cus = 0;
     if (e == hipSuccess) e = hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) {
@@ -1101,7 +1045,7 @@ int tfbs_ctx_scan_counters(tfbs_ctx *ctx, uint64_t out[5]) {
     out[1] = ov[1];
     // (the waves of every slot the last scan launched; a unit's groups share each wave's
     // candidate lists: the LDS list's room once, the global list's once per group)
-    const size_t G = ctx->mfma_merged ? std::max<size_t>(1, ctx->last_margs.unit) : 1, ns = nw / kMBlockWaves;
+    const size_t G = std::max<size_t>(1, ctx->last_margs.unit), ns = nw / kMBlockWaves;
     for (size_t s0 = 0; s0 < ns; s0 += G) {
         const size_t ngu = std::min(G, ns - s0);
         const uint64_t cap = (uint64_t)ngu * (ctx->scan_cand_cap / kMBlockWaves), lcap = std::min<uint64_t>(cap, kMWaveCands);
@@ -1344,7 +1288,7 @@ static int enqueue_assembly(tfbs_ctx *ctx, Batch &B, bool post) {
         HIP_TRY(hipMemsetAsync(ctx->kf_prof.p, 0, (size_t)nr * 128, ctx->stream));
         a.prof = ctx->kf_prof.p;
     }
-    if ((rc = launch_key_fast(a, nr, a.order ? ctx->asm_order_big : 0, ctx->stream, ctx->side[0], ctx->kf_fork,
+    if ((rc = launch_key_fast(a, nr, a.order ? ctx->asm_order_big : 0, ctx->stream, ctx->side, ctx->kf_fork,
                               ctx->kf_join, ctx->asm_leftover)) ||
         (nr == 0 && (rc = launch_asm_report(a.report_src, ctx->asm_ctr.p, ctx->stream))))
         return rc;
@@ -1420,13 +1364,13 @@ static int kf_prof_report(tfbs_ctx *ctx, uint32_t nr) {
             if (h[(size_t)r * 16 + 6]) ev.push_back({{h[(size_t)r * 16 + 14], h[(size_t)r * 16]}, r});
         std::sort(ev.begin(), ev.end());
         double gap = 0, late = 0, early_end = 0;
-        uint32_t n_gap = 0, n_wg = 0;
+        uint32_t n_gap = 0, n_groups = 0;
         for (size_t i = 0; i < ev.size(); i++) {
             const uint64_t *p = &h[(size_t)ev[i].second * 16];
             const bool first = i == 0 || ev[i - 1].first.first != ev[i].first.first;
             const bool last = i + 1 == ev.size() || ev[i + 1].first.first != ev[i].first.first;
             if (first) {
-                n_wg++;
+                n_groups++;
                 late += (double)(p[0] - t_lo_all(h, nr));
             } else {
                 gap += (double)(p[0] - h[(size_t)ev[i - 1].second * 16 + 6]);
@@ -1434,10 +1378,10 @@ static int kf_prof_report(tfbs_ctx *ctx, uint32_t nr) {
             }
             if (last) early_end += (double)(t_hi_all(h, nr) - p[6]);
         }
-        if (n_wg)
+        if (n_groups)
             fprintf(stderr, "[kf prof] %u workgroups: mean gap between a workgroup's regions %.1f us (%u gaps), first "
                             "region start after the kernel's first %.1f us, last end before the kernel's last %.1f us\n",
-                    n_wg, n_gap ? gap / n_gap / 100.0 : 0.0, n_gap, late / n_wg / 100.0, early_end / n_wg / 100.0);
+                    n_groups, n_gap ? gap / n_gap / 100.0 : 0.0, n_gap, late / n_groups / 100.0, early_end / n_groups / 100.0);
     }
     uint32_t early = 0;  // regions started in the first 10 us: the workgroups resident at the start
     for (uint32_t r = 0; r < nr; r++)
@@ -1571,7 +1515,7 @@ static uint64_t step_signature(const tfbs_ctx *ctx, const tfbs_batch *b) {
     mix(ctx->upload_gen);
     buf(ctx->cands); buf(ctx->hitl); buf(ctx->hitn); buf(ctx->candn); buf(ctx->ref_hits); buf(ctx->ref_count); buf(ctx->spill);
     buf(ctx->over); buf(ctx->spill_sorted); buf(ctx->spill_bcnt); buf(ctx->spill_boff); buf(ctx->cand_over);
-    buf(ctx->srcs); buf(ctx->words); buf(ctx->nmask); buf(ctx->counts); buf(ctx->posrel); buf(ctx->inner);
+    buf(ctx->words); buf(ctx->nmask); buf(ctx->counts); buf(ctx->posrel); buf(ctx->inner);
     buf(ctx->haps); buf(ctx->druns); buf(ctx->gnarrow); buf(ctx->gorder); buf(ctx->hd); buf(ctx->hd2); buf(ctx->regions);
     buf(ctx->hits); buf(ctx->asm_scratch); buf(ctx->key_first); buf(ctx->var_counts); buf(ctx->asm_redo);
     buf(ctx->asm_ctr); buf(ctx->cor_arena); buf(ctx->key_flags); buf(ctx->var_keys); buf(ctx->asm_order);
@@ -1587,7 +1531,7 @@ static uint64_t step_signature(const tfbs_ctx *ctx, const tfbs_batch *b) {
     for (uint64_t v : {(uint64_t)ctx->spill_cap, (uint64_t)ctx->cand_over_cap, (uint64_t)ctx->cand_cap,
                        (uint64_t)ctx->scan_cand_cap, (uint64_t)ctx->scan_hit_cap, (uint64_t)ctx->var_keys_cap, ctx->var_cap,
                        (uint64_t)ctx->cor_cap, (uint64_t)ctx->n_regions, (uint64_t)ctx->asm_order_n,
-                       (uint64_t)ctx->asm_order_big, (uint64_t)ctx->n_srcs, (uint64_t)ctx->srcs_on_dev,
+                       (uint64_t)ctx->asm_order_big,
                        (uint64_t)ctx->counts_live, (uint64_t)ctx->mfma_group_words,
                        (uint64_t)(uintptr_t)ctx->var_owner, (uint64_t)ctx->asm_lean_mode,
                        (uint64_t)(ctx->prev_spill <= kPostSerial), (uint64_t)(ctx->prev_redo == 0),

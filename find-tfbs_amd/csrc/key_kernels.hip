@@ -72,29 +72,23 @@ __device__ __forceinline__ uint4 make_ref(const AsmArgs &A, const DevRegion &rg,
     return make_uint4(key0, i, L | (dk << 16), ref_overlaps(A, rg, L, i, 0, min(rg.n_inner, 32u)));
 }
 
-// Every own hit (local haplotype l < U, key) of region r: the workgroup lists of the
-// matrix-core launches (one wave per list), then the region's spill records.
+// Every own hit (local haplotype l < U, key) of region r: the wave lists of the
+// region's haplotype groups (group g's are lists g * kMBlockWaves .. + 7, scan.hpp; one
+// wave per list), then the region's spill records.
 template <class F>
 __device__ __forceinline__ void visit_hits(const AsmArgs &A, uint32_t r, uint32_t hb, uint32_t U, F &&f) {
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t g_lo = hb / A.hpb, g_hi = (hb + U - 1) / A.hpb;
-    for (uint32_t si = 0; si < A.n_srcs; si++) {
-        const HitSrc src = A.srcs[si];
-        const uint32_t ga = max(g_lo, src.g0), gb = min(g_hi + 1, src.g0 + src.ng);
-        if (ga >= gb) continue;
-        const uint32_t per_g = src.ns * kMBlockWaves, n_l = (gb - ga) * per_g;
-        for (uint32_t li = wave; li < n_l; li += kAsmWaves) {
-            const uint32_t g = ga + li / per_g, rem = li % per_g;
-            const uint32_t wg = src.wg_base + (g - src.g0) * src.ns + rem / kMBlockWaves, w = rem % kMBlockWaves;
-            const uint32_t n = A.hitn[(size_t)wg * kMBlockWaves + w];
-            const uint2 *lst = reinterpret_cast<const uint2 *>(A.hitl) + (size_t)wg * A.cand_cap +
-                               (size_t)w * (A.cand_cap / kMBlockWaves);
+    if (A.mfma)
+        for (uint32_t li = g_lo * kMBlockWaves + wave; li < (g_hi + 1) * kMBlockWaves; li += kAsmWaves) {
+            const uint32_t n = A.hitn[li];
+            const uint2 *lst = reinterpret_cast<const uint2 *>(A.hitl) + (size_t)(li / kMBlockWaves) * A.cand_cap +
+                               (size_t)(li % kMBlockWaves) * (A.cand_cap / kMBlockWaves);
             for (uint32_t e = lane; e < n; e += 64) {
                 const uint2 h = lst[e];
                 if (h.x - hb < U) f(h.x - hb, h.y);
             }
         }
-    }
     const uint2 sp = spill_range(A, r);
     for (uint32_t e = sp.x + threadIdx.x; e < sp.y; e += kAsmBlock) {
         const uint32_t *q = A.spill_sorted + 3 * (size_t)e;
@@ -596,31 +590,12 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             }
         }
     }
-    // own hits: the scan workgroups' lists over the region's haplotype groups (one
-    // hitn load per thread), their entries read flat over the workgroup below
-    uint32_t nl = 0;
+    // own hits: the wave lists of the region's haplotype groups (one hitn load per
+    // thread), their entries read flat over the workgroup below
     const uint32_t g_lo = hb / A.hpb, g_hi = (hb + U - 1) / A.hpb;
-    if (A.mfma)
-        for (uint32_t si = 0; si < A.n_srcs; si++) {
-            const HitSrc src = A.srcs[si];
-            const uint32_t ga = max(g_lo, src.g0), gb = min(g_hi + 1, src.g0 + src.ng);
-            if (ga < gb) nl += (gb - ga) * src.ns * kMBlockWaves;
-        }
-    auto list_idx = [&](uint32_t t) -> uint32_t {  // list t of the region's: its wave list (wg x 8 + wave)
-        for (uint32_t si = 0; si < A.n_srcs; si++) {
-            const HitSrc src = A.srcs[si];
-            const uint32_t ga = max(g_lo, src.g0), gb = min(g_hi + 1, src.g0 + src.ng);
-            if (ga >= gb) continue;
-            const uint32_t per_g = src.ns * kMBlockWaves;
-            if (t < (gb - ga) * per_g) {
-                const uint32_t g = ga + t / per_g, rem = t % per_g;
-                const uint32_t wg = src.wg_base + (g - src.g0) * src.ns + rem / kMBlockWaves;
-                return wg * kMBlockWaves + rem % kMBlockWaves;
-            }
-            t -= (gb - ga) * per_g;
-        }
-        return 0;
-    };
+    const uint32_t nl = A.mfma ? (g_hi + 1 - g_lo) * kMBlockWaves : 0u;
+    // list t of the region's: group g's wave lists are g * kMBlockWaves .. + 7 (scan.hpp)
+    auto list_idx = [&](uint32_t t) -> uint32_t { return g_lo * kMBlockWaves + t; };
     uint32_t lcnt = 0, lidx = 0;  // the region's entries (an upper bound of its hits: groups are shared)
     for (uint32_t t = tid; t < nl; t += kFBlock) {
         const uint32_t i = list_idx(t);

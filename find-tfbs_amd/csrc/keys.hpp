@@ -24,8 +24,6 @@ struct AsmArgs {
     // the matrix-core launches' hit lists (ScanArgs::hitl / hitn)
     const uint32_t *hitl, *hitn;
     uint32_t cand_cap;
-    const HitSrc *srcs;
-    uint32_t n_srcs;
     uint32_t mfma;              // 0: the matrix-core kernel did not run (no hit lists, no reference hits)
     // reference hits per region, and the spill records bucketed by region
     const uint32_t *ref_hits, *ref_count;

@@ -1,5 +1,5 @@
 // Matrix-core plan: pack PWM strands into 64-strand tiles of FP6 B fragments
-// (two strands per GEMM column) for scan_mfma_kernel (scan_mfma.hip).
+// (two strands per GEMM column) for scan_mfma_all_kernel (scan_mfma.hip).
 //
 // apply_pwm (pattern.rs:125-135) is score(i) = sum_j w[j][nuc(i + j)], N = 0.
 // With the window's bases one-hot encoded (4 entries per column, all zero for
@@ -222,7 +222,7 @@ void build_mfma_tiles(const Patterns &P, const std::vector<SlotGroup> &groups, c
     while (ti < tiles.size()) {
         // a super tile: consecutive tiles of one depth class within the LDS budget
         const uint32_t nk = mfma_depth_class(tiles[ti].nk);
-        const uint32_t lds_bytes = opt.mfma_lds_by_nk[nk] ? opt.mfma_lds_by_nk[nk] : opt.mfma_lds_bytes;
+        const uint32_t lds_bytes = opt.mfma_lds_bytes;
         // the run of tiles of this class, split into equal-sized super tiles
         size_t run = ti;
         uint64_t run_bytes = 0;

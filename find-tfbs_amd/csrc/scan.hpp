@@ -1,4 +1,5 @@
-// Launch interface of the scan kernels (scan_kernels.hip, scan_dinuc.hip, scan_mfma.hip), used by device.hip.
+// Launch interface of the scan kernels (scan_kernels.hip, scan_dinuc.hip, scan_mfma.hip) and of the
+// window-list builder (window_lists.hip), used by device.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -42,20 +43,23 @@ struct ScanArgs {
     uint32_t hits_wpp;
     uint32_t n_patterns_total;
     // matrix-core candidates (scan_mfma.hip): one region of cand_cap (strand |
-    // haplotype in the group << 24, window) pairs per scan workgroup (region
-    // region_base + blockIdx.x), an equal share per wave, each wave's filled and
-    // rescored by the wave (a unit of n groups: the n regions of its groups' slots as
-    // one, the haplotype counted from the unit's first)
+    // haplotype in the group << 24, window) pairs per haplotype group (region
+    // region_base + the group's index in the launch), an equal share per wave, each
+    // wave's filled and rescored by the wave (a unit of n groups: the n regions of its
+    // groups' slots as one, the haplotype counted from the unit's first)
     uint32_t *cands;  // kCandWords per entry
     uint32_t cand_cap;
     uint32_t region_base;
     // matrix-core hits, sparse (no count matrix, no atomics): the wave that
     // rescores its candidates appends one (haplotype, key = slot * n_inner +
     // range) pair per hit and overlapped inner range to its part of the
-    // workgroup's hit list (hitl + 2 (wg hit_cap + wave hit_cap / 8), the candidate
-    // list's geometry with hit_cap entries per workgroup: cand_cap, or four times that
+    // group's hit list (hitl + 2 (g hit_cap + wave hit_cap / 8), the candidate
+    // list's geometry with hit_cap entries per group: cand_cap, or four times that
     // when windows are shared -- a donor's wave lists its sharers' pairs too) and stores
-    // their number at hitn[8 wg + wave]; the excess goes to the spill list
+    // their number at hitn[8 g + wave]; the excess goes to the spill list.
+    // Invariant: wave list w of haplotype group g of the resident batch is list
+    // g * kMBlockWaves + w, in every launch (launch_mfma_all: region_base = the launch's
+    // first group); the key assembly (key_kernels.hip) reads a region's lists by that index
     uint32_t *hitl;
     uint32_t hit_cap;
     uint32_t *hitn;
@@ -127,7 +131,7 @@ struct ScanArgs {
     uint32_t post_regions;
     uint32_t *post_bcnt, *post_boff, *post_sorted, *post_report, *post_need_wide;
     // TFBS_SCAN_PROF builds of scan_mfma.hip (tools/variant_build.sh): per wave of
-    // workgroup region_base + blockIdx.x, kScanProfWords clock stamps and counts
+    // the workgroup's first list slot, kScanProfWords clock stamps and counts
     // (tools/scan_prof.py); null otherwise
     unsigned long long *prof;
 };
@@ -152,27 +156,17 @@ int fast_kernel_set_lds(const LaunchConfig &cfg);
 // like the fast kernel's; lds_bytes: the largest tile's blocks (dynamic LDS).
 int launch_dinuc(const ScanArgs &a, size_t lds_bytes, uint32_t n_haps, hipStream_t stream);
 int dinuc_kernel_set_lds(size_t lds_bytes);
-// The workgroups of one matrix-core launch: hap groups [g0, g0 + ng) x ns super
-// tiles, workgroup wg_base + (g - g0) ns + super; their hit lists are read back
-// per region by the key assembly (key_kernels.hip).
-struct HitSrc {
-    uint32_t wg_base, ns, g0, ng;
-};
-constexpr int kMaxHitSrcs = 64;
 constexpr uint32_t kMWaveCands = 48;  // a scan wave's candidates kept in LDS before its global list
 // Matrix-core scan (scan_mfma.hip): sparse hits (hitl / hitn / spill), no counts.
 // group_words: the most packed words any haplotype group of haps_per_block spans.
-// One launch per K depth, spread round-robin over `streams` (deepest first);
-// supers: the host copy of a.msupers (sorted by depth); srcs receives one
-// HitSrc per launch (*n_srcs of kMaxHitSrcs).
-int launch_mfma(const ScanArgs &a, const DevMSuper *supers, uint32_t n_supers, uint32_t group_words, uint32_t n_haps,
-                const hipStream_t *streams, uint32_t n_streams, HitSrc *srcs, uint32_t *n_srcs);
-// The same in one launch on `stream`: one workgroup per unit of a.unit haplotype groups
-// scans them against every super tile in turn (scan_mfma_all_kernel); one HitSrc with
-// ns = 1 (a list slot per group, whatever the unit).
+// supers: the host copy of a.msupers (sorted by depth).  One launch on `stream` (one per
+// kMLaunchGroups haplotype groups): one workgroup per unit of a.unit haplotype groups
+// scans them against every super tile in turn (scan_mfma_all_kernel); a list slot per
+// group, whatever the unit.  Returns launches issued or <0.
+constexpr uint64_t kMLaunchGroups = ((1ull << 31) - 1) / kMMaxUnit * kMMaxUnit;  // whole units per launch
 int launch_mfma_all(const ScanArgs &a, const DevMSuper *supers, uint32_t n_supers, uint32_t group_words, uint32_t n_haps,
-                    hipStream_t stream, HitSrc *srcs, uint32_t *n_srcs);
-// Rescores the candidates past the waves' lists (after launch_mfma on the same stream).
+                    hipStream_t stream);
+// Rescores the candidates past the waves' lists (after launch_mfma_all on the same stream).
 int launch_post_scan(const ScanArgs &a, hipStream_t stream);
 // The same (when cand) and the spill records' buckets by region (boff[0 .. n_regions],
 // sorted) in one launch; *done and bcnt[0 .. n_regions] must be zero.
@@ -239,9 +233,6 @@ int build_window_lists(const DevHap *haps, uint32_t n_haps, const uint32_t *drun
                        const uint32_t *words = nullptr, const ClassTab *tab = nullptr,
                        int (*ensure_share)(void *ctx, int c, uint64_t n, uint2 **p) = nullptr,
                        uint64_t shared[2] = nullptr, uint64_t listed[2][2] = nullptr);
-// Super tile image budgets per K depth (1-8) that let each depth's kernel reach
-// the waves per SIMD its registers allow.
-void mfma_depth_budgets(uint32_t out[9]);
 size_t mfma_lds_fixed();  // LDS bytes the MFMA kernel needs besides the image and words
 
 }  // namespace tfbs

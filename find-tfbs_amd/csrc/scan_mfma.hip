@@ -18,10 +18,12 @@
 //    [0, 2048) (mfma.cpp clips the digits so); U > T0 iff the field's top bit (10 or
 //    21) is set.  One OR tree over a lane's 16 outputs (v_or3 + v_bitop3) tests 32
 //    (window, strand) pairs.
-//  * A workgroup (8 waves) stages one super tile (tiles of 64 strands of equal
-//    K depth), the one-hot table, its group's haplotype descriptors and packed
-//    words in LDS.  Every digit fragment is one conflict-free ds_read_b128 +
-//    ds_read_b64 per lane and feeds two window tiles.
+//  * One kernel family, scan_mfma_all_kernel<STAGED, UNIT>, one launch per scan: a
+//    workgroup (8 waves) takes one haplotype group, or a unit of up to kMMaxUnit
+//    consecutive groups, and stages the one-hot table, the haplotype descriptors and
+//    (STAGED) packed words in LDS once, then every super tile (tiles of 64 strands of
+//    one depth class) in turn.  Every digit fragment is one conflict-free
+//    ds_read_b128 + ds_read_b64 per lane and feeds two window tiles.
 //  * Window tiles come from the group's window list (build_window_lists): 32
 //    listed windows of any of the group's haplotypes per tile, lane l & 31 its
 //    own (haplotype, window), so reference-window reuse leaves no holes.
@@ -34,16 +36,16 @@
 //    it rescores those exactly, one per lane (pattern.rs:125-151), applies the
 //    inner-range overlap test (range.rs:18-21 as main.rs:503 uses it) and appends
 //    one (haplotype, key) pair per hit and overlapped range to its part of the
-//    workgroup's hit list (no count matrix, no atomics: the key assembly,
+//    group's hit list (no count matrix, no atomics: the key assembly,
 //    key_kernels.hip, counts them per region); a full wave list spills to a
 //    launch-wide list rescored after the scan.
+//  * After the scan: the overflow candidates' rescoring and the spill records'
+//    bucketing by region (post_scan_kernel, or fused into the scan's last
+//    workgroup).  The window lists are built in window_lists.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <string>
-#include <vector>
 
 #include "scan.hpp"
 
@@ -60,9 +62,6 @@ static_assert(kMBlock / 64 == kMBlockWaves, "hit list parts per workgroup");
 constexpr int kMOnehotBytes = 2048;   // LDS: one-hot table (4-mer -> 4 x 16 bits of FP4), image, words
 constexpr uint32_t kMChunkBytes = 1536;  // one K chunk's B fragments of a 64-strand tile (dwords 0-3 | 4-5)
 constexpr uint32_t kMStagedMax = 80 * 1024;  // LDS per workgroup at 2 workgroups per CU (160 KiB)
-// waves per SIMD the depth kernels' registers allow (see mfma_depth_budgets)
-constexpr uint32_t kMfmaRegWaves[kMMaxChunks + 1] = {4, 4, 4, 4, 4};
-constexpr int kMfmaMinWaves[kMMaxChunks + 1] = {4, 4, 4, 4, 4};
 constexpr uint32_t kTestMask = (1u << (kMFieldBits - 1)) | (1u << (2 * kMFieldBits - 1));  // the fields' top bits
 constexpr uint32_t kQueueBits = 0x20200404u;  // those bits after queue_tile's byte permute (outputs 2j, 2j + 1)
 // e8m0 scales: the digits x 8 (K block 0), x 2^(3 + 11) (block 1: the field one up); the one-hot x 1
@@ -166,7 +165,7 @@ __device__ __forceinline__ v16f mfma_chunk(const v4i &a, const BFrag &f, const v
 // Candidate handling.  A firing lane (its window passed the coarse test for some
 // strand of the tile; ~40 % of the rounds have one) appends one record to its wave's
 // LDS queue (queue_tile): the fields' top bits of its 16 outputs (8 v_perm + 4
-// v_bitop3, 16 bytes), its own list entry (the window: s_went) and the tile's first
+// v_bitop3, 16 bytes), its own list entry (the window) and the tile's first
 // global strand | the lane.  The wave decodes its records in batches, one record per
 // lane (drain_queue, no global load), into (strand | haplotype in group << 24,
 // window) candidates: the first kWaveCands in LDS (s_cand), then the wave's region of
@@ -179,7 +178,6 @@ constexpr uint32_t kWaveCands = kMWaveCands;  // LDS candidates per wave (C3: 66
 __shared__ uint4 s_qdata[kMBlock / 64][kMQueue];
 __shared__ uint2 s_qmeta[kMBlock / 64][kMQueue];
 __shared__ uint2 s_cand[kMBlock / 64][kWaveCands];
-__shared__ uint32_t s_went[kMBlock / 64][64];  // per wave: the current pair's list entries (tile a | tile b)
 __shared__ uint32_t s_hnext;  // the workgroup's next pair of window tiles (scan_super)
 __shared__ uint4 s_hd[kMMaxHapsPerBlock];   // the group's haplotypes: LaneHap
 __shared__ uint4 s_hd2[kMMaxHapsPerBlock];  // and (region, pos_off, drun_off, n_druns) for the rescoring
@@ -356,8 +354,8 @@ __device__ __forceinline__ uint32_t score_candidate(const ScanArgs &A, const uin
 // A.hit_cap, rescore_list): the LDS list's (at most kWaveCands) followed by the wave's
 // region of the global list (TFBS_CAND_CAP makes all of them small in the spill tests).
 __device__ __forceinline__ uint32_t wave_cand_cap(const ScanArgs &A) { return A.cand_cap / (kMBlock / 64); }
-// slot: the workgroup's place in the per-workgroup lists (region_base + its
-// haplotype group in the merged kernel's launch; else + its index).  The wave's
+// slot: the workgroup's place in the per-group lists (region_base + its first
+// haplotype group in the launch = that group's index in the batch).  The wave's
 // global list in a unit of ngu groups whose first slot is `slot`: the groups' regions
 // are consecutive, each wave takes ngu x its share of one (ngu = 1: one workgroup's
 // region in eight parts).
@@ -479,28 +477,8 @@ __device__ __forceinline__ uint32_t coarse_test(const v16f &acc) {
     uint32_t u[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) u[r] = __float_as_uint(acc[r]);
-#ifdef TFBS_OR_TREE  // a tree of depth 3 (the compiler chains the ORs: depth 8); the empty
-                     // asm only hides the partial ORs from reassociation (no instruction)
-    uint32_t p[5] = {u[0] | u[1] | u[2], u[3] | u[4] | u[5], u[6] | u[7] | u[8], u[9] | u[10] | u[11],
-                     u[12] | u[13] | u[14]};
-#pragma unroll
-    for (int k = 0; k < 5; k++) asm volatile("" : "+v"(p[k]));
-    return ((p[0] | p[1] | p[2]) | (p[3] | p[4] | u[15])) & kTestMask;
-#endif
-#if defined(TFBS_AB_NOTEST) || defined(TFBS_AB_NOFIRE)
-    // timing ablations (wrong results): an opaque zero ends the test; NOTEST reads one
-    // accumulator (the MFMAs stay live), NOFIRE keeps the whole test and never fires
-    uint32_t z;
-    asm volatile("s_mov_b32 %0, 0" : "=s"(z));
-#ifdef TFBS_AB_NOTEST
-    return u[15] & z;
-#endif
-#endif
     const uint32_t x = (u[0] | u[1] | u[2]) | (u[3] | u[4] | u[5]) | (u[6] | u[7] | u[8]) | (u[9] | u[10] | u[11]) |
                        (u[12] | u[13] | u[14]) | u[15];
-#ifdef TFBS_AB_NOFIRE
-    return x & kTestMask & z;
-#endif
     return x & kTestMask;
 }
 
@@ -589,7 +567,7 @@ __device__ __forceinline__ void drain_queue(const ScanArgs &A, const GroupCtx &G
 // the list's nw entries being the last tile's padding; the queue has room for the
 // tile's records): each firing lane queues one record -- bytes 1-2 of its outputs
 // (the fields' top bits), its list entry (window row lane & 31 of window tile
-// `which`, s_went) and g0 | lane (g0: the strand tile's first global strand) --;
+// `which`, went) and g0 | lane (g0: the strand tile's first global strand) --;
 // qn (uniform) counts the wave's records.
 __device__ __forceinline__ void queue_tile(const ScanArgs &A, const GroupCtx &G, const v16f &acc, bool mine, uint64_t f,
                                            uint32_t g0, uint32_t went, uint32_t which, uint32_t lane, uint32_t wave,
@@ -597,11 +575,7 @@ __device__ __forceinline__ void queue_tile(const ScanArgs &A, const GroupCtx &G,
     const uint32_t nf = (uint32_t)__popcll(f);
     uint32_t ent = 0, x[4] = {0, 0, 0, 0};
     if (mine) {
-#ifdef TFBS_WENT_LDS  // (A/B: the round-6 first version's LDS copy of the pair's entries)
-        ent = s_went[wave][which * 32 + (lane & 31)];
-#else
         ent = went;  // the lane's own entry of tile `which` (lanes l and l + 32 load the same)
-#endif
         record_bits(acc, x);
     }
     if (__builtin_expect(qn + nf > kMQueue, 0)) {  // the queue is full (dense hits): decoded first
@@ -622,12 +596,10 @@ __device__ __forceinline__ void queue_tile(const ScanArgs &A, const GroupCtx &G,
 template <int D, int NK, bool TWO>
 __device__ __forceinline__ void round_scores(const char *tile, uint32_t lane, const BFrag &f0, const v4i (&a0)[NK],
                                              const v4i (&a1)[NK], const v16f &cb, int sa, v16f &c0, v16f &c1) {
-#ifndef TFBS_B_ALL
     if (D >= 3) {
         // depth 3-4 (the class whose A fragments take 32 VGPRs): chunk kc + 1's
         // fragment read as chunk kc's MFMAs issue, a scheduling barrier between the
-        // chunks -- two fragments live instead of D (no scratch spill in the merged
-        // kernel)
+        // chunks -- two fragments live instead of D (no scratch spill)
         BFrag cur = f0;
         c0 = cb;
         if (TWO) c1 = cb;
@@ -645,7 +617,6 @@ __device__ __forceinline__ void round_scores(const char *tile, uint32_t lane, co
         }
         return;
     }
-#endif
     BFrag f[D];
     f[0] = f0;
 #pragma unroll
@@ -724,9 +695,6 @@ __device__ __forceinline__ void scan_segment(const ScanArgs &A, const char *img,
 #else
         v16f c0, c1;
         round_scores<D, NK, TWO>(tile, lane, pf, a0, a1, cb, sa, c0, c1);
-#endif
-#ifdef TFBS_NO_READ2
-        asm volatile("" ::: "memory");  // (A/B) no ds_read2 merged with the round's reads: no v_mov copies
 #endif
         load_frag0(tile + kTB, lane, pf);
         const uint32_t x0 = coarse_test(c0), x1 = TWO ? coarse_test(c1) : 0u;
@@ -1021,9 +989,6 @@ __device__ __forceinline__ uint32_t scan_loop(const ScanArgs &A, const DevMSuper
         v4i a0[NK], a1[NK];
         entry_onehot<NK>(A, words, ea, tab, a0);
         entry_onehot<NK>(A, words, eb, tab, a1);  // (a copy of the last window when !two: unused)
-#ifdef TFBS_WENT_LDS
-        s_went[wave][lane] = lane < 32 ? ea : eb;  // the firing path's windows (queue_tile)
-#endif
         const uint32_t e0 = ea, e1 = eb;          // (the firing path's entries: the lane's own)
         if (pn < npair) entries(pn, ea, eb);      // in flight while this pair is scored
 #ifdef TFBS_ROUND_PROF
@@ -1098,50 +1063,6 @@ __device__ __forceinline__ const uint32_t *stage_unit_words(const ScanArgs &A, i
     return s_words - wbeg;
 }
 
-// Grid: n_msupers x ceil(n_haps / haps_per_block), 4 waves per SIMD (two workgroups per CU).
-// LDS: one-hot table | super tile image | (STAGED) the packed words of the
-// workgroup's haplotypes, copied once so that every window read is an LDS read.
-template <bool STAGED, int NK>
-__global__ __launch_bounds__(kMBlock, kMfmaMinWaves[NK]) void scan_mfma_kernel(ScanArgs A) {
-#ifdef TFBS_SCAN_PROF
-    const unsigned long long t_start = __builtin_amdgcn_s_memtime(), r_start = __builtin_amdgcn_s_memrealtime();
-#endif
-    int32_t *smem = s_mdyn;
-    const uint32_t sidx = blockIdx.x % A.n_msupers;
-    const uint32_t hg = blockIdx.x / A.n_msupers;
-    const uint32_t slot = A.region_base + blockIdx.x;
-    const DevMSuper S = A.msupers[sidx];
-    const uint32_t h0 = hg * A.haps_per_block;
-    const uint32_t hn = min(h0 + A.haps_per_block, A.n_haps) - h0;
-    stage_image(A, S, reinterpret_cast<uint4 *>(smem));
-    if (threadIdx.x == 0) s_hnext = 0;
-    stage_onehot(smem);
-    const uint32_t *words = stage_group<STAGED>(A, smem, h0, hn);
-    __syncthreads();
-    const char *s_img = reinterpret_cast<const char *>(smem) + kMOnehotBytes;
-    // the wave index is uniform: keep every group-level value in SGPRs
-    const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef TFBS_SCAN_PROF
-    SCAN_STAMP(0, t_start);
-    SCAN_STAMP(5, r_start);
-    SCAN_STAMP(1, __builtin_amdgcn_s_memtime());
-#endif
-    uint32_t qn = 0, cn = 0;
-    const uint32_t n_pairs = scan_loop<NK>(A, S, s_img, words, hg, slot, unit_place(0, 1), lane, wave, qn, cn);
-    (void)n_pairs;
-    SCAN_STAMP(2, __builtin_amdgcn_s_memtime());
-    rescore_list<false>(A, words, h0, slot, 1, wave, lane, cn);
-    SCAN_STAMP(4, __builtin_amdgcn_s_memtime());
-    SCAN_STAMP(6, __builtin_amdgcn_s_memrealtime());
-    SCAN_STAMP(7, (unsigned long long)n_pairs | ((unsigned long long)cn << 32));
-}
-
-// One workgroup per haplotype group for EVERY super tile (the depth classes in
-// turn): the group's words, descriptors and one-hot table are staged once, each
-// super tile's image in turn (a barrier on either side), and the wave rescores its
-// candidates of all of them once at the end -- the per-workgroup costs (staging,
-// the rescoring's dependent loads) are paid once per group instead of once per
-// super tile.  LDS: one-hot table | the largest image | (STAGED) words.
 }  // namespace
 // post_scan_kernel's work by one workgroup of NT threads (defined below); s_sum: NT + 1
 // words of LDS
@@ -1151,6 +1072,13 @@ __device__ void post_one_block(const ScanArgs &A, uint32_t tid, uint32_t n_regio
                                uint32_t *__restrict__ report, uint32_t *__restrict__ need_wide, uint32_t *s_sum);
 namespace {
 
+// One workgroup per haplotype group for EVERY super tile (the depth classes in
+// turn): the group's words, descriptors and one-hot table are staged once, each
+// super tile's image in turn (a barrier on either side), and the wave rescores its
+// candidates of all of them once at the end -- the per-workgroup costs (staging,
+// the rescoring's dependent loads) are paid once per group, not once per super
+// tile.  Grid: one workgroup per group (unit), 4 waves per SIMD (two workgroups per
+// CU).  LDS: one-hot table | the largest image | (STAGED) words.
 // UNIT: the workgroup's haplotypes are a unit of A.unit consecutive groups (the
 // last unit may be short).  The one-hot table, the unit's descriptors (s_hdu) and, where
 // the host gave them room (STAGED, A.unit_lds groups), the packed words of the unit's
@@ -1185,9 +1113,6 @@ __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
     }
     const char *s_img = reinterpret_cast<const char *>(smem) + kMOnehotBytes;
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef TFBS_SETPRIO
-    if (wave >= 4) __builtin_amdgcn_s_setprio(1);  // (A/B) the workgroup's second half wins issue ties
-#endif
     uint32_t qn = 0, cn = 0, n_pairs = 0;
 #ifdef TFBS_ROUND_PROF
     if (threadIdx.x < kMBlockWaves * 9) (&s_rprof[0][0])[threadIdx.x] = 0;
@@ -1200,9 +1125,6 @@ __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
         __syncthreads();  // the previous image's readers (and the pool's) are done
 #ifdef TFBS_ROUND_PROF
         const unsigned long long ts1 = RPROF_T();
-#endif
-#ifdef TFBS_AB_NORESTAGE  // timing ablation (wrong results): the first image only
-        if (si == 0)
 #endif
         stage_image(A, S, reinterpret_cast<uint4 *>(smem));
         if (threadIdx.x == 0) s_hnext = 0;
@@ -1233,10 +1155,8 @@ __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
     }
     (void)n_pairs;
     SCAN_STAMP(2, __builtin_amdgcn_s_memtime());
-#ifndef TFBS_AB_NORESCORE  // timing ablation (wrong results): no rescoring
     if (UNIT) rescore_list<true>(A, A.words, h0, slot, ngu, wave, lane, cn);
     else rescore_list<false>(A, words, h0, slot, 1, wave, lane, cn);
-#endif
     SCAN_STAMP(4, __builtin_amdgcn_s_memtime());
     SCAN_STAMP(6, __builtin_amdgcn_s_memrealtime());
     SCAN_STAMP(7, (unsigned long long)n_pairs | ((unsigned long long)cn << 32));
@@ -1278,347 +1198,7 @@ __global__ __launch_bounds__(256) void cand_over_kernel(ScanArgs A) {
     }
 }
 
-// ---------------------------------------------------------------------------
-// Window lists (ScanArgs::wlist): per depth class of span S, the windows [0, len
-// - lmin + 1) of every haplotype, only those meeting a diff run for a HAP_DEDUP
-// haplotype (tfbs_internal.hpp): f(lo, hi) gets them as ascending intervals.
-template <class F>
-__device__ __forceinline__ uint32_t for_windows(const DevHap &hm, const uint32_t *druns, uint32_t lmin, uint32_t S,
-                                                uint32_t dedup, F &&f) {
-    if (hm.len < lmin) return 0;
-    const uint32_t nw = hm.len - lmin + 1;
-    if (!dedup || !(hm.flags & HAP_DEDUP)) {
-        f(0u, nw);
-        return nw;
-    }
-    uint32_t n = 0, next = 0;  // windows below next are listed
-    for (uint32_t k = 0; k < hm.n_druns; k++) {
-        const uint32_t a = druns[2 * (hm.drun_off + k)], b = druns[2 * (hm.drun_off + k) + 1];
-        const uint32_t lo = max(next, a >= S - 1 ? a - (S - 1) : 0u), hi = min(b, nw - 1) + 1;
-        if (hi > lo) {
-            f(lo, hi);
-            n += hi - lo;
-            next = hi;
-        }
-    }
-    return n;
-}
-
-__global__ __launch_bounds__(256) void wl_count_kernel(const DevHap *__restrict__ haps, uint32_t n,
-                                                       const uint32_t *__restrict__ druns, uint32_t lmin, uint32_t S,
-                                                       uint32_t dedup, uint64_t *__restrict__ cnt) {
-    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
-    if (h > n) return;
-    cnt[h] = h < n ? for_windows(haps[h], druns, lmin, S, dedup, [](uint32_t, uint32_t) {}) : 0u;
-}
-
-// one wave per haplotype: its entries written 64 at a time
-__global__ __launch_bounds__(256) void wl_fill_kernel(const DevHap *__restrict__ haps, uint32_t n,
-                                                      const uint32_t *__restrict__ druns, uint32_t lmin, uint32_t S,
-                                                      uint32_t dedup, uint32_t hpb, const uint64_t *__restrict__ off,
-                                                      uint32_t *__restrict__ list, uint16_t *__restrict__ list16,
-                                                      const uint8_t *__restrict__ gnarrow) {
-    const uint32_t h = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (h >= n) return;
-    uint64_t at = off[h];
-    const uint32_t hl = h % hpb;
-    const bool narrow = gnarrow && gnarrow[h / hpb];
-    for_windows(haps[h], druns, lmin, S, dedup, [&](uint32_t lo, uint32_t hi) {
-        for (uint32_t w = lo + lane; w < hi; w += 64) {
-            if (narrow) list16[at + (w - lo)] = (uint16_t)((w << 6) | hl);
-            else list[at + (w - lo)] = (w << 6) | hl;
-        }
-        at += hi - lo;
-    });
-}
-
-// ---------------------------------------------------------------------------
-// Shared windows.  Haplotypes of one region mostly differ at sites far apart, so near
-// any one site many of them are base for base the same: window i of a depth class of
-// span S is *shared* by two HAP_DEDUP haplotypes of the region without indels or N, of
-// equal length, when it is dirty in both and their bases AND diff columns on [i, i + S)
-// (clipped to the length) are equal -- the exact 64-bit base image and 32-bit column
-// mask are compared, no hash.  The lowest-indexed such haplotype is the window's
-// *donor*: only the donor lists it; the others (its sharers) get one (sharer, [i_lo,
-// i_hi)) entry per run of consecutive windows taken from the same donor, in the
-// donor's entry range (ScanArgs::share), and the rescoring lists a donor's hits for
-// every sharer whose entry covers the window.  That is exact: position, inner ranges
-// and length are the region's, score and the dirty-for-L test depend only on the
-// window's bases and diff columns.  Everything else (the reference, a helper, indel
-// or N haplotypes, haplotypes scanned whole) lists its windows as before.
-__device__ __forceinline__ bool hap_shares(uint32_t flags) {
-    return (flags & (HAP_DEDUP | HAP_REF | HAP_HAS_POS | HAP_HAS_N)) == HAP_DEDUP;
-}
-// bit j: column i + j (j < n <= 32) lies in one of the haplotype's diff runs
-__device__ __forceinline__ uint32_t run_mask(const uint32_t *__restrict__ druns, uint32_t off, uint32_t nr, uint32_t i,
-                                             uint32_t n) {
-    uint32_t m = 0;
-    for (uint32_t k = 0; k < nr; k++) {
-        const uint32_t a = druns[2 * (off + k)], b = druns[2 * (off + k) + 1];
-        const uint32_t lo = max(a, i), hi = min(b, i + n - 1);
-        if (hi < lo) continue;  // (also a boundary run [a, a - 1])
-        const uint32_t cnt = hi - lo + 1;
-        m |= (cnt >= 32 ? 0xFFFFFFFFu : (1u << cnt) - 1) << (lo - i);
-    }
-    return m;
-}
-// the 2-bit bases of columns [i, i + n), n <= 32 (the words carry 3 pad words)
-__device__ __forceinline__ uint64_t window_bases(const uint32_t *__restrict__ words, uint32_t word_off, uint32_t i,
-                                                 uint32_t n) {
-    const uint32_t *w = words + word_off + (i >> 4);
-    const uint32_t sh = 2 * (i & 15);
-    const uint64_t v = (uint64_t)__builtin_amdgcn_alignbit(w[1], w[0], sh) |
-                       ((uint64_t)__builtin_amdgcn_alignbit(w[2], w[1], sh) << 32);
-    return n >= 32 ? v : v & ((1ull << (2 * n)) - 1);
-}
-
-// The donor of window i of haplotype h (hm; `active` lanes, one window each, windows
-// [c_lo, c_hi] over the wave): the lowest-indexed haplotype of the region sharing it,
-// h itself when none does.  h and hm are wave-uniform.
-__device__ __forceinline__ uint32_t find_donor(const DevHap *__restrict__ haps, const DevRegion *__restrict__ regions,
-                                               const uint32_t *__restrict__ druns, const uint32_t *__restrict__ words,
-                                               uint32_t h, const DevHap &hm, uint32_t i, bool active, uint32_t S,
-                                               uint32_t c_lo, uint32_t c_hi, uint32_t lane) {
-    if (!hap_shares(hm.flags)) return h;
-    const uint32_t n = active ? min(S, hm.len - i) : 1u;
-    const uint32_t ii = active ? i : 0u;
-    const uint32_t rm = run_mask(druns, hm.drun_off, hm.n_druns, ii, n);
-    const uint64_t key = window_bases(words, hm.word_off, ii, n);
-    uint32_t donor = h;
-    uint64_t open = __ballot(active);
-    // 64 lower-indexed haplotypes at a time, one per lane: those that may share (some run
-    // of theirs meets the columns of the wave's windows); then the wave compares its
-    // windows with each of them in ascending order
-    for (uint32_t b0 = regions[hm.region].hap_begin; b0 < h && open; b0 += 64) {
-        bool cand = false;
-        if (b0 + lane < h) {
-            const DevHap o = haps[b0 + lane];
-            if (hap_shares(o.flags) && o.len == hm.len)
-                for (uint32_t k = 0; k < o.n_druns && !cand; k++)
-                    cand = druns[2 * (o.drun_off + k)] <= c_hi + S - 1 && druns[2 * (o.drun_off + k) + 1] >= c_lo;
-        }
-        for (uint64_t cm = __ballot(cand); cm && open; cm &= cm - 1) {
-            const uint32_t h2 = b0 + (uint32_t)__builtin_ctzll(cm);
-            const uint32_t o_runs = haps[h2].drun_off, o_nr = haps[h2].n_druns, o_words = haps[h2].word_off;
-            bool eq = false;
-            if (active && donor == h && run_mask(druns, o_runs, o_nr, ii, n) == rm)
-                eq = window_bases(words, o_words, ii, n) == key;
-            if (eq) donor = h2;
-            open &= ~__ballot(eq);
-        }
-    }
-    return donor;
-}
-
-// One wave per haplotype h, its listed windows (for_windows) 64 at a time: f(w, active,
-// donor) with the lane's window, whether it has one, and the window's donor.
-template <class F>
-__device__ __forceinline__ void for_shared_windows(const DevHap *__restrict__ haps,
-                                                   const DevRegion *__restrict__ regions,
-                                                   const uint32_t *__restrict__ druns,
-                                                   const uint32_t *__restrict__ words, uint32_t h, const DevHap &hm,
-                                                   uint32_t lmin, uint32_t S, uint32_t lane, F &&f) {
-    for_windows(hm, druns, lmin, S, 1u, [&](uint32_t lo, uint32_t hi) {
-        for (uint32_t w0 = lo; w0 < hi; w0 += 64) {
-            const uint32_t w = w0 + lane;
-            const bool active = w < hi;
-            f(w, active, find_donor(haps, regions, druns, words, h, hm, w, active, S, w0, min(w0 + 63, hi - 1), lane));
-        }
-    });
-}
-
-// Of the lanes with `sh` (a sharer's window, its donor d): whether the lane starts a
-// run of consecutive lanes with the same donor, and the run's length.
-__device__ __forceinline__ bool sharer_run(bool sh, uint32_t d, uint32_t lane, uint32_t *len) {
-    const uint32_t pd = (uint32_t)__shfl_up((int)d, 1);
-    const bool psh = __shfl_up((int)sh, 1) != 0;
-    const bool start = sh && (lane == 0 || !psh || pd != d);
-    const uint64_t cont = __ballot(sh && !start);
-    const uint64_t after = lane == 63 ? 0ull : cont >> (lane + 1);
-    *len = 1 + (uint32_t)__builtin_ctzll(~after);
-    return start;
-}
-
-// cnt[h]: the windows haplotype h lists itself; scnt[d] += the sharer entries of donor
-// d (zeroed before); hstat[2 h], [2 h + 1]: the (window, strand) pairs and cells of the
-// windows h lists (tab: the class's strand lengths).
-__global__ __launch_bounds__(256) void wl_share_count_kernel(const DevHap *__restrict__ haps, uint32_t n,
-                                                             const DevRegion *__restrict__ regions,
-                                                             const uint32_t *__restrict__ druns,
-                                                             const uint32_t *__restrict__ words, uint32_t lmin,
-                                                             uint32_t S, const ClassTab *__restrict__ tab,
-                                                             uint64_t *__restrict__ cnt,
-                                                             unsigned long long *__restrict__ scnt,
-                                                             uint32_t *__restrict__ hstat) {
-    const uint32_t h = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (h > n) return;
-    if (h == n) {
-        if (lane == 0) cnt[n] = 0;
-        return;
-    }
-    const DevHap hm = haps[h];
-    uint32_t own = 0, rw = 0, rc = 0;
-    for_shared_windows(haps, regions, druns, words, h, hm, lmin, S, lane, [&](uint32_t w, bool active, uint32_t d) {
-        const bool mine = active && d == h;
-        own += (uint32_t)__popcll(__ballot(mine));
-        uint32_t len;
-        if (sharer_run(active && !mine, d, lane, &len)) atomicAdd(scnt + d, 1ull);
-        if (mine) {
-            const uint32_t r = min(hm.len - w, 32u);
-            rw += tab->w[r];
-            rc += tab->c[r];
-        }
-    });
-    for (uint32_t o = 32; o; o >>= 1) {
-        rw += (uint32_t)__shfl_down((int)rw, o);
-        rc += (uint32_t)__shfl_down((int)rc, o);
-    }
-    if (lane == 0) {
-        cnt[h] = own;
-        hstat[2 * (size_t)h] = rw;
-        hstat[2 * (size_t)h + 1] = rc;
-    }
-}
-
-// The haplotype's own windows to its list range (ascending), its sharer entries to
-// their donors' ranges (soff; scur: fill cursors, zeroed before).
-__global__ __launch_bounds__(256) void wl_share_fill_kernel(const DevHap *__restrict__ haps, uint32_t n,
-                                                            const DevRegion *__restrict__ regions,
-                                                            const uint32_t *__restrict__ druns,
-                                                            const uint32_t *__restrict__ words, uint32_t lmin, uint32_t S,
-                                                            uint32_t hpb, const uint64_t *__restrict__ off,
-                                                            uint32_t *__restrict__ list, uint16_t *__restrict__ list16,
-                                                            const uint8_t *__restrict__ gnarrow,
-                                                            const uint64_t *__restrict__ soff,
-                                                            uint32_t *__restrict__ scur, uint2 *__restrict__ share) {
-    const uint32_t h = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (h >= n) return;
-    const DevHap hm = haps[h];
-    uint64_t at = off[h];
-    const uint64_t end = off[h + 1];
-    const uint32_t hl = h % hpb;
-    const bool narrow = gnarrow && gnarrow[h / hpb];
-    for_shared_windows(haps, regions, druns, words, h, hm, lmin, S, lane, [&](uint32_t w, bool active, uint32_t d) {
-        const bool own = active && d == h;
-        const uint64_t ob = __ballot(own);
-        const uint64_t q = at + __builtin_amdgcn_mbcnt_hi((uint32_t)(ob >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ob, 0));
-        if (own && q < end) {  // (q < end: the count pass's number, whatever happens)
-            if (narrow) list16[q] = (uint16_t)((w << 6) | hl);
-            else list[q] = (w << 6) | hl;
-        }
-        at += (uint32_t)__popcll(ob);
-        uint32_t len;
-        if (sharer_run(active && d != h, d, lane, &len)) {
-            const uint64_t e = soff[d] + atomicAdd(scur + d, 1u);
-            if (e < soff[d + 1]) share[e] = make_uint2(h, w | ((w + len) << 16));
-        }
-    });
-}
-
-// sum[0], sum[1] += the even and the odd words of x[0 .. 2 n)
-__global__ __launch_bounds__(256) void pair_sum_kernel(const uint32_t *__restrict__ x, uint32_t n,
-                                                       unsigned long long *__restrict__ sum) {
-    unsigned long long a = 0, b = 0;
-    for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
-        a += x[2 * (size_t)k];
-        b += x[2 * (size_t)k + 1];
-    }
-    for (uint32_t o = 32; o; o >>= 1) {
-        a += (unsigned long long)__shfl_down((long long)a, o);
-        b += (unsigned long long)__shfl_down((long long)b, o);
-    }
-    if ((threadIdx.x & 63) == 0 && (a | b)) {
-        atomicAdd(sum, a);
-        atomicAdd(sum + 1, b);
-    }
-}
-
-__global__ __launch_bounds__(256) void group_cost_kernel(const uint64_t *__restrict__ off0,
-                                                         const uint64_t *__restrict__ off1, uint32_t n_haps, uint32_t hpb,
-                                                         uint32_t n_groups, uint32_t w0, uint32_t w1,
-                                                         uint32_t *__restrict__ cost) {
-    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
-    if (g >= n_groups) return;
-    const uint32_t h0 = g * hpb, h1 = min(h0 + hpb, n_haps);
-    uint64_t c = 0;
-    if (off0) c += (off0[h1] - off0[h0] + 2 * kMWindows - 1) / (2 * kMWindows) * w0;
-    if (off1) c += (off1[h1] - off1[h0] + 2 * kMWindows - 1) / (2 * kMWindows) * w1;
-    cost[g] = (uint32_t)min<uint64_t>(c, 0xFFFFFFFFu);
-}
-
-// The scan's compact haplotype descriptors (ScanArgs::hd): word offset, length,
-// flags, N-mask offset of every DevHap.
-__global__ __launch_bounds__(256) void hd_kernel(const DevHap *__restrict__ haps, uint32_t n, uint4 *__restrict__ hd,
-                                                  uint4 *__restrict__ hd2) {
-    const uint32_t h = blockIdx.x * 256 + threadIdx.x;
-    if (h < n) {
-        const DevHap x = haps[h];
-        hd[h] = make_uint4(x.word_off, x.len, x.flags, x.nmask_off);
-        hd2[h] = make_uint4(x.region, x.pos_off, x.drun_off, x.n_druns);
-    }
-}
-
-// In-place exclusive scan of u64 values, 4096 per workgroup; sums[b] = tile b's total.
-constexpr uint32_t kScanThreads = 1024, kScanTile = 4 * kScanThreads;
-__global__ __launch_bounds__(kScanThreads) void scan_tile_kernel(uint64_t *__restrict__ x, uint64_t n,
-                                                                 uint64_t *__restrict__ sums) {
-    __shared__ uint64_t s[2][kScanThreads];
-    const uint32_t t = threadIdx.x;
-    const uint64_t base = (uint64_t)blockIdx.x * kScanTile + 4 * t;
-    uint64_t v[4], tot = 0;
-    for (int k = 0; k < 4; k++) {
-        v[k] = base + k < n ? x[base + k] : 0;
-        tot += v[k];
-    }
-    int cur = 0;
-    s[0][t] = tot;
-    __syncthreads();
-    for (uint32_t o = 1; o < kScanThreads; o <<= 1) {
-        s[cur ^ 1][t] = s[cur][t] + (t >= o ? s[cur][t - o] : 0);
-        cur ^= 1;
-        __syncthreads();
-    }
-    uint64_t run = s[cur][t] - tot;
-    for (int k = 0; k < 4; k++) {
-        if (base + k < n) x[base + k] = run;
-        run += v[k];
-    }
-    if (t == kScanThreads - 1) sums[blockIdx.x] = s[cur][t];
-}
-
-__global__ __launch_bounds__(256) void scan_add_kernel(uint64_t *__restrict__ x, uint64_t n,
-                                                       const uint64_t *__restrict__ sums) {
-    const uint64_t add = sums[blockIdx.x];
-    for (uint32_t k = threadIdx.x; k < kScanTile; k += 256) {
-        const uint64_t i = (uint64_t)blockIdx.x * kScanTile + k;
-        if (i < n) x[i] += add;
-    }
-}
-
-}  // namespace
-
-int exclusive_scan(uint64_t *x, uint64_t n, uint64_t *tmp, hipStream_t stream) {
-    const uint64_t nt = (n + kScanTile - 1) / kScanTile;
-    if (nt == 0) return TFBS_OK;
-    hipLaunchKernelGGL(scan_tile_kernel, dim3((uint32_t)nt), dim3(kScanThreads), 0, stream, x, n, tmp);
-    if (nt > 1) {
-        if (int rc = exclusive_scan(tmp, nt, tmp + nt, stream)) return rc;
-        hipLaunchKernelGGL(scan_add_kernel, dim3((uint32_t)nt), dim3(256), 0, stream, x, n, tmp);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("scan kernels: ") + hipGetErrorString(e));
-    return TFBS_OK;
-}
-
-namespace {
-
 typedef void (*MfmaKernel)(ScanArgs);
-template <int NK> MfmaKernel mfma_nk(bool staged) {
-    return staged ? scan_mfma_kernel<true, NK> : scan_mfma_kernel<false, NK>;
-}
-MfmaKernel mfma_variant(bool staged, uint32_t nk) {  // depth classes (mfma_depth_class)
-    return nk <= 2 ? mfma_nk<2>(staged) : mfma_nk<4>(staged);
-}
 MfmaKernel mfma_all_variant(bool staged, bool unit) {
     if (unit) return staged ? scan_mfma_all_kernel<true, true> : scan_mfma_all_kernel<false, true>;
     return staged ? scan_mfma_all_kernel<true, false> : scan_mfma_all_kernel<false, false>;
@@ -1749,7 +1329,7 @@ __device__ void post_one_block(const ScanArgs &A, uint32_t tid, uint32_t n_regio
     __syncthreads();
     post_buckets<NT>(A, tid, n_regions, bcnt, boff, sorted, report, need_wide, s_sum);
 }
-// (the merged scan kernel's tail, instantiated above this definition)
+// (the scan kernel's tail, instantiated above this definition)
 template __device__ void post_one_block<kMBlock>(const ScanArgs &, uint32_t, uint32_t, uint32_t *, uint32_t *,
                                                  uint32_t *, uint32_t *, uint32_t *, uint32_t *);
 
@@ -1835,120 +1415,20 @@ int launch_post_scan(const ScanArgs &a, hipStream_t stream) {
     return 1;
 }
 
-uint32_t mfma_group_words(const DevHap *haps, uint32_t n_haps, uint32_t hpb) {
-    uint32_t mx = 0;
-    for (uint32_t h0 = 0; h0 < n_haps; h0 += hpb) {
-        const uint32_t hl = std::min(h0 + hpb, n_haps) - 1;
-        mx = std::max(mx, haps[hl].word_off + (haps[hl].len + 15) / 16 + 3 - haps[h0].word_off);
-    }
-    return mx;
-}
-
-size_t scan_tmp_words(size_t n) {
-    size_t w = 0;
-    for (size_t nt = (n + kScanTile - 1) / kScanTile; nt > 0; nt = nt > 1 ? (nt + kScanTile - 1) / kScanTile : 0) w += nt;
-    return w + 1;
-}
-
-int build_window_lists(const DevHap *haps, uint32_t n_haps, const uint32_t *druns, const uint32_t lmin[2],
-                       const uint32_t span[2], uint32_t hpb, uint32_t dedup, WindowListBufs &bufs, uint64_t total[2], hipStream_t stream,
-                       int (*ensure_list)(void *ctx, int c, uint64_t n, uint32_t **p, uint16_t **p16),
-                       void *ensure_ctx, uint32_t share, const DevRegion *regions, const uint32_t *words,
-                       const ClassTab *tab, int (*ensure_share)(void *ctx, int c, uint64_t n, uint2 **p),
-                       uint64_t shared[2], uint64_t listed[2][2]) {
-    if (n_haps && bufs.hd) hipLaunchKernelGGL(hd_kernel, dim3((n_haps + 255) / 256), dim3(256), 0, stream, haps, n_haps,
-                                             bufs.hd, bufs.hd2);
-    share = share && dedup && n_haps;
-    if (share) {
-        hipError_t e = hipMemsetAsync(bufs.stat, 0, 4 * sizeof(uint64_t), stream);
-        if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("window lists: ") + hipGetErrorString(e));
-    }
-    for (int c = 0; c < 2; c++) {
-        total[c] = 0;
-        if (shared) shared[c] = 0;
-        if (listed) listed[c][0] = listed[c][1] = 0;
-        if (!lmin[c]) continue;
-        const uint32_t S = span[c] ? span[c] : kMChunkCols * (c ? 4 : 2);  // the windows dirty for the longest strand
-        if (share) {  // count (own windows, sharer entries per donor) -> offsets -> fill
-            unsigned long long *scnt = reinterpret_cast<unsigned long long *>(bufs.soff[c]);
-            hipError_t e = hipMemsetAsync(bufs.soff[c], 0, ((size_t)n_haps + 1) * 8, stream);
-            if (e == hipSuccess) e = hipMemsetAsync(bufs.scur, 0, (size_t)n_haps * 8, stream);  // (the count's hstat)
-            if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("window lists: ") + hipGetErrorString(e));
-            hipLaunchKernelGGL(wl_share_count_kernel, dim3(n_haps / 4 + 1), dim3(256), 0, stream, haps, n_haps, regions,
-                               druns, words, lmin[c], S, tab + c, bufs.off[c], scnt, bufs.scur);
-            hipLaunchKernelGGL(pair_sum_kernel, dim3(256), dim3(256), 0, stream, bufs.scur, n_haps,
-                               reinterpret_cast<unsigned long long *>(bufs.stat) + 2 * c);
-            int rc;
-            if ((rc = exclusive_scan(bufs.off[c], (uint64_t)n_haps + 1, bufs.scan_tmp, stream)) ||
-                (rc = exclusive_scan(bufs.soff[c], (uint64_t)n_haps + 1, bufs.scan_tmp, stream)))
-                return rc;
-            uint64_t ns = 0;
-            e = hipMemcpyAsync(&total[c], bufs.off[c] + n_haps, 8, hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&ns, bufs.soff[c] + n_haps, 8, hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(listed[c], bufs.stat + 2 * c, 16, hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("window list size: ") + hipGetErrorString(e));
-            shared[c] = ns;
-            if ((rc = ensure_list(ensure_ctx, c, std::max<uint64_t>(total[c], 1), &bufs.list[c], &bufs.list16[c])) ||
-                (rc = ensure_share(ensure_ctx, c, std::max<uint64_t>(ns, 1), &bufs.share[c])))
-                return rc;
-            e = hipMemsetAsync(bufs.scur, 0, (size_t)n_haps * 4, stream);
-            if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("window lists: ") + hipGetErrorString(e));
-            hipLaunchKernelGGL(wl_share_fill_kernel, dim3((n_haps + 3) / 4), dim3(256), 0, stream, haps, n_haps, regions,
-                               druns, words, lmin[c], S, hpb, bufs.off[c], bufs.list[c], bufs.list16[c], bufs.gnarrow,
-                               bufs.soff[c], bufs.scur, bufs.share[c]);
-            e = hipGetLastError();
-            if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("wl_share_fill_kernel: ") + hipGetErrorString(e));
-            continue;
-        }
-        hipLaunchKernelGGL(wl_count_kernel, dim3(n_haps / 256 + 1), dim3(256), 0, stream, haps, n_haps, druns, lmin[c],
-                           S, dedup, bufs.off[c]);
-        if (int rc = exclusive_scan(bufs.off[c], (uint64_t)n_haps + 1, bufs.scan_tmp, stream)) return rc;
-        hipError_t e = hipMemcpyAsync(&total[c], bufs.off[c] + n_haps, 8, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("window list size: ") + hipGetErrorString(e));
-        if (int rc = ensure_list(ensure_ctx, c, std::max<uint64_t>(total[c], 1), &bufs.list[c], &bufs.list16[c]))
-            return rc;
-        if (n_haps)
-            hipLaunchKernelGGL(wl_fill_kernel, dim3((n_haps + 3) / 4), dim3(256), 0, stream, haps, n_haps, druns,
-                               lmin[c], S, dedup, hpb, bufs.off[c], bufs.list[c], bufs.list16[c], bufs.gnarrow);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("wl_fill_kernel: ") + hipGetErrorString(e));
-    }
-    return TFBS_OK;
-}
-
-int group_costs(const uint64_t *off0, const uint64_t *off1, uint32_t n_haps, uint32_t hpb, uint32_t w0, uint32_t w1,
-                uint32_t *cost, hipStream_t stream) {
-    const uint32_t ng = (n_haps + hpb - 1) / hpb;
-    if (ng == 0) return TFBS_OK;
-    hipLaunchKernelGGL(group_cost_kernel, dim3((ng + 255) / 256), dim3(256), 0, stream, off0, off1, n_haps, hpb, ng, w0,
-                       w1, cost);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("group_cost_kernel: ") + hipGetErrorString(e));
-    return TFBS_OK;
-}
-
 size_t mfma_lds_fixed() { return kMOnehotBytes; }
 
-void mfma_depth_budgets(uint32_t out[9]) {
-    const uint32_t *waves = kMfmaRegWaves;
-    const uint32_t reserve = kMOnehotBytes + 4096 + sizeof(s_qdata) + sizeof(s_qmeta) + sizeof(s_cand) + sizeof(s_went) + sizeof(s_hd) + sizeof(s_hd2) +
-                             256;  // table, staged words, queues
-    // workgroups per CU = 4 SIMDs x waves per SIMD / waves per workgroup
-    for (int nk = 1; nk <= kMMaxChunks; nk++) out[nk] = (160 * 1024) / (4 * waves[nk] / (kMBlock / 64)) - reserve;
-}
-
 int launch_mfma_all(const ScanArgs &a0, const DevMSuper *supers, uint32_t n_supers, uint32_t group_words,
-                    uint32_t n_haps, hipStream_t stream, HitSrc *srcs, uint32_t *n_srcs) {
-    *n_srcs = 0;
+                    uint32_t n_haps, hipStream_t stream) {
     if (n_haps == 0 || n_supers == 0) return 0;
     const uint32_t hpb = a0.haps_per_block;
     const DevMSuper &last = supers[n_supers - 1];
     if ((uint64_t)(last.tile0 + last.tile_count) * kMStrands > (1u << 24) || hpb > kMMaxHapsPerBlock)
         return fail(TFBS_E_ARG, "matrix-core scan: more than 2^24 strands or 64 haplotypes per workgroup");
     const uint32_t n_hg = (n_haps + hpb - 1) / hpb;
-    const size_t static_lds = sizeof(s_qdata) + sizeof(s_qmeta) + sizeof(s_cand) + sizeof(s_went) + sizeof(s_hnext) + sizeof(s_hd) + sizeof(s_hd2);
+    // slack kept in the budget (a retired 2 KiB array) so that the staging decisions below are unchanged
+    constexpr size_t kMLdsSlack = 2048;
+    const size_t static_lds =
+        sizeof(s_qdata) + sizeof(s_qmeta) + sizeof(s_cand) + kMLdsSlack + sizeof(s_hnext) + sizeof(s_hd) + sizeof(s_hd2);
     size_t img_bytes = 0;
     for (uint32_t k = 0; k < n_supers; k++) img_bytes = std::max<size_t>(img_bytes, supers[k].img_bytes);
     const size_t base = kMOnehotBytes + img_bytes + kMChunkBytes;  // (the padding: scan_segment's B prefetch)
@@ -1974,18 +1454,15 @@ int launch_mfma_all(const ScanArgs &a0, const DevMSuper *supers, uint32_t n_supe
         unit_bytes = base + unit_lds * gw;
         staged = unit_lds > 0;
     }
-    // (TFBS_SCAN_LDS_MIN: an occupancy A/B -- more LDS per workgroup, fewer per CU)
-    static const size_t lds_min = getenv("TFBS_SCAN_LDS_MIN") ? (size_t)atol(getenv("TFBS_SCAN_LDS_MIN")) : 0;
-    const size_t lds = std::max(G > 1 ? unit_bytes : staged ? staged_bytes : base, lds_min);
+    const size_t lds = G > 1 ? unit_bytes : staged ? staged_bytes : base;
     const MfmaKernel kern = mfma_all_variant(staged, G > 1);
     hipError_t e = hipSuccess;
     if (lds > 64 * 1024)
         e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("MFMA LDS attribute: ") + hipGetErrorString(e));
     int launches = 0;
-    const uint64_t max_hg = ((1ull << 31) - 1) / kMMaxUnit * kMMaxUnit;  // whole units per launch
-    for (uint64_t g0 = 0; g0 < n_hg; g0 += max_hg) {
-        const uint32_t ng = (uint32_t)std::min<uint64_t>(max_hg, n_hg - g0);
+    for (uint64_t g0 = 0; g0 < n_hg; g0 += kMLaunchGroups) {
+        const uint32_t ng = (uint32_t)std::min<uint64_t>(kMLaunchGroups, n_hg - g0);
         const uint32_t h0 = (uint32_t)(g0 * hpb);
         ScanArgs a = a0;
         a.unit = G;
@@ -1999,86 +1476,15 @@ int launch_mfma_all(const ScanArgs &a0, const DevMSuper *supers, uint32_t n_supe
         a.gnarrow = a0.gnarrow ? a0.gnarrow + g0 : nullptr;
         a.n_haps = std::min<uint32_t>(n_haps - h0, ng * hpb);
         a.hits = a0.hits ? a0.hits + (size_t)h0 * a0.n_patterns_total * a0.hits_wpp : nullptr;
+        // a group's lists are at its index in the batch, whichever launch scans it: the
+        // key assembly indexes them directly (scan.hpp, hitl / hitn)
         a.region_base = (uint32_t)g0;
-        if (*n_srcs >= (uint32_t)kMaxHitSrcs) return fail(TFBS_E_ARG, "matrix-core scan: too many launches");
-        srcs[(*n_srcs)++] = HitSrc{(uint32_t)g0, 1, (uint32_t)g0, ng};
         a.mimg_max = (uint32_t)img_bytes;
         hipLaunchKernelGGL(kern, dim3((ng + G - 1) / G), dim3(kMBlock), lds, stream, a);
         launches++;
     }
     e = hipGetLastError();
     if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("scan_mfma_all_kernel launch: ") + hipGetErrorString(e));
-    return launches;
-}
-
-int launch_mfma(const ScanArgs &a0, const DevMSuper *supers, uint32_t n_supers, uint32_t group_words,
-                uint32_t n_haps, const hipStream_t *streams, uint32_t n_streams, HitSrc *srcs, uint32_t *n_srcs) {
-    *n_srcs = 0;
-    if (n_haps == 0 || n_supers == 0) return 0;
-    const uint32_t hpb = a0.haps_per_block;
-    // candidate list entries: global strand < 2^24, haplotype in the group < 2^8
-    const DevMSuper &last = supers[n_supers - 1];
-    if ((uint64_t)(last.tile0 + last.tile_count) * kMStrands > (1u << 24) || hpb > kMMaxHapsPerBlock)
-        return fail(TFBS_E_ARG, "matrix-core scan: more than 2^24 strands or 64 haplotypes per workgroup");
-    const uint32_t n_hg = (n_haps + hpb - 1) / hpb;
-    const size_t static_lds =
-        sizeof(s_qdata) + sizeof(s_qmeta) + sizeof(s_cand) + sizeof(s_went) + sizeof(s_hnext) + sizeof(s_hd) + sizeof(s_hd2);  // queues, descriptors
-    uint32_t region = 0;
-    int launches = 0;
-    // one launch per K depth (super tiles come sorted by depth): each kernel is
-    // compiled for its depth's registers and LDS; the deepest (longest) first
-    std::vector<std::pair<uint32_t, uint32_t>> groups;  // [s0, s1) per depth
-    for (uint32_t s0 = 0; s0 < n_supers;) {
-        uint32_t s1 = s0;
-        while (s1 < n_supers && supers[s1].nk == supers[s0].nk) s1++;
-        groups.push_back({s0, s1});
-        s0 = s1;
-    }
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        static const bool shallow_first = getenv("TFBS_SCAN_SHALLOW_FIRST") && atoi(getenv("TFBS_SCAN_SHALLOW_FIRST"));
-        const size_t gk = shallow_first ? gi : groups.size() - 1 - gi;  // (A/B: the launch order of the depths)
-        const uint32_t s0 = groups[gk].first, s1 = groups[gk].second;
-        const hipStream_t stream = streams[gi % n_streams];
-        const uint32_t nk = supers[s0].nk;
-        size_t img_bytes = 0;
-        for (uint32_t k = s0; k < s1; k++) img_bytes = std::max<size_t>(img_bytes, supers[k].img_bytes);
-        const uint32_t ns = s1 - s0;
-        // stage the group's words in LDS when they fit beside the image at 4 workgroups per CU
-        const size_t base = kMOnehotBytes + img_bytes + kMChunkBytes;  // (the padding: scan_segment's B prefetch)
-        const size_t staged_bytes = base + ((size_t)group_words * 4 + 15) / 16 * 16;
-        const bool staged = staged_bytes + static_lds <= kMStagedMax;
-        const size_t lds = staged ? staged_bytes : base;
-        const MfmaKernel kern = mfma_variant(staged, nk);
-        hipError_t e = hipSuccess;
-        if (lds > 64 * 1024)
-            e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("MFMA LDS attribute: ") + hipGetErrorString(e));
-        const uint64_t max_hg = std::max<uint64_t>(1, (1ull << 31) / ns - 1);
-        for (uint64_t g0 = 0; g0 < n_hg; g0 += max_hg) {
-            const uint32_t ng = (uint32_t)std::min<uint64_t>(max_hg, n_hg - g0);
-            const uint32_t h0 = (uint32_t)(g0 * hpb);
-            ScanArgs a = a0;
-            a.msupers = a0.msupers + s0;
-            a.n_msupers = ns;
-            a.haps = a0.haps + h0;
-            a.hd = a0.hd + h0;
-            a.hd2 = a0.hd2 + h0;
-            a.hap_base = a0.hap_base + h0;
-            for (int c = 0; c < 2; c++) a.wlist_off[c] = a0.wlist_off[c] ? a0.wlist_off[c] + h0 : nullptr;
-            a.gnarrow = a0.gnarrow ? a0.gnarrow + g0 : nullptr;
-            a.n_haps = std::min<uint32_t>(n_haps - h0, ng * hpb);
-            a.hits = a0.hits ? a0.hits + (size_t)h0 * a0.n_patterns_total * a0.hits_wpp : nullptr;
-            a.region_base = region;
-            if (*n_srcs >= (uint32_t)kMaxHitSrcs) return fail(TFBS_E_ARG, "matrix-core scan: too many launches");
-            srcs[(*n_srcs)++] = HitSrc{region, ns, (uint32_t)g0, ng};
-            region += ns * ng;
-            a.mimg_max = (uint32_t)img_bytes;
-            hipLaunchKernelGGL(kern, dim3(ns * ng), dim3(kMBlock), lds, stream, a);
-            launches++;
-        }
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("scan_mfma_kernel launch: ") + hipGetErrorString(e));
     return launches;
 }
 

@@ -156,9 +156,8 @@ typedef struct tfbs_mfma_bound {
 int tfbs_patterns_mfma_bound(const tfbs_patterns *p, size_t i, const uint8_t *bases, tfbs_mfma_bound *out);
 /* Host-only, read-only diagnostic of the matrix-core plan: copies of the arrays a
  * device context uploads for the matrix-core scan and nothing derived from them.  The
- * plan is built once per call exactly as tfbs_ctx_create builds it with TFBS_MFMA=1,
- * TFBS_MFMA_LDS_KB=lds_kb (0: the default, 44; clamped to 8..144 as there) and
- * TFBS_MFMA_LDS_BY_DEPTH unset.  image: the FP6 digit fragments of every super tile
+ * plan is built once per call exactly as tfbs_ctx_create builds it with TFBS_MFMA=1
+ * and TFBS_MFMA_LDS_KB=lds_kb (0: the default, 44; clamped to 8..144 as there).  image: the FP6 digit fragments of every super tile
  * (lane layout: mfma.cpp, scan_mfma.hip); supers: per super tile its tile count, depth
  * class nk (2 or 4), the byte offset and size of its image, the depth segment ends
  * (byte d - 1: the first tile deeper than d), the common candidate threshold t0, the

@@ -18,9 +18,9 @@ from helpers import T, build_batch, run_oracle
 
 pytestmark = pytest.mark.gpu
 
-MODES = {"default": {}, "per_depth": {"TFBS_SCAN_MERGED": "0"}, "lds8": {"TFBS_MFMA_LDS_KB": "8"},
+MODES = {"default": {}, "lds8": {"TFBS_MFMA_LDS_KB": "8"},
          "small_lists": {"TFBS_CAND_CAP": "64", "TFBS_CAND_OVER_CAP": "16"}}
-ENV = ("TFBS_MFMA", "TFBS_MFMA_LDS_KB", "TFBS_MFMA_LDS_BY_DEPTH", "TFBS_SCAN_MERGED", "TFBS_CAND_CAP",
+ENV = ("TFBS_MFMA", "TFBS_MFMA_LDS_KB", "TFBS_CAND_CAP",
        "TFBS_CAND_OVER_CAP", "TFBS_SCAN_UNIT", "TFBS_MFMA_HAPS_PER_BLOCK", "TFBS_DEDUP", "TFBS_SHARE")
 CASES = ["neighbours", "every_place_1", "every_place_2", "every_place_63", "every_place_64", "every_place_65",
          "depths", "t0mix", "lists", "scales"]
@@ -92,8 +92,7 @@ def test_candidates_equal_the_model(cases, monkeypatch, mode, name):
     fp = F.FilterPlan(case.pset.mfma_plan(int(env.get("TFBS_MFMA_LDS_KB", 0))))
     n_supers = len(fp.supers)
     cand_cap = int(env.get("TFBS_CAND_CAP", 1024))
-    merged = env.get("TFBS_SCAN_MERGED", "1") != "0"
-    n_wg, cap_wg = (1, min(1 << 16, cand_cap * n_supers)) if merged else (n_supers, cand_cap)
+    n_wg, cap_wg = 1, min(1 << 16, cand_cap * n_supers)
     sc = T.Scanner(case.pset)
     try:
         for hname, hap in case.haps.items():

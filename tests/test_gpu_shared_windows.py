@@ -1,4 +1,4 @@
-"""Shared windows (scan_mfma.hip "Shared windows", TFBS_SHARE): a dirty window of an
+"""Shared windows (window_lists.hip "Shared windows", TFBS_SHARE): a dirty window of an
 SNV-only HAP_DEDUP haplotype is listed only for the lowest-indexed haplotype of the
 region that has the same window (its donor), and the rescoring lists a donor's hits
 for its sharers.  Hand-built small regions against the oracle (keys and rows), the

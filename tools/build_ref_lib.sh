@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds the library of a git revision (default HEAD) into
-# find-tfbs_amd/lib/probe<NAME>/ for same-box A/B runs (tools/exp.sh NAME),
+# find-tfbs_amd/lib/probe<NAME>/ for same-box A/B runs (TFBS_LIB=.../probe<NAME>/libtfbs_amd.so, tools/ab_kernels.sh),
 # from a temporary worktree so the working tree is untouched.
 # Usage: bash tools/build_ref_lib.sh [REV] [NAME]
 set -e

@@ -1,6 +1,6 @@
 # PMC stall breakdown of the scan's MFMA phase at the bench's C3 operating point (two
 # SQ passes over bench.py, each its own rocprofv3 run); summaries per pass via
-# tools/pmc_summary.py (the last step's scan_mfma_kernel dispatches).
+# tools/pmc_summary.py (the last step's scan_mfma_all_kernel dispatches).
 # Usage: bash tools/pmc_scan_stalls.sh TAG [bench.py args]
 set -o pipefail
 TAG=${1:?tag}; shift

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Summarise a rocprofv3 --pmc pass over bench.py: counters summed over the
-dispatches of the last scan step's MFMA phase (every scan_mfma_kernel dispatch
-after the last non-MFMA dispatch that precedes them -- one per K depth and hap
-group chunk), plus the dispatches' kernel names.
+dispatches of the last scan step's MFMA phase (every scan_mfma_all_kernel dispatch
+after the last non-MFMA dispatch that precedes them -- one per scan, or one per chunk
+of haplotype groups when a batch takes several launches), plus the dispatches' kernel
+names.
 
 Usage: python tools/pmc_summary.py PMC_DIR [KERNEL]  -> PMC_DIR/pmc_summary.json
        KERNEL (a substring of the kernel name): that kernel's last dispatch instead
@@ -17,7 +18,7 @@ import sys
 
 
 def last_phase(rows):
-    """Dispatch ids of the last run of consecutive scan_mfma_kernel dispatches."""
+    """Dispatch ids of the last run of consecutive scan_mfma_all_kernel dispatches."""
     names = {}
     for r in rows:
         names[int(r["Dispatch_Id"])] = r["Kernel_Name"]

@@ -7,7 +7,7 @@ pass, all stamped with the SHA-256 of the library they profiled: bench.py uses
 the file only when that hash is the running library's.
 
 FETCH_SIZE / WRITE_SIZE are KiB per dispatch (rocprofv3), summed over the last
-step's scan_mfma_kernel dispatches (tools/pmc_summary.py).  On gfx950
+step's scan_mfma_all_kernel dispatches (tools/pmc_summary.py).  On gfx950
 FETCH_SIZE reports half the bytes of wide streaming reads
 (MI355X_MICROARCH.md, HBM section): it is doubled; WRITE_SIZE is taken as is.
 
@@ -35,7 +35,7 @@ def main():
            "fetch_size_bytes": fetch, "fetch_bytes_x2": 2 * fetch, "write_bytes": write,
            "hbm_bytes_per_step": 2 * fetch + write,
            "source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes over `bench.py %s "
-                     "--full --steps 2 --warmup 0 --no-cpu --no-e2e`, the last step's scan_mfma_kernel dispatches "
+                     "--full --steps 2 --warmup 0 --no-cpu --no-e2e`, the last step's scan_mfma_all_kernel dispatches "
                      "summed, FETCH_SIZE x2" % " ".join(sys.argv[1:])}
     ph = os.path.join(root, "mfma_phase.json")
     if os.path.exists(ph):  # the kernel trace of the same command (--kernel-trace --stats pass)

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """MFMA scan phase from a rocprofv3 kernel trace.
 
-One scan step launches one scan_mfma_kernel per K depth, spread over four
-streams, so the step's MFMA phase is the union of those dispatches: from the
-first start to the last end of each run of consecutive scan_mfma dispatches
-(the counts memset that opens every step ends a run).  This is the figure
+One scan step launches scan_mfma_all_kernel once on the ctx stream (once per chunk
+of haplotype groups when a batch takes several launches), so the step's MFMA phase
+is the union of those dispatches: from the first start to the last end of each run
+of consecutive scan_mfma dispatches (the counts memset that opens every step ends a
+run).  This is the figure
 bench.py's roofline divides by (HIP events around the launches on the ctx
 stream); per-kernel averages are listed beside it.
 
