@@ -373,6 +373,16 @@ class Scanner:
         return dict(zip(("left", "arena", "spill", "wide", "leftover", "reruns", "reruns_wide", "reruns_leftover"),
                         (int(x) for x in out)))
 
+    def post_figures(self):
+        """tfbs_ctx_post_figures of the last checked assembly: {"left_out" (it ran without the
+        post-scan stage: no rescoring, no spill buckets), "reruns_post" (since the scanner was made:
+        assemblies that had left it out, reported a spill record or a candidate past the lists and
+        ran again in full), "fused" (the stage ran in the scan kernel's last workgroup), "cand" (the
+        scan's candidates past the waves' lists)}."""
+        out = (C.c_uint64 * 4)()
+        check(lib().tfbs_ctx_post_figures(self.h, out))
+        return dict(zip(("left_out", "reruns_post", "fused", "cand"), (int(x) for x in out)))
+
     def matches_all(self, haplotype):
         """pattern.rs:141-171 for every pattern: list (per pattern, creation order) of [(start, end)]."""
         n = len(haplotype)

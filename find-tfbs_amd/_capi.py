@@ -163,6 +163,7 @@ SIGNATURES = [
     ("tfbs_ctx_assembly_trace", C.c_int, [vp, C.c_int]),
     ("tfbs_batch_assembly_paths", C.c_int, [vp, vp, u32p, C.c_uint32]),
     ("tfbs_ctx_assembly_figures", C.c_int, [vp, u64p]),
+    ("tfbs_ctx_post_figures", C.c_int, [vp, u64p]),
     ("tfbs_batch_region_layout", C.c_int, [vp, C.c_size_t, u32p]),
     ("tfbs_batch_region_hap_runs", C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(C.c_int), u32p, u32p, u32p,
                                             C.c_uint32]),

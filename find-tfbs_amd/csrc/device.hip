@@ -226,6 +226,7 @@ struct tfbs_ctx {
     // lean assemblies assembly_wait ran again in full: all, those that needed the wide spill
     // kernels, those that needed the leftover pass
     uint64_t asm_reruns = 0, asm_reruns_wide = 0, asm_reruns_left = 0;
+    uint64_t asm_reruns_post = 0;     // those that had left the post-scan stage out and met a record or a candidate
     // two slots of block batches (one being made, one copied back and written)
     static constexpr int kBgSlots = 3;  // batches of blocks in flight: two queued while one is written out
     DevBuf<uint8_t> bg_out[kBgSlots], bg_packed[kBgSlots];
@@ -275,6 +276,7 @@ struct tfbs_ctx {
     hipGraphExec_t step_exec = nullptr;
     uint64_t step_sig = 0;       // step_signature() of the graph (or of the last plain step)
     bool step_sig_seen = false;  // the last plain step had step_sig: the next one is captured
+    bool step_asm[4] = {true, true, true, false};  // the graph's asm_wide, asm_leftover, asm_post, asm_post_fused
     bool capturing = false;      // the timing events and asm_ev are left out of a capture
     uint64_t upload_gen = 0;     // tfbs_batch_upload calls (a new batch image: a new graph)
     bool step_graphs = true;     // TFBS_STEP_GRAPH=0: plain launches
@@ -287,6 +289,16 @@ struct tfbs_ctx {
     uint32_t prev_cand = UINT32_MAX;                           // and its scan's candidates past the lists
     bool asm_wide = true, asm_leftover = true;                 // what the enqueued assembly launched
     bool asm_full = false;                                     // (a rerun: everything)
+    // the post-scan stage itself (the rescoring and the spill buckets, launched or in the
+    // scan's tail) is left out when the batch's last checked assembly saw neither a spill
+    // record nor a candidate past the lists: that assembly reads no bucket (asm_args), and
+    // one that then reports either runs again in full.  asm_post: the enqueued assembly
+    // had the stage; asm_post_fused: in the scan kernel's tail
+    bool asm_post = true, asm_post_fused = false;
+    bool asm_post_rerun = false;  // the enqueued assembly is the rerun of one that had left the stage out
+    // the counts of spill_sorted's buckets (AsmArgs::spill_cnt) are the assembly's, at
+    // asm_ctr + kAsmCtrWords (post_scan_kernel, the wide kernels), else check_overflow's spill_bcnt
+    bool spill_cnt_ctr = false;
     // fused post-scan (ScanArgs::post_done): tfbs_step allows it for its lean steps
     // (TFBS_POST_FUSE=0: never); post_fused: the last scan did it (its assembly skips the launch)
     bool post_fuse_env = true, post_fuse_ok = false, post_fused = false;
@@ -504,8 +516,18 @@ static int build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t
     return TFBS_OK;
 }
 
-// asm_ctr's counter words (layout at enqueue_assembly), the spill buckets after them
+// asm_ctr's counter words (layout at enqueue_assembly), the spill buckets after them:
+// per region (and one more) the bucket's record count, then the scatter's fill counter
 constexpr size_t kAsmCtrWords = 24;
+static size_t asm_bucket_words(uint32_t nr) { return 2 * ((size_t)std::max<uint32_t>(1, nr) + 1); }
+
+// A lean assembly without the post-scan stage (tfbs_ctx::asm_post): the batch's last
+// checked assembly saw no spill record and no candidate past the lists (TFBS_ASM_LEAN=2:
+// always -- the tests' rerun).
+static bool asm_skips_post(const tfbs_ctx *ctx) {
+    return ctx->asm_lean_mode != 0 && !ctx->asm_full &&
+           (ctx->asm_lean_mode == 2 || (ctx->prev_spill == 0 && ctx->prev_cand == 0));
+}
 
 // The scan's counters (reference hits per region, the overflow pair) and the
 // assembly's (asm_ctr) zeroed in one launch at the scan's start, instead of three
@@ -603,7 +625,7 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
             m.share[c] = sh ? ctx->sh[c].p : nullptr;
         }
         {
-            const uint32_t na = (uint32_t)(kAsmCtrWords + nr + 1);
+            const uint32_t na = (uint32_t)(kAsmCtrWords + asm_bucket_words(nr));
             if ((rc = ctx->asm_ctr.ensure(na))) return rc;
             hipLaunchKernelGGL(zero3_kernel, dim3(std::min<uint32_t>(256, (std::max(na, nr) + 255) / 256)), dim3(256), 0,
                                ctx->stream, ctx->ref_count.p, nr, ctx->over.p, 2u, ctx->asm_ctr.p, na);
@@ -613,10 +635,11 @@ static int launch_scan(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hits,
         // the post-scan work in the scan's last workgroup when the assembly that follows
         // (tfbs_step) would launch it lean: neither the grid-wide bucketing nor overflow
         // candidates last time (it handles both anyway: too many spill records set
-        // need_wide, and the assembly reruns with the wide kernels)
+        // need_wide, and the assembly reruns with the wide kernels) -- unless that assembly
+        // leaves the stage out altogether
         ctx->post_fused = ctx->post_fuse_ok && ctx->post_fuse_env && ctx->asm_lean_mode != 0 &&
                           !ctx->asm_full && (ctx->asm_lean_mode == 2 || ctx->prev_spill <= kPostSerial) &&
-                          ctx->prev_cand == 0;
+                          ctx->prev_cand == 0 && !asm_skips_post(ctx);
         if (ctx->post_fused) {
             m.post_done = ctx->asm_ctr.p + 21;
             m.post_regions = nr;
@@ -739,6 +762,7 @@ static int check_overflow(tfbs_ctx *ctx, uint32_t n_haps, unsigned long long *hi
                 const int rc = launch_spill_buckets(ctx->over.p, ctx->spill_cap, ctx->spill.p, nr, ctx->spill_bcnt.p,
                                                     ctx->spill_boff.p, ctx->spill_sorted.p, ctx->stream);
                 if (rc) return rc;
+                ctx->spill_cnt_ctr = false;  // (spill_bcnt: its fill counters end at the counts)
             }
             return TFBS_OK;
         }
@@ -771,6 +795,7 @@ static AsmArgs asm_args(tfbs_ctx *ctx, const Batch &B, int mode) {
     a.ref_count = ctx->ref_count.p;
     a.spill_sorted = ctx->spill_sorted.p;
     a.spill_off = ctx->spill_boff.p;
+    a.spill_cnt = ctx->spill_cnt_ctr ? ctx->asm_ctr.p + kAsmCtrWords : ctx->spill_bcnt.p;
     a.spill_count = ctx->plan.m_supers.empty() ? nullptr : ctx->over.p;
     a.spill_cap = ctx->spill_cap;
     a.counts = ctx->counts_live ? ctx->counts.p : nullptr;
@@ -1213,7 +1238,7 @@ static int enqueue_assembly(tfbs_ctx *ctx, Batch &B, bool post) {
     const uint64_t n_keys = (uint64_t)(B.inner.size() / 2) * B.n_slots;
     const uint32_t nr = (uint32_t)B.regions.size();
     if ((rc = ctx->key_first.ensure(std::max<uint64_t>(n_keys, 1))) ||
-        (rc = ctx->key_flags.ensure(std::max<uint64_t>(n_keys, 1))) || (rc = ctx->asm_ctr.ensure(kAsmCtrWords + (size_t)std::max<uint32_t>(1, nr) + 1)) ||
+        (rc = ctx->key_flags.ensure(std::max<uint64_t>(n_keys, 1))) || (rc = ctx->asm_ctr.ensure(kAsmCtrWords + asm_bucket_words(nr))) ||
         (rc = ctx->asm_redo.ensure((size_t)nr + 1)) || (rc = ctx->cor_arena.ensure(ctx->cor_cap)))
         return rc;
     if (!ctx->asm_host) HIP_TRY(hipHostMalloc((void **)&ctx->asm_host, 4 * kAsmCtrWords, hipHostMallocDefault));
@@ -1232,9 +1257,10 @@ static int enqueue_assembly(tfbs_ctx *ctx, Batch &B, bool post) {
     const bool mfma = !ctx->plan.m_supers.empty();
     // the assembly's counters and the spill buckets' (at asm_ctr + kAsmCtrWords): zeroed
     // by the scan for its first assembly, else one memset
+    // (a reassembly without the stage -- the varying lists regrown -- leaves the buckets'
+    // counts as they are: its readers need them)
     if (!(mfma && post && ctx->asm_ctr_zeroed && ctx->n_regions == nr))
-        HIP_TRY(hipMemsetAsync(ctx->asm_ctr.p, 0,
-                               (kAsmCtrWords + (mfma && post ? (size_t)std::max<uint32_t>(1, nr) + 1 : 0)) * 4,
+        HIP_TRY(hipMemsetAsync(ctx->asm_ctr.p, 0, (kAsmCtrWords + (mfma && post ? asm_bucket_words(nr) : 0)) * 4,
                                ctx->stream));
     ctx->asm_ctr_zeroed = false;
     // lean (see tfbs_ctx): left out what the batch's last checked assembly did not need
@@ -1244,18 +1270,29 @@ static int enqueue_assembly(tfbs_ctx *ctx, Batch &B, bool post) {
     if (mfma && post) {  // overflow candidates rescored (once per scan: they append spill records) + spill buckets
         // (without the leftover pass post_scan_kernel copies the overflow counters to
         // asm_ctr[0, 2); asm_ctr[20]: set when the records needed the wide kernels)
+        ctx->asm_post = true;
+        ctx->asm_post_fused = ctx->post_fused;
         if (ctx->post_fused) {  // the scan's last workgroup did it (lean: no wide kernels)
             ctx->asm_wide = false;
+        } else if (asm_skips_post(ctx)) {  // nothing for it last time: no launch, no buckets
+            ctx->asm_post = ctx->asm_wide = false;
         } else if ((rc = launch_post_fused(ctx->last_margs, !ctx->post_done, ctx->asm_ctr.p + 18,
                                            std::max<uint32_t>(1, nr), ctx->asm_ctr.p + kAsmCtrWords, ctx->spill_boff.p,
                                            ctx->spill_sorted.p, ctx->stream, ctx->asm_wide, ctx->asm_ctr.p,
                                            ctx->asm_ctr.p + 20, lean && ctx->prev_cand == 0 ? 1u : 256u))) {
             return rc;
         }
-        ctx->post_done = true;
+        if (ctx->asm_post) {
+            ctx->post_done = true;
+            ctx->spill_cnt_ctr = true;
+        }
     }
     ctx->post_fused = false;
     AsmArgs a = asm_args(ctx, B, 0);
+    // (no stage: no bucket is read -- stale ones least of all -- and key_fast_kernel
+    // reports the scan's overflow counters, whatever they are, for assembly_wait)
+    if (mfma && !ctx->asm_post) a.spill_count = nullptr;
+    a.report_fast = mfma && !ctx->asm_post ? 1u : 0u;
     a.key_first = ctx->key_first.p;
     a.key_flags = ctx->key_flags.p;
     a.var_keys = ctx->var_keys.p;
@@ -1437,10 +1474,15 @@ static int assembly_wait(tfbs_ctx *ctx, Batch &B) {
         int rc;
         // a lean assembly that needed what it left out (more spill records than post_scan_kernel
         // buckets, or regions key_fast_kernel gave up): again with everything
+        // (or a record or a candidate with the post-scan stage left out: whether that one needed
+        // the wide kernels too shows when the rerun has rescored the candidates)
+        const bool need_post = !ctx->asm_post && (nspill || ncand);
         const bool need_wide = !ctx->asm_wide && ctx->asm_host[20], need_left = !ctx->asm_leftover && ctx->asm_host[2];
-        if (need_wide || need_left) {
+        if (need_post || need_wide || need_left) {
             ctx->asm_full = true;
             ctx->asm_reruns++;
+            ctx->asm_reruns_post += need_post ? 1 : 0;
+            ctx->asm_post_rerun = need_post;
             ctx->asm_reruns_wide += need_wide ? 1 : 0;
             ctx->asm_reruns_left += need_left ? 1 : 0;
             rc = enqueue_assembly(ctx, B, true);
@@ -1466,6 +1508,8 @@ static int assembly_wait(tfbs_ctx *ctx, Batch &B) {
             continue;
         }
         ctx->asm_state = 2;
+        ctx->asm_reruns_wide += ctx->asm_post_rerun && nspill > kPostSerial ? 1 : 0;
+        ctx->asm_post_rerun = false;
         ctx->prev_spill = nspill;
         ctx->prev_redo = ctx->asm_host[2];
         ctx->prev_cand = ncand;
@@ -1535,7 +1579,7 @@ static uint64_t step_signature(const tfbs_ctx *ctx, const tfbs_batch *b) {
                        (uint64_t)ctx->counts_live, (uint64_t)ctx->mfma_group_words,
                        (uint64_t)(uintptr_t)ctx->var_owner, (uint64_t)ctx->asm_lean_mode,
                        (uint64_t)(ctx->prev_spill <= kPostSerial), (uint64_t)(ctx->prev_redo == 0),
-                       (uint64_t)(ctx->prev_cand == 0)})
+                       (uint64_t)(ctx->prev_cand == 0), (uint64_t)(ctx->prev_spill == 0)})
         mix(v);
     return h;
 }
@@ -1552,6 +1596,13 @@ static void step_state(tfbs_ctx *ctx, Batch &B) {
     ctx->over_copied = false;
     ctx->asm_batch = &B;
     ctx->asm_state = 1;
+    // what the captured assembly left out (a rerun in full since then changed the flags)
+    ctx->asm_wide = ctx->step_asm[0];
+    ctx->asm_leftover = ctx->step_asm[1];
+    ctx->asm_post = ctx->step_asm[2];
+    ctx->asm_post_fused = ctx->step_asm[3];
+    if (ctx->asm_post) ctx->spill_cnt_ctr = true;
+    ctx->post_done = ctx->asm_post;  // (left out: a rerun in full rescores the candidates)
     B.counts_valid = B.reduced = false;
     B.enc_r0 = B.enc_r1 = 0;
 }
@@ -1603,6 +1654,10 @@ int tfbs_step(tfbs_ctx *ctx, tfbs_batch *b) {
             ctx->step_graph = g;
             ctx->step_exec = x;
             ctx->step_sig = sig;
+            ctx->step_asm[0] = ctx->asm_wide;
+            ctx->step_asm[1] = ctx->asm_leftover;
+            ctx->step_asm[2] = ctx->asm_post;
+            ctx->step_asm[3] = ctx->asm_post_fused;
             HIP_TRY(hipGraphLaunch(ctx->step_exec, ctx->stream));
             HIP_TRY(hipEventRecord(ctx->asm_ev, ctx->stream));
             step_state(ctx, B);
@@ -1661,6 +1716,16 @@ int tfbs_ctx_assembly_figures(tfbs_ctx *ctx, uint64_t out[8]) {
     out[5] = ctx->asm_reruns;
     out[6] = ctx->asm_reruns_wide;
     out[7] = ctx->asm_reruns_left;
+    return TFBS_OK;
+}
+
+int tfbs_ctx_post_figures(tfbs_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (ctx->asm_state != 2 || !ctx->asm_host) return tfbs::fail(TFBS_E_STATE, "no checked assembly on this ctx");
+    out[0] = ctx->asm_post ? 0 : 1;
+    out[1] = ctx->asm_reruns_post;
+    out[2] = ctx->asm_post && ctx->asm_post_fused ? 1 : 0;
+    out[3] = ctx->asm_host[1];
     return TFBS_OK;
 }
 

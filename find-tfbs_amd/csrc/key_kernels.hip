@@ -42,9 +42,14 @@ constexpr uint32_t kAsmRefs = 256;       // reference hits staged in LDS (else r
 constexpr uint32_t kAsmKeyWords = 2048;  // touched-key bitmap: keys handled per key window
 constexpr uint32_t kAsmKeyWin = 32 * kAsmKeyWords;
 
-// Region r's spill records (bucketed: [spill_off[r], spill_off[r + 1]) of spill_sorted).
+// Region r's spill records (bucketed: spill_cnt[r] of them at spill_off[r] of spill_sorted;
+// spill_off[r] means nothing where there is none).
 __device__ __forceinline__ uint2 spill_range(const AsmArgs &A, uint32_t r) {
-    return (A.spill_count && *A.spill_count) ? make_uint2(A.spill_off[r], A.spill_off[r + 1]) : make_uint2(0, 0);
+    if (!A.spill_count || !*A.spill_count) return make_uint2(0, 0);
+    const uint32_t c = A.spill_cnt[r];
+    if (c == 0) return make_uint2(0, 0);
+    const uint32_t o = A.spill_off[r];
+    return make_uint2(o, o + c);
 }
 
 // The inner ranges [k0, k0 + nk) a reference hit (window i of a strand of length L)
@@ -1059,6 +1064,9 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         i = s_tk;
         __syncthreads();
     }
+    // (here, every region's registers dead: at the kernel's start this one line cost the small
+    // shape 18 VGPRs and a wave of occupancy)
+    if (A.report_fast && blockIdx.x == 0 && tid < 2) A.report[tid] = A.report_src ? A.report_src[tid] : 0u;
 }
 
 // Spill bucketing: per-region record counts, their exclusive scan (one

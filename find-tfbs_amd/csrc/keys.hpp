@@ -27,9 +27,11 @@ struct AsmArgs {
     uint32_t mfma;              // 0: the matrix-core kernel did not run (no hit lists, no reference hits)
     // reference hits per region, and the spill records bucketed by region
     const uint32_t *ref_hits, *ref_count;
-    const uint32_t *spill_sorted, *spill_off;
-    // the scan's spill record count (device, ScanArgs::over[0]; 0: spill_off is not
-    // read), bucketed up to spill_cap records
+    // (region r's: [spill_off[r], spill_off[r] + spill_cnt[r]) of spill_sorted; spill_off[r]
+    // is read only where spill_cnt[r] != 0)
+    const uint32_t *spill_sorted, *spill_off, *spill_cnt;
+    // the scan's spill record count (device, ScanArgs::over[0]; 0 or a null pointer:
+    // neither spill_off nor spill_cnt is read), bucketed up to spill_cap records
     const uint32_t *spill_count;
     uint32_t spill_cap;
     uint32_t *counts;           // dense counts: read (LUT/generic slots) / written (mode 1)
@@ -61,6 +63,9 @@ struct AsmArgs {
     // counters; null: zeros) to report[0..1] (null: not)
     const uint32_t *report_src;
     uint32_t *report;
+    // != 0: key_fast_kernel's first workgroups copy them too (an assembly without the
+    // post-scan stage, whose report this is otherwise when the list pass is left out)
+    uint32_t report_fast;
     // key_fast_kernel: workgroup b takes region order[b] (regions by distinct haplotypes,
     // most first: the longest regions start first and do not trail the launch), or b
     const uint32_t *order;

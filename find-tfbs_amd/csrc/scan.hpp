@@ -126,7 +126,7 @@ struct ScanArgs {
     // finish (ticket post_done) does post_scan_kernel's work -- the overflow candidates'
     // rescoring, the overflow counters to post_report, the spill records bucketed by
     // region (post_need_wide set when they are too many) -- instead of a launch after
-    // the scan; post_done null: no fusion
+    // the scan; post_done null: no fusion; post_bcnt as launch_post_fused's bcnt
     uint32_t *post_done;
     uint32_t post_regions;
     uint32_t *post_bcnt, *post_boff, *post_sorted, *post_report, *post_need_wide;
@@ -168,8 +168,10 @@ int launch_mfma_all(const ScanArgs &a, const DevMSuper *supers, uint32_t n_super
                     hipStream_t stream);
 // Rescores the candidates past the waves' lists (after launch_mfma_all on the same stream).
 int launch_post_scan(const ScanArgs &a, hipStream_t stream);
-// The same (when cand) and the spill records' buckets by region (boff[0 .. n_regions],
-// sorted) in one launch; *done and bcnt[0 .. n_regions] must be zero.
+// The same (when cand) and the spill records' buckets by region in one launch: region
+// r's records at [boff[r], boff[r] + bcnt[r]) of sorted, boff[r] written only where
+// bcnt[r] != 0 (the buckets' order in sorted is arbitrary); *done and bcnt's
+// 2 (n_regions + 1) words (the counts, then the scatter's fill counters) must be zero.
 // wide: also the grid-wide spill bucketing (more than kPostSerial records); report /
 // need_wide: post_scan_kernel's optional outputs (see there); cand_grid: the rescoring's
 // workgroups (1 when the batch's last scan had no candidate past the lists: the same

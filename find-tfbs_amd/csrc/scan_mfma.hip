@@ -1209,11 +1209,14 @@ MfmaKernel mfma_all_variant(bool staged, bool unit) {
 // The scan's post-processing in one launch: every workgroup rescores its share of
 // the overflow candidates (cand_over_kernel's work, when `cand`), then the last
 // workgroup to finish -- the one whose ticket on *done (zeroed before) is the
-// grid's last -- buckets the spill records by region (a histogram, an exclusive
-// scan into boff, a scatter into sorted; bcnt n_regions + 1 zeroed before) on its
-// own: spills are rare, and no records (the usual case) costs one counter read.
+// grid's last -- buckets the spill records by region on its own (post_buckets: region
+// r's records end up at [boff[r], boff[r] + bcnt[r]) of sorted, boff[r] written only
+// where bcnt[r] != 0; bcnt: 2 (n_regions + 1) words zeroed before, the counts and the
+// scatter's fill counters): spills are rare, and no records (the usual case) costs
+// one counter read.
 constexpr uint32_t kPostBlock = 256;
 
+// (spill_hist_wide_kernel's, more than kPostSerial records)
 // boff[0 .. n_regions]: the exclusive prefix of the bucket counts (one workgroup of
 // kPostBlock threads) -- each thread a run of consecutive buckets, one block scan of
 // the runs' sums (not one per 256 buckets: 10 000 regions took 40 scans of 16
@@ -1305,15 +1308,28 @@ __device__ void post_buckets(const ScanArgs &A, uint32_t tid, uint32_t n_regions
         if (need_wide && tid == 0) *need_wide = 1u;
         return;
     }
-    for (uint32_t e = tid; e < n; e += NT) atomicAdd(&bcnt[A.spill[3 * (size_t)e] & 0x7FFFFFFFu], 1u);
-    __threadfence();  // (the counters' atomics and boff's stores seen by every thread of the block)
+    // No pass over the regions: the record that finds its region's count at 0 is the
+    // region's leader (bit k of lead: this thread's k-th record) and, the counts final,
+    // takes the region's slots from a cursor in LDS -- the buckets lie in sorted in the
+    // leaders' order.  The fill counters are a second zeroed array, so that bcnt keeps
+    // the counts for the readers (AsmArgs::spill_cnt).
+    static_assert(kPostSerial <= 32 * NT, "a thread's records: one bit each");
+    uint32_t *bfill = bcnt + n_regions + 1;
+    if (tid == 0) s_sum[0] = 0;
+    uint32_t lead = 0;
+    for (uint32_t e = tid, k = 0; e < n; e += NT, k++)
+        if (atomicAdd(&bcnt[A.spill[3 * (size_t)e] & 0x7FFFFFFFu], 1u) == 0) lead |= 1u << k;
+    __threadfence();  // (the counters' atomics seen by every thread of the block)
     __syncthreads();
-    spill_bucket_offsets<NT>(tid, n_regions, bcnt, boff, s_sum);
-    __threadfence();  // (the counters' atomics and boff's stores seen by every thread of the block)
+    for (; lead; lead &= lead - 1) {
+        const uint32_t r = A.spill[3 * (size_t)(tid + (uint32_t)__builtin_ctz(lead) * NT)] & 0x7FFFFFFFu;
+        boff[r] = atomicAdd(&s_sum[0], __atomic_load_n(&bcnt[r], __ATOMIC_RELAXED));
+    }
+    __threadfence();  // (boff's stores seen by every thread of the block)
     __syncthreads();
     for (uint32_t e = tid; e < n; e += NT) {
         const uint32_t r = A.spill[3 * (size_t)e] & 0x7FFFFFFFu;
-        const uint32_t at = boff[r] + atomicAdd(&bcnt[r], 1u);
+        const uint32_t at = boff[r] + atomicAdd(&bfill[r], 1u);
         sorted[3 * (size_t)at] = A.spill[3 * (size_t)e];
         sorted[3 * (size_t)at + 1] = A.spill[3 * (size_t)e + 1];
         sorted[3 * (size_t)at + 2] = A.spill[3 * (size_t)e + 2];

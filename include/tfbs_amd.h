@@ -480,9 +480,19 @@ int tfbs_batch_assembly_paths(tfbs_ctx *ctx, const tfbs_batch *b, uint32_t *mask
  * launched the wide spill bucketing kernels / the leftover pass (a lean assembly leaves out
  * what the batch's last one did not need, TFBS_ASM_LEAN), and since the ctx was made: out[5]
  * lean assemblies run again in full, out[6] those of them that needed the wide kernels (more
- * than 8 192 spill records; the device flag a lean post_scan_kernel sets, cleared by the rerun),
+ * than 8 192 spill records; the device flag a lean post_scan_kernel sets, cleared by the rerun --
+ * or, for an assembly without the post-scan stage, the rerun's record count),
  * out[7] those that needed the leftover pass. */
 int tfbs_ctx_assembly_figures(tfbs_ctx *ctx, uint64_t out[8]);
+/* The post-scan stage (the overflow candidates' rescoring and the spill records' buckets) of the
+ * last checked assembly: out[0] 1 if it was left out (a lean assembly leaves it out when the
+ * batch's last checked assembly saw no spill record and no candidate past the lists; under
+ * TFBS_ASM_LEAN=2 always), out[1] since the ctx was made the assemblies that had left it out,
+ * reported a record or a candidate and ran again in full (they count in out[5] of
+ * tfbs_ctx_assembly_figures too), out[2] 1 if the stage ran in the scan kernel's last
+ * workgroup (TFBS_POST_FUSE=1) and not as a launch, out[3] the scan's candidates past the
+ * waves' lists (out[2] of tfbs_ctx_assembly_figures: its spill records). */
+int tfbs_ctx_post_figures(tfbs_ctx *ctx, uint64_t out[4]);
 /* What the key assembly branches on, from the host batch (no device; the tests' proofs).
  * tfbs_batch_region_layout: out[0] the region's first distinct haplotype in the batch (the
  * scan groups haplotypes TFBS_MFMA_HAPS_PER_BLOCK at a time from 0), out[1] its distinct
