@@ -681,6 +681,15 @@ class RegionBatch:
         check(lib().tfbs_batch_region_hap_runs(self.h, region, h, C.byref(reuses), C.byref(off), C.byref(n), ab, 32))
         return bool(reuses.value), off.value, [(ab[2 * k], ab[2 * k + 1]) for k in range(n.value)]
 
+    def hap_own_runs(self, region, h):
+        """tfbs_batch_region_hap_own_runs: (reuses the reference's hits, offset of its runs in the
+        batch's run array, [(a, b)] its diff runs in its own columns: what the scan reads)."""
+        reuses, off, n = C.c_int(), C.c_uint32(), C.c_uint32()
+        ab = (C.c_uint32 * 64)()
+        check(lib().tfbs_batch_region_hap_own_runs(self.h, region, h, C.byref(reuses), C.byref(off), C.byref(n), ab,
+                                                   32))
+        return bool(reuses.value), off.value, [(ab[2 * k], ab[2 * k + 1]) for k in range(n.value)]
+
     def keys(self, region):
         """count_matches_by_sample for one region: {(bed, (s, e), pattern_id): (L, R)}."""
         L = lib()

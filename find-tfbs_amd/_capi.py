@@ -167,7 +167,9 @@ SIGNATURES = [
     ("tfbs_batch_region_layout", C.c_int, [vp, C.c_size_t, u32p]),
     ("tfbs_batch_region_hap_runs", C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(C.c_int), u32p, u32p, u32p,
                                             C.c_uint32]),
-    ("tfbs_batch_encode", C.c_int, [vp, vp, C.c_size_t, C.c_size_t]),
+    ("tfbs_batch_region_hap_own_runs", C.c_int, [vp, C.c_size_t, C.c_uint32, C.POINTER(C.c_int), u32p, u32p, u32p,
+                                                C.c_uint32]),
+    ("tfbs_batch_encode",C.c_int, [vp, vp, C.c_size_t, C.c_size_t]),
     ("tfbs_batch_encode_flags", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_int]),
     ("tfbs_batch_encode_stats", C.c_int, [vp, u64p]),
     ("tfbs_ctx_rows_bgzf_seconds", C.c_int, [vp, C.POINTER(C.c_double)]),

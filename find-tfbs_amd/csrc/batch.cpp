@@ -1611,6 +1611,23 @@ int tfbs_batch_region_hap_runs(const tfbs_batch *b, size_t region, uint32_t h, i
     return TFBS_OK;
 }
 
+int tfbs_batch_region_hap_own_runs(const tfbs_batch *b, size_t region, uint32_t h, int *reuses, uint32_t *run_off,
+                                   uint32_t *n_runs, uint32_t *ab, uint32_t cap) {
+    if (!b || region >= b->b.regions.size()) return tfbs::fail(TFBS_E_ARG, "bad region");
+    const tfbs::DevRegion &rg = b->b.regions[region];
+    if (h >= rg.hap_count) return tfbs::fail(TFBS_E_ARG, "bad haplotype");
+    const tfbs::DevHap &hp = b->b.haps[rg.hap_begin + h];
+    const bool dedup = (hp.flags & tfbs::HAP_DEDUP) != 0;
+    if (reuses) *reuses = dedup ? 1 : 0;
+    if (run_off) *run_off = dedup ? hp.drun_off : 0;
+    if (n_runs) *n_runs = dedup ? hp.n_druns : 0;
+    for (uint32_t k = 0; ab && dedup && k < hp.n_druns && k < cap; k++) {
+        ab[2 * k] = b->b.druns[2 * (size_t)(hp.drun_off + k)];
+        ab[2 * k + 1] = b->b.druns[2 * (size_t)(hp.drun_off + k) + 1];
+    }
+    return TFBS_OK;
+}
+
 int tfbs_patch_haplotype(uint64_t rs, uint64_t re, size_t nd, const uint64_t *dpos, const uint8_t *dref,
                          const uint32_t *dnref, const uint8_t *dalt, const uint32_t *dnalt, const uint8_t *ref_nucs,
                          const uint64_t *ref_pos, size_t n_ref, uint8_t *out_nucs, uint64_t *out_pos, size_t cap,

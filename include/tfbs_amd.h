@@ -504,10 +504,19 @@ int tfbs_ctx_post_figures(tfbs_ctx *ctx, uint64_t out[4]);
  * (window w of a strand of length L is dirty iff some run [a, b] has a <= w + L - 1 and
  * b >= w; b = UINT32_MAX: to the end; [a, a - 1]: two touching segments): *n_runs of them at
  * *run_off of the batch's run array (key_fast_kernel stages the span from the region's lowest
- * offset to its highest end), the first cap as (a, b) pairs in ab. */
+ * offset to its highest end), the first cap as (a, b) pairs in ab.
+ * tfbs_batch_region_hap_own_runs: the same haplotype's diff runs in its own columns, which
+ * decide the windows the matrix-core scan reads and whose hits it lists (the window lists and
+ * the rescoring's dirty test, with the same predicate over the haplotype's windows); the same
+ * arguments and errors.  The list of tfbs_batch_region_hap_runs itself when every column of
+ * the haplotype stands at its reference column (no indel); otherwise a list of its own, which
+ * that one follows in the run array, and either may be empty while the other is not (equal
+ * *run_off: one list, or no run in the haplotype's own columns). */
 int tfbs_batch_region_layout(const tfbs_batch *b, size_t region, uint32_t out[4]);
 int tfbs_batch_region_hap_runs(const tfbs_batch *b, size_t region, uint32_t h, int *reuses, uint32_t *run_off,
                                uint32_t *n_runs, uint32_t *ab, uint32_t cap);
+int tfbs_batch_region_hap_own_runs(const tfbs_batch *b, size_t region, uint32_t h, int *reuses, uint32_t *run_off,
+                                   uint32_t *n_runs, uint32_t *ab, uint32_t cap);
 /* counts_as_genotypes' per-sample half on the device (main.rs:439-534, SURVEY.md
  * 8(f) f1) for the varying keys of regions [r0, r1) after tfbs_batch_reduce:
  * per key v[s] = C[hap(2s)] + C[hap(2s+1)] over the samples, min / max, the

@@ -1,4 +1,5 @@
 """Shared helpers: run the oracle and the product on the same region inputs."""
+import ctypes
 import os
 import random
 
@@ -53,8 +54,8 @@ def run_oracle(pset, n_samples, beds, regions, chrom="chr1", min_maf=0):
     return keys, rows, stats
 
 
-def build_batch(pset, n_samples, beds, regions):
-    b = T.RegionBatch(pset, n_samples)
+def build_batch(pset, n_samples, beds, regions, build_device=None):
+    b = T.RegionBatch(pset, n_samples, build_device=build_device)
     for name, _ in beds:
         b.add_bed(name)
     for reg in regions:
@@ -111,3 +112,29 @@ def many_variant_regions(n_samples, lmax, n_sites=(64, 90), seed=12):
                 recs.append(("car", es + p, rb, alt, sorted(rnd.sample(range(H), 3))))
         regs.append({"merged": (s, e), "ref": ref, "records": recs})
     return regs
+
+
+def depth_classes(ps):
+    """Per depth class of the matrix-core tiles (strands in ascending length, 64 per tile;
+    a tile of strands of up to 16 columns is class 0, else class 1): (shortest, longest
+    strand, {length: strands}) or None; and the longer patterns' {length: patterns}."""
+    lens = sorted(len(p.weights) for p in ps.to_list() if len(p.weights))
+    short = [L for L in lens if L <= 32]
+    cl = [{}, {}]
+    for t in range(0, len(short), 64):
+        tile = short[t:t + 64]
+        c = cl[1 if max(tile) > 16 else 0]
+        for L in tile:
+            c[L] = c.get(L, 0) + 1
+    longer = {}
+    for L in lens:
+        if L > 32:
+            longer[L] = longer.get(L, 0) + 1
+    return [(min(c), max(c), c) if c else None for c in cl], longer
+
+
+def window_list_entries(sc):
+    """tfbs_ctx_window_lists: the entries of the uploaded batch's window lists, per depth class."""
+    ent, sec = (ctypes.c_uint64 * 2)(), ctypes.c_double()
+    T.check(T.lib().tfbs_ctx_window_lists(sc.h, ent, ctypes.byref(sec)))
+    return [ent[0], ent[1]]

@@ -375,7 +375,8 @@ def test_reference_window_reuse_vs_oracle(tmp_path, monkeypatch, thr, fast_max_u
     """Reference-window reuse (HAP_DEDUP, ref_fixup_kernel) on its edge cases, against
     the oracle: an SNV every haplotype carries (no reference group: the helper copy of
     the reference supplies the hits), N runs in the reference, haplotypes with indels
-    (reused before the first indel, scanned after it), 40 nested inner ranges (the fix-up's path past 32 ranges) and
+    (reused inside every segment, before and after an indel: only the windows meeting a diff
+    run or spanning two segments are scanned), 40 nested inner ranges (the fix-up's path past 32 ranges) and
     p = 0.05 thresholds (over 64 reference hits per region: the overflow list; with
     small candidate lists, the candidate overflow list and its regrowth).  fast_max_u:
     regions of more distinct haplotypes than that leave key_fast_kernel for the list

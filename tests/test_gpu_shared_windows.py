@@ -5,11 +5,10 @@ for its sharers.  Hand-built small regions against the oracle (keys and rows), t
 same with TFBS_SHARE=0, and the window lists' sizes against a brute-force count made
 here from the regions' haplotypes: distinct (region, class, window, bases) among the
 haplotypes that may share, plus every window of the others."""
-import ctypes
-
 import pytest
 
 from helpers import T, build_batch, make_regions_synth, run_oracle, synth_patterns
+from helpers import depth_classes as _classes, window_list_entries as _lists
 
 pytestmark = pytest.mark.gpu
 
@@ -18,25 +17,6 @@ pytestmark = pytest.mark.gpu
 def need_gpu():
     if T.device_count() == 0:
         pytest.fail("gpu test without a visible HIP device")
-
-
-def _classes(ps):
-    """Per depth class of the matrix-core tiles (strands in ascending length, 64 per tile;
-    a tile of strands of up to 16 columns is class 0, else class 1): (shortest, longest
-    strand, {length: strands}) or None; and the longer patterns' {length: patterns}."""
-    lens = sorted(len(p.weights) for p in ps.to_list() if len(p.weights))
-    short = [L for L in lens if L <= 32]
-    cl = [{}, {}]
-    for t in range(0, len(short), 64):
-        tile = short[t:t + 64]
-        c = cl[1 if max(tile) > 16 else 0]
-        for L in tile:
-            c[L] = c.get(L, 0) + 1
-    longer = {}
-    for L in lens:
-        if L > 32:
-            longer[L] = longer.get(L, 0) + 1
-    return [(min(c), max(c), c) if c else None for c in cl], longer
 
 
 def _haplotypes(reg, H):
@@ -102,12 +82,6 @@ def _model(ps, regions, H):
             for L, k in lens.items():
                 scan_windows += k * (sum(1 for i in unshared if i <= n - L) + sum(1 for i, _ in distinct if i <= n - L))
     return (listed if exact else None), removed, (scan_windows if exact else None)
-
-
-def _lists(sc):
-    ent, sec = (ctypes.c_uint64 * 2)(), ctypes.c_double()
-    T.check(T.lib().tfbs_ctx_window_lists(sc.h, ent, ctypes.byref(sec)))
-    return [ent[0], ent[1]]
 
 
 def _check(monkeypatch, ps, n_samples, beds, regions, modes=((False, False), (True, True))):
