@@ -8,11 +8,12 @@ LIBDIR := $(PKG)/lib
 OBJDIR := $(PKG)/lib/obj
 JOBS ?= 8
 
-HOST_SRCS := $(SRC)/patterns.cpp $(SRC)/plan.cpp $(SRC)/plan_dinuc.cpp $(SRC)/mfma.cpp $(SRC)/batch.cpp $(SRC)/group_host.cpp $(SRC)/aggregate.cpp $(SRC)/hits.cpp $(SRC)/best.cpp $(SRC)/scores.cpp $(SRC)/effects.cpp $(SRC)/synth.cpp $(SRC)/io.cpp $(SRC)/inflate.cpp $(SRC)/run.cpp
-HIP_SRCS := $(SRC)/device.hip $(SRC)/scan_kernels.hip $(SRC)/scan_dinuc.hip $(SRC)/scan_hits.hip $(SRC)/scan_best.hip $(SRC)/score_rows.hip $(SRC)/scan_effects.hip $(SRC)/scan_mfma.hip $(SRC)/window_lists.hip $(SRC)/key_kernels.hip $(SRC)/bgzf_gpu.hip $(SRC)/build_gpu.hip
+HOST_SRCS := $(SRC)/patterns.cpp $(SRC)/plan.cpp $(SRC)/plan_dinuc.cpp $(SRC)/mfma.cpp $(SRC)/batch.cpp $(SRC)/group_host.cpp $(SRC)/aggregate.cpp $(SRC)/hits.cpp $(SRC)/best.cpp $(SRC)/scores.cpp $(SRC)/effects.cpp $(SRC)/synth.cpp $(SRC)/score_dist.cpp $(SRC)/io.cpp $(SRC)/inflate.cpp $(SRC)/run.cpp
+HIP_SRCS := $(SRC)/device.hip $(SRC)/scan_kernels.hip $(SRC)/scan_dinuc.hip $(SRC)/scan_hits.hip $(SRC)/scan_best.hip $(SRC)/score_rows.hip $(SRC)/scan_effects.hip $(SRC)/scan_mfma.hip $(SRC)/window_lists.hip $(SRC)/key_kernels.hip $(SRC)/bgzf_gpu.hip $(SRC)/build_gpu.hip $(SRC)/score_dist.hip
 HDRS := $(wildcard $(SRC)/*.hpp) include/tfbs_amd.h
 HOST_OBJS := $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
-HIP_OBJS := $(patsubst $(SRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS))
+# score_dist.hip stands beside score_dist.cpp (its host twin): its object is score_dist_dev.o
+HIP_OBJS := $(patsubst $(OBJDIR)/score_dist.o,$(OBJDIR)/score_dist_dev.o,$(patsubst $(SRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRCS)))
 
 CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter
 # DINUC_K=5: the dinucleotide kernel's other lookup width ("scan_dinuc_kernel"), built beside
@@ -33,6 +34,10 @@ $(OBJDIR)/%.o: $(SRC)/%.cpp $(HDRS)
 $(OBJDIR)/scan_mfma.o: HIPFLAGS += -mllvm -amdgpu-mfma-vgpr-form -ffinite-math-only
 
 $(OBJDIR)/%.o: $(SRC)/%.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
+
+$(OBJDIR)/score_dist_dev.o: $(SRC)/score_dist.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 

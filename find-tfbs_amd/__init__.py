@@ -242,12 +242,56 @@ class PatternSet:
         return list(out[:n])
 
 
-def parse_pwm_files(pwm_file, threshold_dir, pwm_threshold, wanted_pwms, add_reverse_patterns=True, dipwm_file=None):
+    def score_tails(self, i, scores, device=0):
+        """Exact tail(m) = #{x in {A,C,G,T}^L : score(x) >= m} of strand i for every m in scores, as
+        Python ints; the p-value of "score >= m" is tail / 4 ** len(strand).  device: the HIP device
+        that computes the table, -1: the host twin."""
+        n = len(scores)
+        sc = (C.c_int32 * max(1, n))(*scores)
+        lo = (C.c_uint64 * max(1, n))()
+        hi = (C.c_uint64 * max(1, n))()
+        check(lib().tfbs_patterns_score_tails(self.h, device, i, sc, n, lo, hi))
+        return [(hi[k] << 64) | lo[k] for k in range(n)]
+
+    def pvalue_thresholds(self, p, device=0):
+        """One min_score per strand in creation order for the p-value p (0 <= p < 1):
+        max{m : tail(m) > floor(p * 4 ** L)}; an OtherPattern keeps its own."""
+        n = len(self)
+        out = (C.c_int32 * max(1, n))()
+        check(lib().tfbs_patterns_pvalue_thresholds(self.h, device, p, out))
+        return list(out[:n])
+
+    def with_min_scores(self, ms):
+        """A copy whose strand k has min_score ms[k]; ids, names, order and weights stay."""
+        if len(ms) != len(self):
+            raise ValueError("one min_score per strand")
+        arr = (C.c_int32 * max(1, len(ms)))(*ms)
+        h = C.c_void_p()
+        check(lib().tfbs_patterns_with_min_scores(self.h, arr, C.byref(h)))
+        return PatternSet(h)
+
+
+def pvalue_tile_widths():
+    """The bins one workgroup takes in a gather step and in the suffix sum of the device path."""
+    out = (C.c_uint32 * 2)()
+    lib().tfbs_pvalue_tile_widths(out)
+    return out[0], out[1]
+
+
+def parse_pwm_files(pwm_file, threshold_dir, pwm_threshold, wanted_pwms, add_reverse_patterns=True, dipwm_file=None,
+                    pvalue=None, device=0):
     """pattern.rs:37-87.  Returns a PatternSet (index it or .to_list() for Pattern objects).
     dipwm_file: a dinucleotide PWM file (rows of 16 weights, AA AC .. TT) whose pattern ids
-    continue after pwm_file's; pwm_file may then be None."""
+    continue after pwm_file's; pwm_file may then be None.  pvalue: every named definition
+    loads and its strands take PatternSet.pvalue_thresholds' min_score, computed on `device`
+    (-1: the host); threshold_dir may then be None and pwm_threshold is ignored."""
     h = C.c_void_p()
-    if dipwm_file is None:
+    if pvalue is not None:
+        check(lib().tfbs_patterns_from_files_pvalue(_u(pwm_file) if pwm_file is not None else None,
+                                                    _u(dipwm_file) if dipwm_file is not None else None,
+                                                    _u(",".join(wanted_pwms)), 1 if add_reverse_patterns else 0,
+                                                    device, pvalue, C.byref(h)))
+    elif dipwm_file is None:
         check(lib().tfbs_patterns_from_files(_u(pwm_file), _u(threshold_dir), pwm_threshold,
                                              _u(",".join(wanted_pwms)), 1 if add_reverse_patterns else 0,
                                              C.byref(h)))
@@ -1075,7 +1119,7 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
         pwm_threshold, wanted_pwms, output_file, forward_only=False, run_tabix=False, min_maf=0, threads=1,
         after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None,
         hits_output=None, hits_mode="diff", best_output=None, best_mode="diff", effects_output=None,
-        effects_mode="sites", scores_output=None, scores_min_spread=1):
+        effects_mode="sites", scores_output=None, scores_min_spread=1, pwm_pvalue=None):
     """main.rs:234-393 `run` with the reference's argument order; writes the BGZF VCF.
     devices: list of HIP devices; batch g of merged regions runs on devices[g % n] (same
     text for any list; a device may repeat).  hits_output: also write every region's hit
@@ -1085,7 +1129,8 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     effects (EFFECTS_HEADER, then RegionBatch.effects_tsv's lines in effects_mode "sites" or "all");
     scores_output: also write the score rows (RegionBatch.score_rows with min_maf and
     scores_min_spread, POS from 1) there as a second BGZF VCF under the main output's #CHROM line;
-    the main output does not change."""
+    the main output does not change.  pwm_pvalue: the patterns load as parse_pwm_files(pvalue=...)
+    loads them, on the run's first device; pwm_threshold_directory may then be None."""
     a = _capi.tfbs_run_args()
     keep = [_u(x) if x is not None else None for x in (chromosome, bcf, ",".join(bed_files), reference_genome_file,
                                                         wanted_samples, pwm_file, pwm_threshold_directory,
@@ -1111,8 +1156,12 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     bo = _u(best_output) if best_output is not None else None
     a.best_output = bo
     a.best_mode = BEST_MODES[best_mode]
-    x = _capi.tfbs_run_ext_scores()
-    x.size = C.sizeof(_capi.tfbs_run_ext_scores)
+    if pwm_pvalue is None:
+        x = _capi.tfbs_run_ext_scores()
+    else:
+        x = _capi.tfbs_run_ext_pvalue()
+        x.pwm_pvalue = pwm_pvalue
+    x.size = C.sizeof(x)
     so = _u(scores_output) if scores_output is not None else None
     x.scores_output = so
     x.scores_min_spread = scores_min_spread

@@ -88,6 +88,11 @@ class tfbs_run_ext_scores(C.Structure):
     _fields_ = tfbs_run_ext._fields_ + [("scores_output", C.c_char_p), ("scores_min_spread", C.c_uint64)]
 
 
+class tfbs_run_ext_pvalue(C.Structure):
+    """tfbs_run_ext as the header has it since the p-value thresholds (pwm_pvalue at the end)."""
+    _fields_ = tfbs_run_ext_scores._fields_ + [("pwm_pvalue", C.c_double)]
+
+
 # (name, restype, argtypes) for every symbol in include/tfbs_amd.h
 SIGNATURES = [
     ("tfbs_strerror", C.c_char_p, [C.c_int]),
@@ -109,6 +114,12 @@ SIGNATURES = [
     ("tfbs_patterns_mfma_plan", C.c_int, [vp, C.c_uint32, u8p, C.c_size_t, C.POINTER(C.c_size_t),
                                           C.POINTER(tfbs_mfma_super), C.c_size_t, C.POINTER(C.c_size_t), i32p,
                                           C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("tfbs_patterns_score_tails", C.c_int, [vp, C.c_int, C.c_size_t, i32p, C.c_size_t, u64p, u64p]),
+    ("tfbs_patterns_pvalue_thresholds", C.c_int, [vp, C.c_int, C.c_double, i32p]),
+    ("tfbs_patterns_with_min_scores", C.c_int, [vp, i32p, C.POINTER(vp)]),
+    ("tfbs_patterns_from_files_pvalue", C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_double,
+                                                  C.POINTER(vp)]),
+    ("tfbs_pvalue_tile_widths", None, [u32p]),
     ("tfbs_parse_weight", C.c_int, [C.c_char_p, i32p]),
     ("tfbs_parse_threshold_file", C.c_int, [C.c_char_p, C.c_float, i32p]),
     ("tfbs_device_count", C.c_int, [C.POINTER(C.c_int)]),

@@ -12,7 +12,7 @@ static void usage() {
     fprintf(stderr,
             "find-tfbs-amd 1.0.1 (MI355X)\nFind patterns in a VCF file\n\n"
             "USAGE: find-tfbs-amd --chromosome CHROM --input IN --output OUT --reference REF --bed BED[,BED..]\n"
-            "       --pwm_names N1[,N2..] --pwm_file PWM --pwm_threshold_directory DIR --pwm_threshold T\n"
+            "       --pwm_names N1[,N2..] --pwm_file PWM (--pwm_threshold_directory DIR --pwm_threshold T | --pwm_pvalue P)\n"
             "       [--dipwm_file DIPWM] [--hits_output FILE [--hits_mode all|diff]]\n"
             "       [--best_output FILE [--best_mode all|diff]]\n"
             "       [--effects_output FILE [--effects_mode sites|all]]\n"
@@ -21,6 +21,10 @@ static void usage() {
             "       [--tabix] [--verbose] [--device D | --devices D1,D2,.. | --gpus N] [--regions_per_batch N]\n"
             "  --devices: one contiguous block of merged regions per listed HIP device (a device may repeat);\n"
             "  --gpus N: devices 0..N-1.  The output is the same for any device list.\n"
+            "  --pwm_pvalue P (0 < P < 1): every named definition loads and each strand's threshold is the exact one\n"
+            "  of p-value P under a uniform background (the largest top set of scores with probability <= P),\n"
+            "  computed on the run's first device; --pwm_threshold_directory and --pwm_threshold are then not\n"
+            "  required, and ignored when given.\n"
             "  --dipwm_file: dinucleotide PWMs (rows of 16 weights, AA AC .. TT); --pwm_file is then optional\n"
             "  and --pwm_names selects from both files.\n"
             "  --hits_output FILE: also write where the sites are, as BGZF TSV: per merged region and distinct\n"
@@ -99,6 +103,15 @@ int main(int argc, char **argv) {
         }
         else if (k == "--scores_output") x.scores_output = val("--scores_output");
         else if (k == "--scores_min_spread") x.scores_min_spread = strtoull(val("--scores_min_spread"), nullptr, 10);
+        else if (k == "--pwm_pvalue") {
+            char *end = nullptr;
+            const char *v = val("--pwm_pvalue");
+            x.pwm_pvalue = strtod(v, &end);
+            if (end == v || *end || !(x.pwm_pvalue > 0) || !(x.pwm_pvalue < 1)) {
+                fprintf(stderr, "error: --pwm_pvalue is a number above 0 and below 1\n");
+                return 2;
+            }
+        }
         else if (k == "--pwm_threshold_directory") a.pwm_threshold_dir = val(k.c_str());
         else if (k == "--pwm_threshold" || k == "-t") {
             a.pwm_threshold = strtof(val(k.c_str()), nullptr);
@@ -139,7 +152,7 @@ int main(int argc, char **argv) {
         }
     }
     if (!a.chromosome || !a.bcf || !a.output || !a.reference || !a.bed_files || !a.pwm_names ||
-        (!a.pwm_file && !a.dipwm_file) || !a.pwm_threshold_dir || !have_thr) {
+        (!a.pwm_file && !a.dipwm_file) || (!(x.pwm_pvalue > 0) && (!a.pwm_threshold_dir || !have_thr))) {
         usage();
         return 2;
     }

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "patterns.hpp"
+#include "score_dist.hpp"
 #include "tfbs_internal.hpp"
 
 namespace tfbs {
@@ -161,9 +162,8 @@ static std::vector<int32_t> revcomp_di(const std::vector<int32_t> &w16) {
 
 // One definitions file (pattern.rs:37-87): rows of ncol weights (4: a PWM, 16: a
 // dinucleotide PWM), pattern ids from *next_id on.
-static int parse_definitions(const std::string &pwm_file, int ncol, const std::map<std::string, int32_t> &thresholds,
-                             const std::vector<std::string> &wanted, bool add_reverse, uint16_t *next_id,
-                             Patterns *out) {
+int parse_definitions(const std::string &pwm_file, int ncol, const std::map<std::string, int32_t> &thresholds,
+                      const std::vector<std::string> &wanted, bool add_reverse, uint16_t *next_id, Patterns *out) {
     std::ifstream in(pwm_file, std::ios::binary);
     if (!in) return fail(TFBS_E_IO, "Could not open file " + pwm_file);
     std::stringstream ss;
@@ -519,6 +519,39 @@ int tfbs_patterns_from_files(const char *pwm_file, const char *thr_dir, float th
     }
     *out = ps;
     return TFBS_OK;
+}
+
+int tfbs_patterns_with_min_scores(const tfbs_patterns *p, const int32_t *min_scores, tfbs_patterns **out) {
+    if (!p || !out || (!min_scores && !p->p.pats.empty())) return tfbs::fail(TFBS_E_ARG, "null argument");
+    auto *ps = new tfbs_patterns();
+    for (size_t i = 0; i < p->p.pats.size(); i++) {  // (add: a slot cache of its own, the names as p made them)
+        tfbs::Pat q = p->p.pats[i];
+        q.min_score = min_scores[i];
+        ps->p.add(q);
+    }
+    *out = ps;
+    return TFBS_OK;
+}
+
+int tfbs_patterns_from_files_pvalue(const char *pwm_file, const char *dipwm_file, const char *names_csv,
+                                    int add_reverse, int device, double pvalue, tfbs_patterns **out) {
+    if ((!pwm_file && !dipwm_file) || !names_csv || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (int rc = tfbs::dist_check_pvalue(pvalue)) return rc;
+    const std::vector<std::string> wanted = split_names(names_csv);
+    std::map<std::string, int32_t> named;  // every named definition loads
+    for (auto &name : wanted) named[name] = 0;
+    tfbs_patterns loaded;
+    uint16_t next_id = 0;
+    int rc = 0;
+    if (pwm_file) rc = tfbs::parse_definitions(pwm_file, 4, named, wanted, add_reverse != 0, &next_id, &loaded.p);
+    if (!rc && dipwm_file)
+        rc = tfbs::parse_definitions(dipwm_file, 16, named, wanted, add_reverse != 0, &next_id, &loaded.p);
+    if (!rc && loaded.p.pats.empty()) rc = tfbs::fail(TFBS_E_NOPATTERN, "no pattern loaded");
+    if (!rc) rc = tfbs::check_kinds(loaded.p);
+    if (rc) return rc;
+    std::vector<int32_t> ms(loaded.p.pats.size());
+    if ((rc = tfbs::pvalue_thresholds(loaded.p, device, pvalue, ms.data()))) return rc;
+    return tfbs_patterns_with_min_scores(&loaded, ms.data(), out);
 }
 
 size_t tfbs_patterns_count(const tfbs_patterns *p) { return p ? p->p.pats.size() : 0; }

@@ -116,6 +116,10 @@ int parse_pwm_files(const std::string &pwm_file, const std::string &thr_dir, flo
 // of 16, pattern ids continuing); either path may be null (skipped).
 int parse_pwm_files_di(const std::string *pwm_file, const std::string *dipwm_file, const std::string &thr_dir,
                        float thr, const std::vector<std::string> &wanted, bool add_reverse, Patterns *out);
+// One definitions file (rows of ncol = 4 or 16 weights): the definitions named in `wanted`
+// take pattern ids from *next_id on, and those with an entry in `thresholds` load with it.
+int parse_definitions(const std::string &pwm_file, int ncol, const std::map<std::string, int32_t> &thresholds,
+                      const std::vector<std::string> &wanted, bool add_reverse, uint16_t *next_id, Patterns *out);
 const Patterns &patterns_of(const tfbs_patterns *p);
 
 }  // namespace tfbs

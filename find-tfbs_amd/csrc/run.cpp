@@ -654,7 +654,9 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     int effects_mode = TFBS_EFFECTS_SITES;
     const char *scores_output = nullptr;
     uint64_t scores_min_spread = 1;
+    double pwm_pvalue = 0;
     if (ext) {
+        if (ext->size >= offsetof(tfbs_run_ext, pwm_pvalue) + sizeof ext->pwm_pvalue) pwm_pvalue = ext->pwm_pvalue;
         if (ext->size >= offsetof(tfbs_run_ext, scores_output) + sizeof ext->scores_output)
             scores_output = ext->scores_output;
         if (ext->size >= offsetof(tfbs_run_ext, scores_min_spread) + sizeof ext->scores_min_spread &&
@@ -665,7 +667,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
         if (ext->size >= offsetof(tfbs_run_ext, effects_mode) + sizeof ext->effects_mode) effects_mode = ext->effects_mode;
     }
     if (!a || !a->chromosome || !a->bcf || !a->bed_files || !a->reference || (!a->pwm_file && !a->dipwm_file) ||
-        !a->pwm_threshold_dir || !a->pwm_names || !a->output)
+        (!a->pwm_threshold_dir && !(pwm_pvalue > 0)) || !a->pwm_names || !a->output)
         return fail(TFBS_E_ARG, "missing required argument");
     RunSetup S;
     S.a = a;
@@ -682,7 +684,9 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     } warm_join{warm};
 
     // patterns (main.rs:237-250)
-    int rc = a->dipwm_file ? tfbs_patterns_from_files_di(a->pwm_file, a->dipwm_file, a->pwm_threshold_dir,
+    int rc = pwm_pvalue > 0 ? tfbs_patterns_from_files_pvalue(a->pwm_file, a->dipwm_file, a->pwm_names,
+                                                              a->forward_only ? 0 : 1, parse_devices(a)[0], pwm_pvalue, &S.pp)
+             : a->dipwm_file ? tfbs_patterns_from_files_di(a->pwm_file, a->dipwm_file, a->pwm_threshold_dir,
                                                          a->pwm_threshold, a->pwm_names, a->forward_only ? 0 : 1, &S.pp)
                            : tfbs_patterns_from_files(a->pwm_file, a->pwm_threshold_dir, a->pwm_threshold, a->pwm_names,
                                                       a->forward_only ? 0 : 1, &S.pp);

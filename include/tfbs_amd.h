@@ -176,6 +176,53 @@ int tfbs_patterns_mfma_plan(const tfbs_patterns *p, uint32_t lds_kb, uint8_t *im
                             size_t *image_bytes, tfbs_mfma_super *supers, size_t supers_cap, size_t *n_supers,
                             int32_t *meta, size_t meta_cap, size_t *meta_ints);
 
+/* ------------------------------------------------------------------ */
+/* Thresholds from a p-value: exact score distributions                  */
+/* (the reference has no counterpart; README.md, "Thresholds from a      */
+/* p-value")                                                            */
+/* ------------------------------------------------------------------ */
+/* Take a TFBS_KIND_PWM or TFBS_KIND_DIPWM strand of L bases.  S(x) is its score of the
+ * sequence x in {A,C,G,T}^L, summed without wrapping (the count path's score; the mono N
+ * column plays no part); cnt(s) = #{x : S(x) = s}; tail(m) = #{x : S(x) >= m}, an exact
+ * integer of at most 4^L: 4^L for m <= the lowest attainable score, 0 above the highest.
+ * The threshold of a p-value p (a finite double, 0 <= p < 1): x = floor(p * 4^L), exact (p
+ * is a dyadic rational: a shift of its 53-bit mantissa inside 128 bits), and
+ *     min_score = max{ m : tail(m) > x },
+ * always an attained score.  The windows that match (score > min_score) are the largest top
+ * set of scores whose p-value is <= p: parse_threshold_file's rule (the last table row with
+ * pvalue > threshold, matched strictly above) on an exact table.  p = 0 gives the highest
+ * score: nothing matches.
+ * Limits, each TFBS_E_ARG with a message naming the strand: L > 63 (4^L must fit 128 bits);
+ * sum_j max(|lo_j|, |hi_j|) > INT32_MAX over the columns' (rows') lowest and highest weights
+ * (the sums could wrap int32); sum_j (hi_j - lo_j) + 1 > 2^24 bins (mono) or 2^22
+ * (dinucleotide: four tables, one per last base); p outside [0, 1) or not finite.
+ * device >= 0: the HIP device that computes the tables (score_dist.hip), in chunks of
+ * strands whose buffers fit TFBS_PVALUE_SCRATCH_MB (default 256, fractions allowed, read at
+ * the call; at least one strand; the result does not depend on it).  device == -1: the
+ * same definition on the host's threads (TFBS_HOST_THREADS, at most 16) in 128-bit integers.
+ *
+ * tfbs_patterns_score_tails: tail(scores[k]) of strand i (creation order) as two 64-bit
+ * halves.  The denominator is 4^length: the p-value of "score >= m" as a double is
+ * ldexp((double)tail_hi * 18446744073709551616.0 + (double)tail_lo, -2 * (int)length)
+ * (rounded; the integers are exact).  TFBS_E_ARG for a TFBS_KIND_OTHER strand. */
+int tfbs_patterns_score_tails(const tfbs_patterns *p, int device, size_t i, const int32_t *scores, size_t n,
+                              uint64_t *tail_lo, uint64_t *tail_hi);
+/* One min_score per strand in creation order (tfbs_patterns_count entries); a
+ * TFBS_KIND_OTHER strand gets its own min_score back. */
+int tfbs_patterns_pvalue_thresholds(const tfbs_patterns *p, int device, double pvalue, int32_t *min_scores);
+/* A copy of p whose strand k has min_score min_scores[k]; ids, names, order and weights
+ * are p's. */
+int tfbs_patterns_with_min_scores(const tfbs_patterns *p, const int32_t *min_scores, tfbs_patterns **out);
+/* tfbs_patterns_from_files_di's ids and names without a threshold directory: every
+ * definition named in names_csv loads and its strands take tfbs_patterns_pvalue_thresholds'
+ * min_score (on `device`, -1: the host).  A definition the limits refuse fails the call
+ * with a message naming it.  TFBS_E_NOPATTERN when nothing is named. */
+int tfbs_patterns_from_files_pvalue(const char *pwm_file, const char *dipwm_file, const char *names_csv,
+                                    int add_reverse, int device, double pvalue, tfbs_patterns **out);
+/* The bins one workgroup takes in a gather step (out[0]) and in the suffix sum (out[1]) of
+ * score_dist.hip: the spans at which the device path crosses a tile (for its tests). */
+void tfbs_pvalue_tile_widths(uint32_t out[2]);
+
 /* pattern.rs:13-16 parse_weight: (f32(s) * 1000f32).round() as i32. */
 int tfbs_parse_weight(const char *s, int32_t *out);
 /* pattern.rs:18-35 parse_threshold_file: returns 1 (found, *out set), 0 (None) or an error. */
@@ -969,6 +1016,9 @@ typedef struct tfbs_run_ext {
                                        BGZF VCF under the main output's #CHROM line, POS from 1, min_maf as the
                                        main rows'; NULL = none: the run does nothing more than without it */
     uint64_t scores_min_spread;     /* --scores_min_spread: tfbs_batch_score_rows' min_spread (0 counts as 1) */
+    double pwm_pvalue;              /* --pwm_pvalue: > 0: the patterns load by tfbs_patterns_from_files_pvalue on the
+                                       run's first device; pwm_threshold_dir may then be NULL and pwm_threshold is
+                                       ignored.  0: thresholds come from the directory as before */
 } tfbs_run_ext;
 int tfbs_run_ex(const tfbs_run_args *args, const tfbs_run_ext *ext);
 
