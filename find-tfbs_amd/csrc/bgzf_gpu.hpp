@@ -1,4 +1,4 @@
-// Launch interface of the device BGZF row writer (bgzf_gpu.hip), used by device.hip.
+// Launch interface of the device BGZF row writer (bgzf_gpu.hip), used by ctx_rows.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -26,12 +26,7 @@
 #include <vector>
 
 #include "batch.hpp"
-
-#define HIP_OK(expr)                                                                                       \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) return fail(TFBS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));  \
-    } while (0)
+#include "hip_util.hpp"
 
 namespace tfbs {
 namespace {
@@ -169,37 +164,18 @@ __global__ __launch_bounds__(kGrpBlock) void mask_group_kernel(const GrpRegion *
     }
 }
 
-template <typename T>
-struct Buf {
-    T *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return TFBS_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t c = std::max<size_t>(n, 64);
-        HIP_OK(hipMalloc(&p, c * sizeof(T)));
-        cap = c;
-        return TFBS_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+constexpr size_t kGrpFloor = 64;  // the least elements of a grouper buffer
 
 struct GpuGrouper final : DevGrouper {
     int dev = 0;
-    hipStream_t stream = nullptr;
-    Buf<unsigned long long> sig;  // zero between chunks
+    Stream stream;  // (first: destroyed after the buffers)
+    DevBuf<unsigned long long> sig;  // zero between chunks
     bool sig_zero = false;        // sig holds zeros up to its capacity
-    Buf<uint32_t> car, n_groups, first, counts;
-    uint32_t *total_host = nullptr;  // pinned: the chunk's masks
-    Buf<unsigned long long> masks;
-    Buf<GrpRecord> recs;
-    Buf<GrpRegion> regs;
+    DevBuf<uint32_t> car, n_groups, first, counts;
+    PinnedArray<uint32_t> total_host;  // the chunk's masks
+    DevBuf<unsigned long long> masks;
+    DevBuf<GrpRecord> recs;
+    DevBuf<GrpRegion> regs;
     PinnedBytes car_host;
     // membership rows: one allocation per chunk, held by its batch until it goes
     // (recycle), then reused by a later chunk that fits
@@ -210,17 +186,7 @@ struct GpuGrouper final : DevGrouper {
     ~GpuGrouper() override {
         (void)hipSetDevice(dev);
         if (stream) (void)hipStreamSynchronize(stream);
-        sig.release();
-        car.release();
-        n_groups.release();
-        first.release();
-        counts.release();
-        if (total_host) (void)hipHostFree(total_host);
-        masks.release();
-        recs.release();
-        regs.release();
         for (auto &m : memb_all) (void)hipFree(m.first);
-        if (stream) (void)hipStreamDestroy(stream);
     }
     void recycle(std::vector<void *> &allocs) override {
         std::lock_guard<std::mutex> g(memb_mu);
@@ -255,7 +221,7 @@ struct GpuGrouper final : DevGrouper {
     }
     int group(size_t n_car, const std::vector<GrpRecord> &rv, const std::vector<GrpRegion> &rg, uint32_t H,
               GroupOut &out) override {
-        HIP_OK(hipSetDevice(dev));
+        HIP_TRY(hipSetDevice(dev));
         const size_t nr = rg.size();
         out.n_groups.assign(nr, 0);
         out.first.assign(nr, 0);
@@ -268,33 +234,33 @@ struct GpuGrouper final : DevGrouper {
         int rc;
         const size_t sig_n = nr * (size_t)H;
         if (sig_n > sig.cap) sig_zero = false;
-        if ((rc = sig.ensure(sig_n)) || (rc = car.ensure(std::max<size_t>(n_car, 1))) ||
-            (rc = recs.ensure(std::max<size_t>(rv.size(), 1))) || (rc = regs.ensure(nr)) ||
-            (rc = n_groups.ensure(nr + 1)) || (rc = first.ensure(nr)) || (rc = masks.ensure(nr * kGrpMax)) ||
-            (rc = counts.ensure(nr * kGrpMax)))
+        if ((rc = sig.ensure_exact(sig_n, kGrpFloor)) || (rc = car.ensure_exact(std::max<size_t>(n_car, 1), kGrpFloor)) ||
+            (rc = recs.ensure_exact(std::max<size_t>(rv.size(), 1), kGrpFloor)) || (rc = regs.ensure_exact(nr, kGrpFloor)) ||
+            (rc = n_groups.ensure_exact(nr + 1, kGrpFloor)) || (rc = first.ensure_exact(nr, kGrpFloor)) || (rc = masks.ensure_exact(nr * kGrpMax, kGrpFloor)) ||
+            (rc = counts.ensure_exact(nr * kGrpMax, kGrpFloor)))
             return rc;
-        if (!total_host) HIP_OK(hipHostMalloc((void **)&total_host, 4, hipHostMallocDefault));
-        HIP_OK(hipMemsetAsync(n_groups.p + nr, 0, 4, stream));  // the masks' counter
+        if (!total_host) HIP_TRY(total_host.alloc(1));
+        HIP_TRY(hipMemsetAsync(n_groups.p + nr, 0, 4, stream));  // the masks' counter
         if (!sig_zero) {
-            HIP_OK(hipMemsetAsync(sig.p, 0, sig.cap * sizeof(unsigned long long), stream));
+            HIP_TRY(hipMemsetAsync(sig.p, 0, sig.cap * sizeof(unsigned long long), stream));
             sig_zero = true;
         }
-        if (n_car) HIP_OK(hipMemcpyAsync(car.p, car_host.p, n_car * 4, hipMemcpyHostToDevice, stream));
+        if (n_car) HIP_TRY(hipMemcpyAsync(car.p, car_host.p, n_car * 4, hipMemcpyHostToDevice, stream));
         if (!rv.empty())
-            HIP_OK(hipMemcpyAsync(recs.p, rv.data(), rv.size() * sizeof(GrpRecord), hipMemcpyHostToDevice, stream));
-        HIP_OK(hipMemcpyAsync(regs.p, rg.data(), nr * sizeof(GrpRegion), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(recs.p, rv.data(), rv.size() * sizeof(GrpRecord), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(regs.p, rg.data(), nr * sizeof(GrpRegion), hipMemcpyHostToDevice, stream));
         if (!rv.empty())
             hipLaunchKernelGGL(mask_scatter_kernel, dim3((uint32_t)rv.size()), dim3(256), 0, stream, recs.p, car.p,
                                sig.p, H);
         hipLaunchKernelGGL(mask_group_kernel, dim3((uint32_t)nr), dim3(kGrpBlock), 0, stream, regs.p, recs.p, car.p,
                            sig.p, H, mb, stride, n_groups.p, first.p, n_groups.p + nr, masks.p, counts.p);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpyAsync(out.n_groups.data(), n_groups.p, nr * 4, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipMemcpyAsync(out.first.data(), first.p, nr * 4, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipMemcpyAsync(total_host, n_groups.p + nr, 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out.n_groups.data(), n_groups.p, nr * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(out.first.data(), first.p, nr * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(total_host.p, n_groups.p + nr, 4, hipMemcpyDeviceToHost, stream));
         hipError_t e = hipStreamSynchronize(stream);
         if (e == hipSuccess) {
-            const uint32_t tot = *total_host;
+            const uint32_t tot = total_host[0];
             out.masks.resize(tot);
             out.counts.resize(tot);
             if (tot) {
@@ -312,8 +278,8 @@ struct GpuGrouper final : DevGrouper {
         return TFBS_OK;
     }
     int fetch(uint64_t m, uint32_t H, uint16_t *out) override {
-        HIP_OK(hipSetDevice(dev));
-        HIP_OK(hipMemcpy(out, (const void *)(uintptr_t)m, (size_t)H * 2, hipMemcpyDeviceToHost));
+        HIP_TRY(hipSetDevice(dev));
+        HIP_TRY(hipMemcpy(out, (const void *)(uintptr_t)m, (size_t)H * 2, hipMemcpyDeviceToHost));
         return TFBS_OK;
     }
 };
@@ -336,7 +302,7 @@ DevGrouper *make_gpu_grouper(int device) {
     }
     auto *g = new GpuGrouper();
     g->dev = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (hipSetDevice(device) != hipSuccess || g->stream.create() != hipSuccess) {
         delete g;
         fail(TFBS_E_HIP, "device grouping stream");
         return nullptr;

@@ -5,7 +5,7 @@
 //    in two steps (pair_head, PAIR_OPEN), what a wave knows of its pair (PairScan) and the walk
 //    over the pair's windows (WALK_CHUNKS, scored_window, SCORE_WINDOWS).  A kernel keeps what
 //    it does with a chunk's scores.
-//  * Host: the drivers' common state (PairState, first_use), Buf, HITS_TRY, the scratch budget.
+//  * Host: the drivers' common state (PairState, first_use), the scratch budget.
 //
 // A wave owns one (haplotype, strand) pair; its lanes are 64 consecutive windows and it walks
 // the 64-window chunks in ascending order.  A lane takes the bases of its window 16 at a time:
@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "hip_util.hpp"
 #include "hits.hpp"
 #include "scan.hpp"
 
@@ -211,46 +212,22 @@ __device__ __forceinline__ uint32_t scored_window(const PairScan &P, uint32_t i)
     return i < P.nwin ? i : 0;  // (window 0 exists: reads stay inside the haplotype's pads)
 }
 
-template <typename T>
-struct Buf {  // a device buffer that only grows
-    T *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return TFBS_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(TFBS_E_HIP, std::string("hipMalloc (hit lists): ") + hipGetErrorString(e));
-        }
-        cap = n;
-        return TFBS_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 // What the drivers keep on a ctx: the pattern set's tables on the device (build_hit_tables),
 // the chunk's haplotype list, the pinned buffer of the copy-back and the events.
 struct PairState {
-    Buf<DevHitStrand> strands;
-    Buf<int32_t> weights;
+    DevBuf<DevHitStrand> strands;
+    DevBuf<int32_t> weights;
     uint32_t n_strands = 0;
-    Buf<uint32_t> hap_ids;
+    DevBuf<uint32_t> hap_ids;
     PinnedBytes host;
-    hipEvent_t ev[3] = {};
+    Event ev[3];
     // The tables uploaded and n_events events created; a failure reads "<label>: ...".
     int upload(const Patterns &P, hipStream_t stream, int n_events, const char *label) {
         HitTables T;
         build_hit_tables(P, &T);
         n_strands = (uint32_t)T.strands.size();
         int rc;
-        if ((rc = strands.ensure(T.strands.size())) || (rc = weights.ensure(T.weights.size() + 4))) return rc;
+        if ((rc = strands.ensure_exact(T.strands.size())) || (rc = weights.ensure_exact(T.weights.size() + 4))) return rc;
         hipError_t e = hipSuccess;
         if (!T.strands.empty())
             e = hipMemcpyAsync(strands.p, T.strands.data(), T.strands.size() * sizeof(DevHitStrand),
@@ -258,14 +235,9 @@ struct PairState {
         if (e == hipSuccess && !T.weights.empty())
             e = hipMemcpyAsync(weights.p, T.weights.data(), T.weights.size() * 4, hipMemcpyHostToDevice, stream);
         for (int k = 0; k < n_events; k++)
-            if (e == hipSuccess) e = hipEventCreate(&ev[k]);
+            if (e == hipSuccess) e = ev[k].create();
         if (e == hipSuccess) e = hipStreamSynchronize(stream);  // (T goes out of scope)
         return e == hipSuccess ? TFBS_OK : fail(TFBS_E_HIP, std::string(label) + ": " + hipGetErrorString(e));
-    }
-    ~PairState() {
-        strands.release(); weights.release(); hap_ids.release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
     }
     PairSrc src(const ScanImage &img) const {
         return PairSrc{strands.p, weights.p, n_strands, img.haps, img.words, img.nmask};
@@ -286,21 +258,8 @@ int first_use(S **state, const Patterns &P, hipStream_t stream, int n_events, co
     return TFBS_OK;
 }
 
-#define HITS_TRY(expr)                                                                       \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) return fail(TFBS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// The scratch budget of an environment variable in MiB (fractions too; read at the call).
-inline uint64_t scratch_budget(const char *name, double dflt_mb) {
-    const char *env = getenv(name);
-    const double mb = env && *env ? strtod(env, nullptr) : dflt_mb;
-    return mb > 0 ? (uint64_t)std::min(mb * 1048576.0, 9.0e18) : 0;
 }
 
 }  // namespace tfbs

@@ -1,6 +1,6 @@
 // Hit lists (tfbs_batch_hits), best sites (tfbs_batch_best) and variant effects
 // (tfbs_batch_effects): the interfaces of scan_hits.hip, scan_best.hip and scan_effects.hip to
-// device.hip, what they share on the host (the tables, ScanImage, site_range, text_out) and the
+// ctx_outputs.hip, what they share on the host (the tables, ScanImage, site_range, text_out) and the
 // host-only helpers of hits.cpp, best.cpp and effects.cpp.
 #pragma once
 
@@ -85,7 +85,7 @@ int region_baseline(const Batch &B, const RegionH &R, std::vector<std::vector<ui
 // A `hap` line's carrier_ids column: "*" for the baseline, "." without membership.
 std::string carrier_id_text(const Batch &B, const std::vector<std::vector<uint32_t>> &ids, uint32_t h, uint32_t base);
 
-// ---- best sites (tfbs_batch_best): scan_best.hip's interface to device.hip, best.cpp's formatter
+// ---- best sites (tfbs_batch_best): scan_best.hip's interface to ctx_outputs.hip, best.cpp's formatter
 // One (haplotype, strand, range) as the kernel writes it: 16 bytes, one vector store.
 struct alignas(16) DevBestRec {
     int32_t score;
@@ -103,7 +103,7 @@ void best_last_ms(const BestState *s, double out[2]);
 // tfbs_batch_best_tsv's text appended to out (no header line); the records are whole regions.
 int best_tsv(const Batch &B, const tfbs_best *best, size_t n, const std::string &chrom, int mode, std::string &out);
 
-// ---- variant effects (tfbs_batch_effects): scan_effects.hip's interface to device.hip, effects.cpp's formatter
+// ---- variant effects (tfbs_batch_effects): scan_effects.hip's interface to ctx_outputs.hip, effects.cpp's formatter
 // One scored record of a chunk as the kernel reads it: R and A packed into one run of the
 // chunk's words (and N-mask words, has_n), A from base a_base (a multiple of 32) of the run.
 struct DevEffVar {

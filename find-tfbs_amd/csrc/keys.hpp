@@ -1,8 +1,10 @@
-// Launch interface of the key kernels (key_kernels.hip), used by device.hip.
+// Launch interface of the key kernels (key_kernels.hip), used by ctx_assembly.hip and ctx_encode.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 
 #include "batch.hpp"
@@ -81,6 +83,25 @@ struct AsmArgs {
     uint32_t *path;
     uint32_t grid_cap;  // TFBS_KF_GRID: at most this many persistent workgroups per shape (0: what fits)
 };
+
+// The words of the assembly's counter block (tfbs_ctx's asm_ctr: zeroed by the scan or by one
+// memset, its first kAsmCtrWords copied back once per assembly).  The kernels take pointers to
+// the words; only the host names them.
+enum AsmCtr : uint32_t {
+    kCtrOver = 0,      // 0-1: the scan's spill / candidate overflow counts (copied here for assembly_wait)
+    kCtrRedoN = 2,     // regions left to key_asm_kernel (AsmArgs::redo_n)
+    kCtrCorUsed = 3,   // words of the correction arena taken (AsmArgs::cor_used)
+    kCtrVarTot = 4,    // 4-7: the varying keys' and counts' u64 totals (AsmArgs::var_tot)
+    kCtrWhy = 8,       // 8-15: key_fast_kernel's give-up reasons (debug, AsmArgs::why)
+    kCtrNext = 16,     // 16-17: key_fast_kernel's region counters, one per shape (AsmArgs::next)
+    kCtrWgDone = 18,   // 18-19: finished workgroups of post_scan_kernel and of spill_hist_wide_kernel
+    kCtrNeedWide = 20, // set when the spill records needed the wide bucketing kernels
+    kCtrPostDone = 21, // the fused post-scan's done flag (ScanArgs::post_done)
+    kAsmCtrWords = 24, // 22-23 spare; the spill buckets follow
+};
+// The spill buckets behind the counter words: per region (and one more) the bucket's record
+// count, then the scatter's fill counter.
+inline size_t asm_bucket_words(uint32_t nr) { return 2 * ((size_t)std::max<uint32_t>(1, nr) + 1); }
 
 // key_asm_kernel over every region (mode 0 or 1).
 int launch_key_asm(const AsmArgs &a, uint32_t n_regions, hipStream_t stream);

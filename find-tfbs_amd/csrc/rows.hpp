@@ -58,7 +58,7 @@ int build_row_parts(const Batch &B, size_t r0, size_t r1, uint32_t min_maf, uint
                     std::shared_ptr<RowParts> &out, uint64_t *n_rows);
 int plan_from_parts(const Batch &B, RowParts &P, size_t r0, size_t r1, const std::string &chrom, uint32_t *fake,
                     RowPlan &plan);
-// tfbs_batch_rows_bgzf (device.hip) whose POS base is asked for once the call's rows
+// tfbs_batch_rows_bgzf (ctx_rows.hip) whose POS base is asked for once the call's rows
 // are counted: pos_base(n_rows, &base) -- it may block -- sets *fake_position.
 int rows_bgzf_chained(::tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, const char *chromosome,
                       uint32_t min_maf, uint32_t *fake_position, int fd, uint64_t *bytes, uint64_t *n_rows,

@@ -1,5 +1,5 @@
 // Launch interface of the scan kernels (scan_kernels.hip, scan_dinuc.hip, scan_mfma.hip) and of the
-// window-list builder (window_lists.hip), used by device.hip.
+// window-list builder (window_lists.hip), used by ctx_scan.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

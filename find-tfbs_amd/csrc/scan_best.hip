@@ -143,10 +143,9 @@ __global__ __launch_bounds__(kHitBlock) void scan_best_kernel(BestArgs A) {
 }  // namespace
 
 struct BestState : PairState {  // host: a chunk's records, copied back
-    Buf<uint64_t> hap_off;
-    Buf<DevBestRec> recs;
+    DevBuf<uint64_t> hap_off;
+    DevBuf<DevBestRec> recs;
     double ms[2] = {0, 0};
-    ~BestState() { hap_off.release(); recs.release(); }
 };
 
 void best_state_destroy(BestState *s) { delete s; }
@@ -156,7 +155,7 @@ void best_last_ms(const BestState *s, double out[2]) {
 }
 
 int best_prepare(BestState **state, int device, void *stream, const Patterns &P, uint32_t *n_strands) {
-    HITS_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     if (int rc = first_use(state, P, static_cast<hipStream_t>(stream), 2, "best-site tables")) return rc;
     *n_strands = (*state)->n_strands;
     return TFBS_OK;
@@ -168,9 +167,9 @@ int best_launch_chunk(BestState *state, void *stream_, const ScanImage &img, con
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     BestState &S = *state;
     int rc;
-    if ((rc = S.hap_ids.ensure(nh)) || (rc = S.hap_off.ensure(nh)) || (rc = S.recs.ensure(nrec))) return rc;
-    HITS_TRY(hipMemcpyAsync(S.hap_ids.p, ids, 4 * nh, hipMemcpyHostToDevice, stream));
-    HITS_TRY(hipMemcpyAsync(S.hap_off.p, hap_off, 8 * nh, hipMemcpyHostToDevice, stream));
+    if ((rc = S.hap_ids.ensure_exact(nh)) || (rc = S.hap_off.ensure_exact(nh)) || (rc = S.recs.ensure_exact(nrec))) return rc;
+    HIP_TRY(hipMemcpyAsync(S.hap_ids.p, ids, 4 * nh, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(S.hap_off.p, hap_off, 8 * nh, hipMemcpyHostToDevice, stream));
     BestArgs A{};
     A.src = S.src(img);
     A.posrel = img.posrel;
@@ -181,14 +180,14 @@ int best_launch_chunk(BestState *state, void *stream_, const ScanImage &img, con
     A.n_haps = (uint32_t)nh;
     A.rec_cap = nrec;
     A.recs = S.recs.p;
-    HITS_TRY(hipEventRecord(S.ev[0], stream));
+    HIP_TRY(hipEventRecord(S.ev[0], stream));
     hipLaunchKernelGGL(scan_best_kernel, dim3((uint32_t)((nh * S.n_strands + kHitWaves - 1) / kHitWaves)),
                        dim3(kHitBlock), 0, stream, A);
-    HITS_TRY(hipGetLastError());
-    HITS_TRY(hipEventRecord(S.ev[1], stream));
-    HITS_TRY(hipEventSynchronize(S.ev[1]));  // (the host part's clock starts when the kernel is done)
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.ev[1], stream));
+    HIP_TRY(hipEventSynchronize(S.ev[1]));  // (the host part's clock starts when the kernel is done)
     float ms = 0;
-    HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
     *kernel_ms += ms;
     *d_hap_off = S.hap_off.p;
     *recs = S.recs.p;
@@ -242,8 +241,8 @@ int best_run(BestState **state, int device, void *stream_, const Patterns &P, co
                                     &S.ms[0])))
             return rc;
         const double t0 = now_ms();
-        HITS_TRY(hipMemcpyAsync(S.host.p, S.recs.p, nrec * sizeof(DevBestRec), hipMemcpyDeviceToHost, stream));
-        HITS_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(S.host.p, S.recs.p, nrec * sizeof(DevBestRec), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         const DevBestRec *rec = reinterpret_cast<const DevBestRec *>(S.host.p);
         size_t at = out->size();
         out->resize(at + nrec);

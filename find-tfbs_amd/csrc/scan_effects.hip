@@ -134,10 +134,9 @@ inline uint64_t pos_at(const PosRuns &r, uint32_t i) {
 }  // namespace
 
 struct EffectsState : PairState {  // host: a chunk's image and records
-    Buf<uint32_t> image;  // the chunk's descriptors, words and N-mask words: one upload
-    Buf<DevEffRec> recs;
+    DevBuf<uint32_t> image;  // the chunk's descriptors, words and N-mask words: one upload
+    DevBuf<DevEffRec> recs;
     double ms[3] = {0, 0, 0};
-    ~EffectsState() { image.release(); recs.release(); }
 };
 
 void effects_state_destroy(EffectsState *s) { delete s; }
@@ -151,7 +150,7 @@ int effects_run(EffectsState **state, int device, void *stream_, const Patterns 
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (!B.keep_variants) return fail(TFBS_E_STATE, "batch built without tfbs_batch_keep_variants");
     if (B.kept.size() != B.rh.size()) return fail(TFBS_E_STATE, "kept variants out of step with the regions");
-    HITS_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     if (int rc = first_use(state, P, stream, 2, "variant-effect tables")) return rc;
     EffectsState &S = **state;
     S.ms[0] = S.ms[1] = S.ms[2] = 0;
@@ -197,28 +196,28 @@ int effects_run(EffectsState **state, int device, void *stream_, const Patterns 
         memcpy(image.data(), vars.data(), nv * sizeof(DevEffVar));
         if (!words.empty()) memcpy(image.data() + w0, words.data(), 4 * words.size());
         if (!nmask.empty()) memcpy(image.data() + m0, nmask.data(), 4 * nmask.size());
-        if ((rc = S.image.ensure(image.size())) || (rc = S.recs.ensure(nrec)) ||
+        if ((rc = S.image.ensure_exact(image.size())) || (rc = S.recs.ensure_exact(nrec)) ||
             (rc = S.host.reserve(nrec * sizeof(DevEffRec))))
             return rc;
         S.ms[0] += now_ms() - t_prep;
-        HITS_TRY(hipMemcpyAsync(S.image.p, image.data(), 4 * image.size(), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(S.image.p, image.data(), 4 * image.size(), hipMemcpyHostToDevice, stream));
         EffArgs A{};
         A.src = PairSrc{S.strands.p, S.weights.p, S.n_strands, nullptr, S.image.p + w0, S.image.p + m0};
         A.vars = reinterpret_cast<const DevEffVar *>(S.image.p);
         A.n_vars = (uint32_t)nv;
         A.rec_cap = nrec;
         A.recs = S.recs.p;
-        HITS_TRY(hipEventRecord(S.ev[0], stream));
+        HIP_TRY(hipEventRecord(S.ev[0], stream));
         hipLaunchKernelGGL(scan_effects_kernel, dim3((uint32_t)((nrec + kHitWaves - 1) / kHitWaves)), dim3(kHitBlock), 0,
                            stream, A);
-        HITS_TRY(hipGetLastError());
-        HITS_TRY(hipEventRecord(S.ev[1], stream));
-        HITS_TRY(hipEventSynchronize(S.ev[1]));  // (the host part's clock starts when the kernel is done)
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(S.ev[1], stream));
+        HIP_TRY(hipEventSynchronize(S.ev[1]));  // (the host part's clock starts when the kernel is done)
         const double t0 = now_ms();
-        HITS_TRY(hipMemcpyAsync(S.host.p, S.recs.p, nrec * sizeof(DevEffRec), hipMemcpyDeviceToHost, stream));
-        HITS_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(S.host.p, S.recs.p, nrec * sizeof(DevEffRec), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         float ms = 0;
-        HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
         S.ms[1] += ms;
         const DevEffRec *q = reinterpret_cast<const DevEffRec *>(S.host.p);
         for (size_t k = 0; k < nv; k++) {

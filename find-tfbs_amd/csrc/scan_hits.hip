@@ -118,10 +118,9 @@ void build_hit_tables(const Patterns &P, HitTables *out) {
 }
 
 struct HitsState : PairState {  // host: hap_off, then the records, copied back
-    Buf<uint64_t> off, tmp, hap_off;
-    Buf<DevHitRec> recs;
+    DevBuf<uint64_t> off, tmp, hap_off;
+    DevBuf<DevHitRec> recs;
     double ms[4] = {0, 0, 0, 0};
-    ~HitsState() { off.release(); tmp.release(); hap_off.release(); recs.release(); }
 };
 
 void hits_state_destroy(HitsState *s) { delete s; }
@@ -144,7 +143,7 @@ uint64_t chunk_fixed_bytes(uint64_t nh, uint64_t ns) {
 int hits_run(HitsState **state, int device, void *stream_, const Patterns &P, const ScanImage &img,
              const Batch &B, size_t r0, size_t r1, std::vector<tfbs_hit> *out, uint64_t *per_region) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HITS_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     if (int rc = first_use(state, P, stream, 3, "hit tables")) return rc;
     HitsState &S = **state;
     for (double &m : S.ms) m = 0;
@@ -168,32 +167,32 @@ int hits_run(HitsState **state, int device, void *stream_, const Patterns &P, co
         while (nh > 1 && chunk_fixed_bytes(nh, ns) > budget) nh -= std::max<uint64_t>(1, nh / 1024);
         const uint64_t fixed = chunk_fixed_bytes(nh, ns);
         const uint64_t np = nh * ns + 1;
-        if ((rc = S.hap_ids.ensure(nh)) || (rc = S.off.ensure(np)) || (rc = S.tmp.ensure(scan_tmp_words(np))) ||
-            (rc = S.hap_off.ensure(nh + 1)) || (rc = S.host.reserve(8 * (nh + 1))))
+        if ((rc = S.hap_ids.ensure_exact(nh)) || (rc = S.off.ensure_exact(np)) || (rc = S.tmp.ensure_exact(scan_tmp_words(np))) ||
+            (rc = S.hap_off.ensure_exact(nh + 1)) || (rc = S.host.reserve(8 * (nh + 1))))
             return rc;
-        HITS_TRY(hipMemcpyAsync(S.hap_ids.p, ids.data() + start, 4 * nh, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(S.hap_ids.p, ids.data() + start, 4 * nh, hipMemcpyHostToDevice, stream));
         A.hap_ids = S.hap_ids.p;
         A.off = S.off.p;
         A.k0 = 0;
         A.k1 = A.n_chunk = (uint32_t)nh;
-        HITS_TRY(hipEventRecord(S.ev[0], stream));
+        HIP_TRY(hipEventRecord(S.ev[0], stream));
         hipLaunchKernelGGL(scan_hits_kernel<false>, dim3((uint32_t)((np - 1 + kHitWaves - 1) / kHitWaves)),
                            dim3(kHitBlock), 0, stream, A);
-        HITS_TRY(hipGetLastError());
-        HITS_TRY(hipEventRecord(S.ev[1], stream));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(S.ev[1], stream));
         if ((rc = exclusive_scan(S.off.p, np, S.tmp.p, stream))) return rc;
         hipLaunchKernelGGL(hits_hap_offsets_kernel, dim3((uint32_t)(nh / 256 + 1)), dim3(256), 0, stream, S.off.p,
                            (uint32_t)nh, (uint32_t)ns, S.hap_off.p);
-        HITS_TRY(hipGetLastError());
-        HITS_TRY(hipEventRecord(S.ev[2], stream));
-        HITS_TRY(hipEventSynchronize(S.ev[2]));  // (the host part's clock starts when the kernels are done)
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(S.ev[2], stream));
+        HIP_TRY(hipEventSynchronize(S.ev[2]));  // (the host part's clock starts when the kernels are done)
         double t0 = now_ms();
-        HITS_TRY(hipMemcpyAsync(S.host.p, S.hap_off.p, 8 * (nh + 1), hipMemcpyDeviceToHost, stream));
-        HITS_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(S.host.p, S.hap_off.p, 8 * (nh + 1), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         float ms = 0;
-        HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
         S.ms[0] += ms;
-        HITS_TRY(hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
+        HIP_TRY(hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
         S.ms[1] += ms;
         std::vector<uint64_t> hap_off(nh + 1);
         memcpy(hap_off.data(), S.host.p, 8 * (nh + 1));
@@ -212,23 +211,23 @@ int hits_run(HitsState **state, int device, void *stream_, const Patterns &P, co
             const uint64_t nrec = hap_off[k1] - hap_off[k0];
             S.ms[3] += now_ms() - t0;
             if (nrec) {
-                if ((rc = S.recs.ensure(nrec)) || (rc = S.host.reserve(nrec * sizeof(DevHitRec)))) return rc;
+                if ((rc = S.recs.ensure_exact(nrec)) || (rc = S.host.reserve(nrec * sizeof(DevHitRec)))) return rc;
                 A.k0 = (uint32_t)k0;
                 A.k1 = (uint32_t)k1;
                 A.rec_base = hap_off[k0];
                 A.rec_cap = nrec;
                 A.recs = S.recs.p;
-                HITS_TRY(hipEventRecord(S.ev[0], stream));
+                HIP_TRY(hipEventRecord(S.ev[0], stream));
                 hipLaunchKernelGGL(scan_hits_kernel<true>,
                                    dim3((uint32_t)(((k1 - k0) * ns + kHitWaves - 1) / kHitWaves)), dim3(kHitBlock), 0,
                                    stream, A);
-                HITS_TRY(hipGetLastError());
-                HITS_TRY(hipEventRecord(S.ev[1], stream));
-                HITS_TRY(hipEventSynchronize(S.ev[1]));
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(S.ev[1], stream));
+                HIP_TRY(hipEventSynchronize(S.ev[1]));
                 t0 = now_ms();
-                HITS_TRY(hipMemcpyAsync(S.host.p, S.recs.p, nrec * sizeof(DevHitRec), hipMemcpyDeviceToHost, stream));
-                HITS_TRY(hipStreamSynchronize(stream));
-                HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+                HIP_TRY(hipMemcpyAsync(S.host.p, S.recs.p, nrec * sizeof(DevHitRec), hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
                 S.ms[2] += ms;
                 const DevHitRec *rec = reinterpret_cast<const DevHitRec *>(S.host.p);
                 const size_t base = out->size();

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "hip_util.hpp"
 #include "score_dist.hpp"
 
 namespace tfbs {
@@ -216,59 +217,29 @@ void pvalue_x(double p, uint32_t L, uint64_t *lo, uint64_t *hi) {
     } else if (sh > -64) *lo = m >> -sh;
 }
 
-struct DevMem {  // device allocations of one call, freed with it
-    std::vector<void *> ptrs;  // a chunk's
-    void *A = nullptr, *B = nullptr;  // the ping-pong buffers, sized for the call's largest chunk
-    hipStream_t stream = nullptr;
-    int prev_device = -1;
-    ~DevMem() {
-        for (void *p : ptrs) (void)hipFree(p);
-        if (A) (void)hipFree(A);
-        if (B) (void)hipFree(B);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (prev_device >= 0) (void)hipSetDevice(prev_device);
-    }
-    template <typename T>
-    int alloc(T **out, size_t n) {
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(TFBS_E_HIP, std::string("hipMalloc (score distributions): ") + hipGetErrorString(e));
+struct DistDev {  // one call's device state; released in reverse: the buffers, the stream, then the device restored
+    struct Restore {
+        int device = -1;  // the device current before the call
+        ~Restore() {
+            if (device >= 0) (void)hipSetDevice(device);
         }
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return TFBS_OK;
-    }
+    } prev;
+    Stream stream;
+    DevBuf<Bin> A, B;  // the ping-pong buffers, sized for the call's largest chunk
     int buffers(uint64_t bins) {
-        Bin *a, *b;
-        int rc;
-        if ((rc = alloc(&a, bins)) || (rc = alloc(&b, bins))) return rc;
-        ptrs.resize(ptrs.size() - 2);
-        A = a;
-        B = b;
-        return TFBS_OK;
-    }
-    void release() {
-        for (void *p : ptrs) (void)hipFree(p);
-        ptrs.clear();
+        const int rc = A.ensure_exact(std::max<uint64_t>(bins, 1));
+        return rc ? rc : B.ensure_exact(std::max<uint64_t>(bins, 1));
     }
 };
 
-#define DIST_TRY(expr)                                                                                      \
-    do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
-        if (e_ != hipSuccess) return fail(TFBS_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
 template <typename T>
-int upload(DevMem &M, const std::vector<T> &v, T **out) {
-    if (int rc = M.alloc(out, v.size())) return rc;
-    if (!v.empty()) DIST_TRY(hipMemcpyAsync(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, M.stream));
+int upload(DistDev &M, const std::vector<T> &v, DevBuf<T> &out) {
+    if (int rc = out.ensure_exact(std::max<size_t>(v.size(), 1))) return rc;
+    if (!v.empty()) HIP_TRY(hipMemcpyAsync(out.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, M.stream));
     return TFBS_OK;
 }
 
-int open_device(DevMem &M, int device) {
+int open_device(DistDev &M, int device) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
         (void)hipGetLastError();
@@ -277,9 +248,9 @@ int open_device(DevMem &M, int device) {
     if (device >= n) return fail(TFBS_E_ARG, "no HIP device " + std::to_string(device));
     int prev = -1;
     (void)hipGetDevice(&prev);
-    DIST_TRY(hipSetDevice(device));
-    M.prev_device = prev;
-    DIST_TRY(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking));
+    HIP_TRY(hipSetDevice(device));
+    M.prev.device = prev;
+    HIP_TRY(M.stream.create());
     return TFBS_OK;
 }
 
@@ -288,7 +259,7 @@ uint64_t strand_bytes(const DistStrand &s) { return 2 * strand_bins(s) * sizeof(
 
 // The distributions of strands [first, last) of S: their thresholds into thr (by pattern
 // index), or, store_tail (one strand), tail(scores) into lo / hi.
-int run_chunk(DevMem &M, const std::vector<DistStrand> &S, size_t first, size_t last, double p, int32_t *thr,
+int run_chunk(DistDev &M, const std::vector<DistStrand> &S, size_t first, size_t last, double p, int32_t *thr,
               const int32_t *scores, size_t n_scores, uint64_t *lo, uint64_t *hi) {
     const uint32_t n = (uint32_t)(last - first);
     const bool store_tail = scores != nullptr;
@@ -324,62 +295,55 @@ int run_chunk(DevMem &M, const std::vector<DistStrand> &S, size_t first, size_t 
             row[k + 1] = row[k] + tiles;
         }
     }
-    DevDist *dD;
-    uint32_t *d_shift, *d_span, *d_step_begin, *d_scan_begin;
-    Bin *A = (Bin *)M.A, *B = (Bin *)M.B, *tsum;
-    int32_t *d_thr;
+    DevBuf<DevDist> dD;  // the chunk's own, freed on return
+    DevBuf<uint32_t> d_shift, d_span, d_step_begin, d_scan_begin;
+    DevBuf<Bin> tsum;
+    DevBuf<int32_t> d_thr;
+    Bin *const A = M.A.p, *const B = M.B.p;
     int rc;
-    if ((rc = upload(M, D, &dD)) || (rc = upload(M, shift, &d_shift)) || (rc = upload(M, span, &d_span)) ||
-        (rc = upload(M, step_begin, &d_step_begin)) || (rc = upload(M, scan_begin, &d_scan_begin)) ||
-        (rc = M.alloc(&tsum, scan_begin[n])) ||
-        (rc = M.alloc(&d_thr, n)))
+    if ((rc = upload(M, D, dD)) || (rc = upload(M, shift, d_shift)) || (rc = upload(M, span, d_span)) ||
+        (rc = upload(M, step_begin, d_step_begin)) || (rc = upload(M, scan_begin, d_scan_begin)) ||
+        (rc = tsum.ensure_exact(std::max<uint32_t>(scan_begin[n], 1))) || (rc = d_thr.ensure_exact(std::max<uint32_t>(n, 1))))
         return rc;
     for (uint32_t j = 0; j < max_steps; j++) {
-        const uint32_t *row = d_step_begin + (size_t)j * (n + 1);
+        const uint32_t *row = d_step_begin.p + (size_t)j * (n + 1);
         const uint32_t tiles = step_begin[(size_t)j * (n + 1) + n];
-        hipLaunchKernelGGL(dist_step_kernel, dim3(tiles), dim3(kDistStepTile), 0, M.stream, dD, row, n, d_shift, d_span,
+        hipLaunchKernelGGL(dist_step_kernel, dim3(tiles), dim3(kDistStepTile), 0, M.stream, dD.p, row, n, d_shift.p, d_span.p,
                            A, B, j);
     }
     const uint32_t st = scan_begin[n];
-    hipLaunchKernelGGL(dist_tile_sum_kernel, dim3(st), dim3(256), 0, M.stream, dD, d_scan_begin, n, A, B, tsum);
-    hipLaunchKernelGGL(dist_tile_scan_kernel, dim3(n), dim3(256), 0, M.stream, d_scan_begin, tsum);
-    hipLaunchKernelGGL(dist_pick_kernel, dim3(st), dim3(256), 0, M.stream, dD, d_scan_begin, n, A, B, tsum, d_thr,
+    hipLaunchKernelGGL(dist_tile_sum_kernel, dim3(st), dim3(256), 0, M.stream, dD.p, d_scan_begin.p, n, A, B, tsum.p);
+    hipLaunchKernelGGL(dist_tile_scan_kernel, dim3(n), dim3(256), 0, M.stream, d_scan_begin.p, tsum.p);
+    hipLaunchKernelGGL(dist_pick_kernel, dim3(st), dim3(256), 0, M.stream, dD.p, d_scan_begin.p, n, A, B, tsum.p, d_thr.p,
                        store_tail ? 1 : 0);
-    DIST_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (!store_tail) {
         std::vector<int32_t> h(n);
-        DIST_TRY(hipMemcpyAsync(h.data(), d_thr, n * sizeof(int32_t), hipMemcpyDeviceToHost, M.stream));
-        DIST_TRY(hipStreamSynchronize(M.stream));
+        HIP_TRY(hipMemcpyAsync(h.data(), d_thr.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, M.stream));
+        HIP_TRY(hipStreamSynchronize(M.stream));
         for (uint32_t k = 0; k < n; k++) thr[S[first + k].index] = h[k];
     } else {
-        int32_t *d_scores;
-        uint64_t *d_lo, *d_hi;
-        if ((rc = M.alloc(&d_scores, n_scores)) || (rc = M.alloc(&d_lo, n_scores)) || (rc = M.alloc(&d_hi, n_scores)))
-            return rc;
-        DIST_TRY(hipMemcpyAsync(d_scores, scores, n_scores * sizeof(int32_t), hipMemcpyHostToDevice, M.stream));
-        hipLaunchKernelGGL(dist_gather_kernel, dim3((uint32_t)((n_scores + 255) / 256)), dim3(256), 0, M.stream, dD, A, B,
-                           d_scores, (uint32_t)n_scores, d_lo, d_hi);
-        DIST_TRY(hipGetLastError());
-        DIST_TRY(hipMemcpyAsync(lo, d_lo, n_scores * sizeof(uint64_t), hipMemcpyDeviceToHost, M.stream));
-        DIST_TRY(hipMemcpyAsync(hi, d_hi, n_scores * sizeof(uint64_t), hipMemcpyDeviceToHost, M.stream));
-        DIST_TRY(hipStreamSynchronize(M.stream));
+        DevBuf<int32_t> d_scores;
+        DevBuf<uint64_t> d_lo, d_hi;
+        const size_t ns = std::max<size_t>(n_scores, 1);
+        if ((rc = d_scores.ensure_exact(ns)) || (rc = d_lo.ensure_exact(ns)) || (rc = d_hi.ensure_exact(ns))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_scores.p, scores, n_scores * sizeof(int32_t), hipMemcpyHostToDevice, M.stream));
+        hipLaunchKernelGGL(dist_gather_kernel, dim3((uint32_t)((n_scores + 255) / 256)), dim3(256), 0, M.stream, dD.p, A, B,
+                           d_scores.p, (uint32_t)n_scores, d_lo.p, d_hi.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(lo, d_lo.p, n_scores * sizeof(uint64_t), hipMemcpyDeviceToHost, M.stream));
+        HIP_TRY(hipMemcpyAsync(hi, d_hi.p, n_scores * sizeof(uint64_t), hipMemcpyDeviceToHost, M.stream));
+        HIP_TRY(hipStreamSynchronize(M.stream));
     }
-    M.release();
     return TFBS_OK;
-}
-
-uint64_t scratch_budget() {
-    const char *env = getenv("TFBS_PVALUE_SCRATCH_MB");
-    const double mb = env && *env ? strtod(env, nullptr) : 256.0;
-    return mb > 0 ? (uint64_t)std::min(mb * 1048576.0, 9.0e18) : 0;
 }
 
 }  // namespace
 
 int dev_pvalue_thresholds(const std::vector<DistStrand> &S, int device, double p, int32_t *min_scores) {
-    DevMem M;
+    DistDev M;
     if (int rc = open_device(M, device)) return rc;
-    const uint64_t budget = scratch_budget();
+    const uint64_t budget = scratch_budget("TFBS_PVALUE_SCRATCH_MB", 256.0);
     std::vector<size_t> ends;  // chunks of whole strands, at least one
     uint64_t most = 0;
     for (size_t first = 0; first < S.size();) {
@@ -402,7 +366,7 @@ int dev_pvalue_thresholds(const std::vector<DistStrand> &S, int device, double p
 
 int dev_score_tails(const DistStrand &S, int device, const int32_t *scores, size_t n, uint64_t *lo, uint64_t *hi) {
     if (n > UINT32_MAX) return fail(TFBS_E_ARG, "more than 2^32 - 1 scores in one call");
-    DevMem M;
+    DistDev M;
     if (int rc = open_device(M, device)) return rc;
     const std::vector<DistStrand> one{S};
     if (int rc = M.buffers(strand_bins(S))) return rc;

@@ -271,19 +271,19 @@ __global__ __launch_bounds__(kTextBlock) void score_text_kernel(const DevTextRow
 }  // namespace
 
 struct ScoresState {
-    Buf<uint32_t> pid_off, pid_strand;
+    DevBuf<uint32_t> pid_off, pid_strand;
     std::vector<uint16_t> pids;                 // ascending pattern ids
-    Buf<uint64_t> rows;                         // membership rows' addresses
-    Buf<uint16_t> memb, pidx;
-    Buf<uint32_t> pab, pcnt, pair_n, toks;
-    Buf<DevFoldRegion> regs;
-    Buf<int32_t> vals;
-    Buf<uint8_t> none, text;
-    Buf<DevCand> cands;
-    Buf<DevScoreHdr> hdr;
-    Buf<DevTextRow> trows;
+    DevBuf<uint64_t> rows;                         // membership rows' addresses
+    DevBuf<uint16_t> memb, pidx;
+    DevBuf<uint32_t> pab, pcnt, pair_n, toks;
+    DevBuf<DevFoldRegion> regs;
+    DevBuf<int32_t> vals;
+    DevBuf<uint8_t> none, text;
+    DevBuf<DevCand> cands;
+    DevBuf<DevScoreHdr> hdr;
+    DevBuf<DevTextRow> trows;
     PinnedBytes host;
-    hipEvent_t ev[2] = {};
+    Event ev[2];
     double ms[4] = {0, 0, 0, 0};
     int init(const Patterns &P, hipStream_t stream) {
         std::map<uint16_t, std::vector<uint32_t>> by_pid;  // ascending pattern_id -> its strands in creation order
@@ -295,20 +295,13 @@ struct ScoresState {
             off.push_back((uint32_t)strands.size());
         }
         int rc;
-        if ((rc = pid_off.ensure(off.size())) || (rc = pid_strand.ensure(std::max<size_t>(strands.size(), 1)))) return rc;
-        HITS_TRY(hipMemcpyAsync(pid_off.p, off.data(), 4 * off.size(), hipMemcpyHostToDevice, stream));
+        if ((rc = pid_off.ensure_exact(off.size())) || (rc = pid_strand.ensure_exact(std::max<size_t>(strands.size(), 1)))) return rc;
+        HIP_TRY(hipMemcpyAsync(pid_off.p, off.data(), 4 * off.size(), hipMemcpyHostToDevice, stream));
         if (!strands.empty())
-            HITS_TRY(hipMemcpyAsync(pid_strand.p, strands.data(), 4 * strands.size(), hipMemcpyHostToDevice, stream));
-        for (hipEvent_t &e : ev) HITS_TRY(hipEventCreate(&e));
-        HITS_TRY(hipStreamSynchronize(stream));  // (the vectors go out of scope)
+            HIP_TRY(hipMemcpyAsync(pid_strand.p, strands.data(), 4 * strands.size(), hipMemcpyHostToDevice, stream));
+        for (Event &e : ev) HIP_TRY(e.create());
+        HIP_TRY(hipStreamSynchronize(stream));  // (the vectors go out of scope)
         return TFBS_OK;
-    }
-    ~ScoresState() {
-        pid_off.release(); pid_strand.release(); rows.release(); memb.release(); pidx.release(); pab.release();
-        pcnt.release(); pair_n.release(); toks.release(); regs.release(); vals.release(); none.release();
-        text.release(); cands.release(); hdr.release(); trows.release();
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -321,9 +314,9 @@ void scores_last_ms(const ScoresState *s, double out[4]) {
 namespace {
 
 template <typename T>
-int put(Buf<T> &b, const std::vector<T> &v, hipStream_t stream) {
-    if (int rc = b.ensure(std::max<size_t>(v.size(), 1))) return rc;
-    if (!v.empty()) HITS_TRY(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+int put(DevBuf<T> &b, const std::vector<T> &v, hipStream_t stream) {
+    if (int rc = b.ensure_exact(std::max<size_t>(v.size(), 1))) return rc;
+    if (!v.empty()) HIP_TRY(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
     return TFBS_OK;
 }
 
@@ -350,7 +343,7 @@ int scores_run(ScoresState **state, BestState **best, int device, void *stream_,
                const ScanImage &img, const Batch &B, size_t r0, size_t r1, const std::string &chrom, uint32_t min_maf,
                uint64_t min_spread, uint32_t *fake, std::string *out, uint64_t *n_rows) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    HITS_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     *n_rows = 0;
     uint32_t n_strands = 0;
     int rc;
@@ -426,7 +419,7 @@ int scores_run(ScoresState **state, BestState **best, int device, void *stream_,
             else hostr.push_back(i);
         }
         if (!hostr.empty()) {
-            if ((rc = S.host.reserve(hostr.size() * Hp * 2)) || (rc = S.memb.ensure(hostr.size() * Hp))) return rc;
+            if ((rc = S.host.reserve(hostr.size() * Hp * 2)) || (rc = S.memb.ensure_exact(hostr.size() * Hp))) return rc;
             uint16_t *m = reinterpret_cast<uint16_t *>(S.host.p);
             for (size_t k = 0; k < hostr.size(); k++) {
                 const RegionH &R = B.rh[todo[start + hostr[k]]];
@@ -437,11 +430,11 @@ int scores_run(ScoresState **state, BestState **best, int device, void *stream_,
                     if (R.nonref_id[i] < 2 * (size_t)N) row[R.nonref_id[i]] = (uint16_t)R.nonref_local[i];
                 rows[hostr[k]] = (uint64_t)(uintptr_t)(S.memb.p + k * Hp);
             }
-            HITS_TRY(hipMemcpyAsync(S.memb.p, m, hostr.size() * Hp * 2, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(S.memb.p, m, hostr.size() * Hp * 2, hipMemcpyHostToDevice, stream));
         }
-        if ((rc = put(S.rows, rows, stream)) || (rc = S.pab.ensure(nreg * (size_t)kEncMaxPairs)) ||
-            (rc = S.pcnt.ensure(nreg * (size_t)kEncMaxPairs)) || (rc = S.pair_n.ensure(nreg)) ||
-            (rc = S.pidx.ensure(nreg * (size_t)N)))
+        if ((rc = put(S.rows, rows, stream)) || (rc = S.pab.ensure_exact(nreg * (size_t)kEncMaxPairs)) ||
+            (rc = S.pcnt.ensure_exact(nreg * (size_t)kEncMaxPairs)) || (rc = S.pair_n.ensure_exact(nreg)) ||
+            (rc = S.pidx.ensure_exact(nreg * (size_t)N)))
             return rc;
         if ((rc = launch_pair_table(S.rows.p, (uint32_t)nreg, N, S.pab.p, S.pcnt.p, S.pair_n.p, S.pidx.p, stream)))
             return rc;
@@ -469,8 +462,8 @@ int scores_run(ScoresState **state, BestState **best, int device, void *stream_,
                                     &S.ms[0])))
             return rc;
         pair_n.resize(nreg);
-        HITS_TRY(hipMemcpyAsync(pair_n.data(), S.pair_n.p, 4 * nreg, hipMemcpyDeviceToHost, stream));
-        HITS_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipMemcpyAsync(pair_n.data(), S.pair_n.p, 4 * nreg, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         // the candidate rows of the regions whose pairs are listed
         cands.clear();
         uint64_t ntok = 0;
@@ -486,31 +479,31 @@ int scores_run(ScoresState **state, BestState **best, int device, void *stream_,
                 }
             }
         }
-        if ((rc = put(S.regs, regs, stream)) || (rc = S.vals.ensure(nval)) || (rc = S.none.ensure(nval)) ||
-            (rc = put(S.cands, cands, stream)) || (rc = S.hdr.ensure(std::max<size_t>(cands.size(), 1))) ||
-            (rc = S.toks.ensure(std::max<uint64_t>(ntok, 1))))
+        if ((rc = put(S.regs, regs, stream)) || (rc = S.vals.ensure_exact(nval)) || (rc = S.none.ensure_exact(nval)) ||
+            (rc = put(S.cands, cands, stream)) || (rc = S.hdr.ensure_exact(std::max<size_t>(cands.size(), 1))) ||
+            (rc = S.toks.ensure_exact(std::max<uint64_t>(ntok, 1))))
             return rc;
-        HITS_TRY(hipEventRecord(S.ev[0], stream));
+        HIP_TRY(hipEventRecord(S.ev[0], stream));
         hipLaunchKernelGGL(score_fold_kernel,
                            dim3((uint32_t)std::min<uint64_t>((max_vals + kFoldBlock - 1) / kFoldBlock, 1024), (uint32_t)nreg),
                            dim3(kFoldBlock), 0, stream, S.regs.p, d_hap_off, d_recs, nrec, S.pid_off.p, S.pid_strand.p,
                            (uint32_t)npid, S.vals.p, S.none.p);
-        HITS_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         if (!cands.empty()) {
             hipLaunchKernelGGL(score_stats_kernel, dim3((uint32_t)cands.size()), dim3(kStatBlock), 0, stream, S.cands.p,
                                S.vals.p, S.none.p, S.pab.p, S.pcnt.p, S.pair_n.p, S.hdr.p, S.toks.p);
-            HITS_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
-        HITS_TRY(hipEventRecord(S.ev[1], stream));
-        HITS_TRY(hipEventSynchronize(S.ev[1]));
+        HIP_TRY(hipEventRecord(S.ev[1], stream));
+        HIP_TRY(hipEventSynchronize(S.ev[1]));
         float ms = 0;
-        HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
         S.ms[1] += ms;
         double t0 = now_ms();
         if ((rc = S.host.reserve(std::max<size_t>(cands.size(), 1) * sizeof(DevScoreHdr)))) return rc;
         if (!cands.empty())
-            HITS_TRY(hipMemcpyAsync(S.host.p, S.hdr.p, cands.size() * sizeof(DevScoreHdr), hipMemcpyDeviceToHost, stream));
-        HITS_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipMemcpyAsync(S.host.p, S.hdr.p, cands.size() * sizeof(DevScoreHdr), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
         // the rows: picked from the headers, or made on the host for a region whose pairs are not listed
         picked.clear();
         const DevScoreHdr *hd = reinterpret_cast<const DevScoreHdr *>(S.host.p);
@@ -544,9 +537,9 @@ int scores_run(ScoresState **state, BestState **best, int device, void *stream_,
             const uint64_t nv = (uint64_t)R.ranges.size() * npid * U;
             hv.resize(nv);
             hn.resize(nv);
-            HITS_TRY(hipMemcpyAsync(hv.data(), S.vals.p + regs[i].val_off, 4 * nv, hipMemcpyDeviceToHost, stream));
-            HITS_TRY(hipMemcpyAsync(hn.data(), S.none.p + regs[i].val_off, nv, hipMemcpyDeviceToHost, stream));
-            HITS_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipMemcpyAsync(hv.data(), S.vals.p + regs[i].val_off, 4 * nv, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(hn.data(), S.none.p + regs[i].val_off, nv, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
             if ((rc = region_locals(B, R, local))) return rc;
             left.resize(N);
             right.resize(N);
@@ -586,20 +579,20 @@ int scores_run(ScoresState **state, BestState **best, int device, void *stream_,
                 bytes += add;
                 g1++;
             }
-            if ((rc = S.text.ensure(bytes + 16)) || (rc = S.host.reserve(bytes + 16))) return rc;
+            if ((rc = S.text.ensure_exact(bytes + 16)) || (rc = S.host.reserve(bytes + 16))) return rc;
             if (!trows.empty()) {
                 if ((rc = put(S.trows, trows, stream))) return rc;
-                HITS_TRY(hipEventRecord(S.ev[0], stream));
+                HIP_TRY(hipEventRecord(S.ev[0], stream));
                 hipLaunchKernelGGL(score_text_kernel, dim3((uint32_t)trows.size()), dim3(kTextBlock), 0, stream, S.trows.p,
                                    S.toks.p, S.pidx.p, N, S.text.p, bytes);
-                HITS_TRY(hipGetLastError());
-                HITS_TRY(hipEventRecord(S.ev[1], stream));
-                HITS_TRY(hipEventSynchronize(S.ev[1]));
-                HITS_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(S.ev[1], stream));
+                HIP_TRY(hipEventSynchronize(S.ev[1]));
+                HIP_TRY(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
                 S.ms[2] += ms;
                 t0 = now_ms();
-                HITS_TRY(hipMemcpyAsync(S.host.p, S.text.p, bytes, hipMemcpyDeviceToHost, stream));
-                HITS_TRY(hipStreamSynchronize(stream));
+                HIP_TRY(hipMemcpyAsync(S.host.p, S.text.p, bytes, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipStreamSynchronize(stream));
             } else {
                 t0 = now_ms();
             }

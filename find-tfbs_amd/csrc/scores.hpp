@@ -1,5 +1,5 @@
 // Score rows (tfbs_batch_score_rows; include/tfbs_amd.h, "Score rows"): the interface of
-// score_rows.hip to device.hip, and the host-only definition (scores.cpp) that the device's
+// score_rows.hip to ctx_outputs.hip, and the host-only definition (scores.cpp) that the device's
 // text equals byte for byte.
 #pragma once
 

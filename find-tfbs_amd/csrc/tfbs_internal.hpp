@@ -1,7 +1,9 @@
 // Internal declarations shared by the host C++ and the HIP translation units.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -11,6 +13,13 @@ namespace tfbs {
 
 // Sets this thread's last-error message and returns code.
 int fail(int code, const std::string &msg);
+
+// The scratch budget of an environment variable in MiB (fractions too; read at the call).
+inline uint64_t scratch_budget(const char *name, double dflt_mb) {
+    const char *env = getenv(name);
+    const double mb = env && *env ? strtod(env, nullptr) : dflt_mb;
+    return mb > 0 ? (uint64_t)std::min(mb * 1048576.0, 9.0e18) : 0;
+}
 
 // util.rs:4-16 to_nucleotide: ASCII -> 0..4, or -1.
 inline int to_nuc(uint8_t c) {

@@ -277,3 +277,39 @@ def test_prep_overlap_same_batch(tmp_path, indel, monkeypatch):
                    [(b.region_stats(r), b.input_digest(r)) for r in range(b.num_regions)])
     assert got["0"][0] == 300
     assert got["0"] == got["1"]
+
+
+def test_write_out_keeps_order_on_append_descriptor(tmp_path):
+    """write_out (ctx_rows.hip: the rows' file writes) sends a large write out as positioned
+    pieces on a few threads, from the descriptor's offset.  An O_APPEND descriptor ignores a
+    pwrite's offset: every piece goes to the file's end, in whatever order the threads get there,
+    and the offset computed from where the descriptor stood is not where the bytes went.  So the
+    append case starts with the offset away from the end (at 0, behind 4 bytes written): positioned
+    pieces leave it at n, in-order writes at the file's end, 4 + n -- whatever the threads' order.
+    Four pieces (160 MiB and more) and two rounds also give the pieces' order its chances.  The
+    plain descriptor keeps the split: the bytes land at its offset.  A host helper without a
+    C-ABI entry point: called by its C++ name."""
+    import ctypes
+
+    import numpy as np
+    fn = getattr(T.lib(), "_ZN4tfbs9write_outEiPKcm")  # int tfbs::write_out(int, const char *, unsigned long)
+    fn.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_uint64]
+    fn.restype = ctypes.c_int
+    n = (160 << 20) + 12345  # (four pieces of 32 MiB and more)
+    data = ((np.arange(n, dtype=np.uint64) * 2654435761) >> 13).astype(np.uint8).tobytes()
+    for flags, rounds in ((os.O_APPEND, 2), (0, 1)):
+        for k in range(rounds):
+            path = str(tmp_path / "out")
+            fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC | flags, 0o600)
+            try:
+                os.write(fd, b"head")
+                if flags:
+                    os.lseek(fd, 0, os.SEEK_SET)  # (an append descriptor writes at the end wherever it stands)
+                assert fn(fd, data, n) == 0
+                assert os.lseek(fd, 0, os.SEEK_CUR) == 4 + n == os.fstat(fd).st_size, (flags, k)
+                os.write(fd, b"tail")
+            finally:
+                os.close(fd)
+            got = open(path, "rb").read()
+            assert len(got) == n + 8 and got[:4] == b"head" and got[-4:] == b"tail", (flags, k)
+            assert got[4:-4] == data, (flags, k)
