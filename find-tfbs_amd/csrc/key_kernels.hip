@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 #include "keys.hpp"
 
@@ -478,9 +479,30 @@ __device__ __forceinline__ uint32_t cor_key(uint32_t c) { return c >> 12; }
 __device__ __forceinline__ bool cor_neg(uint32_t c) { return (c >> 11) & 1u; }
 __device__ __forceinline__ uint32_t cor_hap(uint32_t c) { return c & 2047u; }
 
+// A placement the region body is compiled for (KfTyped: every list it names sits in
+// LDS, its accesses are DS instructions) or finds out as it runs (KfAny: a branch in
+// front of a DS or a global instruction); no pointer that may be either reaches a load.
+using KfTyped = std::true_type;
+using KfAny = std::false_type;
+// KfAny's global side goes through pointers of the global address space: the branch's
+// two loads then differ in type, and the compiler cannot merge them into one load
+// through a pointer chosen at run time (a FLAT instruction, which waits on both counters).
+typedef uint32_t kf_u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t ld_global(const uint32_t *p) {
+    return *(const __attribute__((address_space(1))) uint32_t *)p;
+}
+__device__ __forceinline__ uint2 ld_global(const uint2 *p) {
+    const kf_u32x2 v = *(const __attribute__((address_space(1))) kf_u32x2 *)p;
+    return make_uint2(v.x, v.y);
+}
+__device__ __forceinline__ void st_global(uint32_t *p, uint32_t v) {
+    *(__attribute__((address_space(1))) uint32_t *)p = v;
+}
+
 // Appends v from the wave's lanes with want set, in lane order (one LDS atomic
-// per wave); *n counts every attempt (> cap: overflow).
-__device__ __forceinline__ void wave_push(uint32_t *list, uint32_t *n, uint32_t cap, bool want, uint32_t v) {
+// per wave), with put(slot, v); *n counts every attempt (> cap: overflow).
+template <class Put>
+__device__ __forceinline__ void wave_push(Put &&put, uint32_t *n, uint32_t cap, bool want, uint32_t v) {
     const uint64_t m = __ballot(want);
     if (!m) return;
     const uint32_t lane = threadIdx.x & 63, leader = (uint32_t)__builtin_ctzll(m);
@@ -489,7 +511,7 @@ __device__ __forceinline__ void wave_push(uint32_t *list, uint32_t *n, uint32_t 
     base = (uint32_t)__shfl((int)base, (int)leader);
     if (want) {
         const uint32_t at = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-        if (at < cap) list[at] = v;
+        if (at < cap) put(at, v);
     }
 }
 
@@ -633,8 +655,17 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         return (h.flags & HAP_DEDUP) ? (h.rrun_off - run0) | (h.n_rruns << 16) : kFNone;
     };
     // the runs in LDS when they fit, else read from global memory (L2)
-    const uint2 *const runs = nruns <= kFRuns ? s_run : reinterpret_cast<const uint2 *>(A.druns) + run0;
-    if (nruns <= kFRuns)
+    const bool runs_lds = nruns <= kFRuns;
+    const uint2 *const druns = reinterpret_cast<const uint2 *>(A.druns) + (nruns ? run0 : 0u);
+    auto run_at = [&](auto typed, uint32_t k) -> uint2 {  // run k of the region's, by placement
+        if constexpr (decltype(typed)::value) {
+            return s_run[k];
+        } else {
+            if (runs_lds) return s_run[k];
+            return ld_global(druns + k);
+        }
+    };
+    if (runs_lds)
         for (uint32_t k = tid; k < nruns; k += kFBlock)
             s_run[k] = make_uint2(A.druns[2 * (run0 + k)], A.druns[2 * (run0 + k) + 1]);
     // reference hits: the region's list, then its spill records of kind 1
@@ -659,13 +690,12 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     if (nref > kFRefs) return give_up(3);
     // D: per HAP_DEDUP haplotype the reference hits in its dirty windows (a run
     // [a, b] meets the columns [w, w + L - 1] of window w).  Up to 64 Ki (haplotype,
-    // reference hit) pairs are tested pairwise -- a wave's lanes are hpw haplotypes x
-    // rpl hits, every run of the lane's haplotype tried (<= 16) -- so the waves share
-    // the work and no lane walks a chain of LDS reads; past that the hits are sorted
+    // reference hit) pairs are tested pairwise, a lane per haplotype: the lane reads
+    // each of its runs (<= 16) once and tries it on 64 reference hits at a time --
+    // s_ref[p] is the same word for the whole wave, a broadcast read with no chain
+    // behind it -- and keeps the dirty hits as a bit mask; past that the hits are sorted
     // by window and each haplotype walks its runs over them (a hit in [a - 31, b] of
     // run [a, b] tested once: runs ascend, the cursor only moves forward).
-    // f(l, ref hit, dirty): in pairwise mode called by every lane of the wave together
-    // (uniform = true), else only for dirty pairs.
     const bool pairwise = (uint64_t)U * nref <= 65536;
     if (!pairwise) pw |= TFBS_PATH_WALK;
     if (!pairwise) {  // the reference hits by window (rank sort; ties by list position)
@@ -683,54 +713,66 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         __syncthreads();
     }
     stamp(2, wall_clock64());
-    const uint32_t rpl = nref <= 1 ? 1u : nref >= 64 ? 64u : 1u << (32 - __clz(nref - 1));  // hits per lane group
-    const uint32_t hpw = 64 / rpl;                                                         // haplotypes per wave
-    auto each_dirty = [&](auto &&f) {
-        if (!nref) return;
-        if (pairwise) {
-            for (uint32_t l0 = wave * hpw; l0 < U; l0 += kFWaves * hpw) {
-                const uint32_t l = l0 + lane / rpl;
-                for (uint32_t p0 = 0; p0 < nref; p0 += rpl) {
-                    const uint32_t p = p0 + lane % rpl;
-                    uint4 q = make_uint4(0, 0, 0, 0);
-                    bool dirty = false;
-                    if (l < U && p < nref) {
-                        const uint32_t x = hap_info(l);
-                        if (x != kFNone) {
-                            q = s_ref[p];
-                            const uint32_t k0 = x & 0xFFFFu, k1 = k0 + (x >> 16);
-                            for (uint32_t k = k0; k < k1 && !dirty; k++)
-                                dirty = run_meets(runs[k].x, runs[k].y, q.y, q.z & 0xFFFFu);
-                        }
-                    }
-                    f(l, q, dirty, true);
+    // f(l, p0, m) by every lane of the wave together: bit p of m says that reference hit
+    // p0 + p is dirty for haplotype l (m = 0 for a lane past U or without reuse)
+    auto dirty_masks = [&](auto typed, auto &&f) {
+        for (uint32_t l0 = wave * 64; l0 < U; l0 += kFBlock) {
+            const uint32_t l = l0 + lane;
+            const uint32_t x = l < U ? hap_info(l) : kFNone;
+            const uint32_t k0 = x == kFNone ? 0u : x & 0xFFFFu, k1 = x == kFNone ? 0u : k0 + (x >> 16);
+            for (uint32_t p0 = 0; p0 < nref; p0 += 64) {
+                const uint32_t np = min(64u, nref - p0);
+                // lane p holds hit p0 + p's first and last column; the walk below reads them
+                // lane by lane into scalars (v_readlane: no LDS read, nothing to wait for).
+                // The run loop is the wave's: it goes on while any lane has a run left, a lane
+                // past its own tries a run that meets nothing, so every lane stays switched on
+                uint32_t rw = 0, re = 0;
+                if (lane < np) {
+                    const uint4 q = s_ref[p0 + lane];
+                    rw = q.y;
+                    re = q.y + (q.z & 0xFFFFu) - 1;
                 }
+                uint64_t m = 0;
+                for (uint32_t i = 0; __ballot(i < k1 - k0) != 0; i++) {
+                    uint2 ab = make_uint2(0xFFFFFFFFu, 0u);
+                    if (i < k1 - k0) ab = run_at(typed, k0 + i);
+                    for (uint32_t p = 0; p < np; p++) {  // (run_meets: a <= w + L - 1 and b >= w)
+                        const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)rw, (int)p);
+                        const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)re, (int)p);
+                        if (ab.x <= e && ab.y >= w) m |= 1ull << p;
+                    }
+                }
+                f(l, p0, m);
             }
-            return;
         }
+    };
+    // f(l, reference hit) for every dirty pair, each lane on its own
+    auto dirty_walk = [&](auto typed, auto &&f) {
         for (uint32_t l = tid; l < U; l += kFBlock) {
             const uint32_t x = hap_info(l);
             if (x == kFNone) continue;
             const uint32_t k0 = x & 0xFFFFu, k1 = k0 + (x >> 16);
             uint32_t p = 0;
             for (uint32_t k = k0; k < k1 && p < nref; k++) {
-                const uint32_t a = runs[k].x, b = runs[k].y;
+                const uint2 ab = run_at(typed, k);
+                const uint32_t a = ab.x, b = ab.y;
                 const uint32_t lo = a >= kMChunkCols * kMMaxChunks - 1 ? a - (kMChunkCols * kMMaxChunks - 1) : 0u;
                 while (p < nref && s_ref[p].y < lo) p++;
                 for (; p < nref && s_ref[p].y <= b; p++) {
                     const uint4 q = s_ref[p];
                     bool dirty = false;
-                    for (uint32_t k2 = k0; k2 < k1 && !dirty; k2++)
-                        dirty = run_meets(runs[k2].x, runs[k2].y, q.y, q.z & 0xFFFFu);
-                    if (dirty) f(l, q, true, false);
+                    for (uint32_t k2 = k0; k2 < k1 && !dirty; k2++) {
+                        const uint2 r2 = run_at(typed, k2);
+                        dirty = run_meets(r2.x, r2.y, q.y, q.z & 0xFFFFu);
+                    }
+                    if (dirty) f(l, q);
                 }
             }
         }
     };
-    // the slot of a lane's first of c entries: one counter atomic per wave (an
-    // inclusive scan of the lanes' counts) when the wave calls together, else per lane
-    auto slots = [&](uint32_t c, bool uniform, uint32_t *ctr) -> uint32_t {
-        if (!uniform) return atomicAdd(ctr, c);
+    // the slot of a lane's first of c entries, the wave calling together: one counter
+    // atomic per wave (an inclusive scan of the lanes' counts)
+    auto slots = [&](uint32_t c, uint32_t *ctr) -> uint32_t {
         if (!__ballot(c > 1)) {  // (one entry per lane at most: a ballot prefix)
             const uint64_t m = __ballot(c != 0);
             if (!m) return 0;
@@ -751,37 +793,39 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         if (lane == 0 && tot) base = atomicAdd(ctr, tot);
         return (uint32_t)__shfl((int)base, 0) + x - c;
     };
+    // a lane's corrections from its mask (one entry per inner range of each dirty hit),
+    // put(slot, entry) from one slot reservation per wave; returns their count
+    auto list_mask = [&](uint32_t l, uint32_t p0, uint64_t m, uint32_t *ctr, auto &&put) -> uint32_t {
+        uint32_t c = 0;
+        for (uint64_t b = m; b; b &= b - 1) c += __popc(s_ref[p0 + (uint32_t)__builtin_ctzll(b)].w);
+        uint32_t at = slots(c, ctr);
+        for (uint64_t b = m; b; b &= b - 1) {
+            const uint4 q = s_ref[p0 + (uint32_t)__builtin_ctzll(b)];
+            for (uint32_t w = q.w; w; w &= w - 1, at++) put(at, cor_entry(q.x + __builtin_ctz(w), l, 1));
+        }
+        return c;
+    };
     // pairwise mode lists the dirty corrections while counting them, at the top of
     // s_cor downwards (the first kFCor); the walk lists them in a second pass
-    // (a wave of at most 64 pairwise steps keeps a bit per step and lists its
-    // corrections after the pass: one slot reservation for the wave, no atomic per step)
-    const uint32_t n_p = (nref + rpl - 1) / rpl;
-    const uint32_t n_l0 = U > wave * hpw ? (U - wave * hpw + kFWaves * hpw - 1) / (kFWaves * hpw) : 0u;
-    const bool stepbits = pairwise && n_l0 * n_p <= 64;
-    uint32_t nd = 0, it = 0;
-    uint64_t dm = 0;  // steps whose pair is dirty
-    each_dirty([&](uint32_t l, const uint4 &q, bool dirty, bool uniform) {
-        const uint32_t c = dirty ? __popc(q.w) : 0u;
-        nd += c;
-        if (!uniform) return;
-        if (stepbits) {
-            if (c) dm |= 1ull << it;
-            it++;
-            return;
-        }
-        uint32_t at = slots(c, true, &s_ndirty);
-        for (uint32_t m = q.w; c && m; m &= m - 1, at++)
-            if (at < kFCor) s_cor[kFCor - 1 - at] = cor_entry(q.x + __builtin_ctz(m), l, 1);
-    });
-    if (stepbits && nref) {
-        uint32_t at = slots(nd, true, &s_ndirty);
-        for (uint64_t m = dm; m; m &= m - 1) {
-            const uint32_t k = (uint32_t)__builtin_ctzll(m);
-            const uint32_t l = wave * hpw + (k / n_p) * kFWaves * hpw + lane / rpl;
-            const uint4 q = s_ref[(k % n_p) * rpl + lane % rpl];
-            for (uint32_t b = q.w; b; b &= b - 1, at++)
-                if (at < kFCor) s_cor[kFCor - 1 - at] = cor_entry(q.x + __builtin_ctz(b), l, 1);
-        }
+    // (TFBS_PATH_STEPBITS: the figure the report has carried since a wave kept one bit
+    // per pairwise step of hpw haplotypes x rpl hits -- wave 0 had at most 64 of them)
+    const uint32_t rpl = nref <= 1 ? 1u : nref >= 64 ? 64u : 1u << (32 - __clz(nref - 1));
+    const uint32_t hpw = 64 / rpl, n_p = (nref + rpl - 1) / rpl;
+    const bool stepbits = pairwise && (U + kFWaves * hpw - 1) / (kFWaves * hpw) * n_p <= 64;
+    uint32_t nd = 0;
+    if (nref) {
+        auto count_and_list = [&](auto typed) {
+            if (pairwise)
+                dirty_masks(typed, [&](uint32_t l, uint32_t p0, uint64_t m) {
+                    nd += list_mask(l, p0, m, &s_ndirty, [&](uint32_t at, uint32_t v) {
+                        if (at < kFCor) s_cor[kFCor - 1 - at] = v;
+                    });
+                });
+            else
+                dirty_walk(typed, [&](uint32_t, const uint4 &q) { nd += __popc(q.w); });
+        };
+        if (runs_lds) count_and_list(KfTyped{});
+        else count_and_list(KfAny{});
     }
     uint32_t nD = 0;
     (void)block_excl_scan<kFWaves>(nd, s_w, nD);
@@ -803,9 +847,31 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     __syncthreads();
     if (!in_lds && s_arena == kFNone) return give_up(4);  // the host grows the arena for the next call
     stamp(3, wall_clock64());
-    uint32_t *const cor = in_lds ? s_cor : A.cor_arena + s_arena;
+    uint32_t *const cor_g = A.cor_arena + (in_lds ? 0u : s_arena);  // (the arena share: global memory)
+    auto cor_ld = [&](auto typed, uint32_t e) -> uint32_t {  // entry e of the list, by placement
+        if constexpr (decltype(typed)::value) {
+            return s_cor[e];
+        } else {
+            if (in_lds) return s_cor[e];
+            return ld_global(cor_g + e);
+        }
+    };
+    auto cor_st = [&](auto typed, uint32_t e, uint32_t v) {
+        if constexpr (decltype(typed)::value) {
+            s_cor[e] = v;
+        } else {
+            if (in_lds) s_cor[e] = v;
+            else st_global(cor_g + e, v);
+        }
+    };
     if (!in_lds && dirty_listed)
-        for (uint32_t e = tid; e < nD; e += kFBlock) cor[e] = s_cor[kFCor - 1 - e];
+        for (uint32_t e = tid; e < nD; e += kFBlock) st_global(cor_g + e, s_cor[kFCor - 1 - e]);
+    const uint32_t nw = (K + 31) / 32;
+    uint32_t nA = 0, nB = 0, ncor = 0, T = 0;
+    // the list and the touched keys, compiled twice: for corrections and runs in LDS
+    // (typed), and for any placement
+    auto lists_and_rows = [&](auto typed) {
+    auto put = [&](uint32_t at, uint32_t v) { cor_st(typed, at, v); };
     const uint2 *hitl = reinterpret_cast<const uint2 *>(A.hitl);
     for (uint32_t l0 = 0; l0 < nl; l0 += kFLists) {  // kFLists lists at a time: their offsets in LDS
         const uint32_t nlc = min(kFLists, nl - l0);
@@ -842,7 +908,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             }
 #pragma unroll
             for (uint32_t q = 0; q < kFBatch; q++)
-                wave_push(cor, &s_ncor, need, h[q].x - hb < U, cor_entry(h[q].y, h[q].x - hb, 0));
+                wave_push(put, &s_ncor, need, h[q].x - hb < U, cor_entry(h[q].y, h[q].x - hb, 0));
         }
         __syncthreads();  // s_loff / s_lidx reused by the next lists
     }
@@ -855,26 +921,29 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             want = !(q[0] >> 31) && q[1] - hb < U;
             v = cor_entry(q[2], q[1] - hb, 0);
         }
-        wave_push(cor, &s_ncor, need, want, v);
+        wave_push(put, &s_ncor, need, want, v);
     }
-    if (!dirty_listed)
-        each_dirty([&](uint32_t l, const uint4 &q, bool dirty, bool uniform) {
-            const uint32_t c = dirty ? __popc(q.w) : 0u;
-            uint32_t at = slots(c, uniform, &s_ncor);
-            for (uint32_t m = q.w; c && m; m &= m - 1, at++)
-                if (at < need) cor[at] = cor_entry(q.x + __builtin_ctz(m), l, 1);
-        });
-    const uint32_t nw = (K + 31) / 32;
+    if (!dirty_listed && nref) {  // (the walk, or more dirty corrections than the top of s_cor holds)
+        auto put_in = [&](uint32_t at, uint32_t v) {
+            if (at < need) cor_st(typed, at, v);
+        };
+        if (pairwise)
+            dirty_masks(typed, [&](uint32_t l, uint32_t p0, uint64_t m) { (void)list_mask(l, p0, m, &s_ncor, put_in); });
+        else
+            dirty_walk(typed, [&](uint32_t l, const uint4 &q) {
+                uint32_t at = atomicAdd(&s_ncor, (uint32_t)__popc(q.w));
+                for (uint32_t m = q.w; m; m &= m - 1, at++) put_in(at, cor_entry(q.x + __builtin_ctz(m), l, 1));
+            });
+    }
     for (uint32_t w = tid; w < nw; w += kFBlock) s_bits[w] = 0;
     __syncthreads();
     stamp(4, wall_clock64());
     // the corrections: [0, nA) and, listed at the top of s_cor, [kFCor - nB, kFCor)
-    const uint32_t nA = s_ncor, nB = in_lds && dirty_listed ? nD : 0u, ncor = nA + nB;  // (nA <= need)
-    auto cor_at = [&](uint32_t e) -> uint32_t & { return e < nA ? cor[e] : s_cor[kFCor - nB + (e - nA)]; };
+    nA = s_ncor, nB = in_lds && dirty_listed ? nD : 0u, ncor = nA + nB;  // (nA <= need)
     // touched keys: own hits (the dirty reference hits' keys are reference keys),
     // reference hits, every key of a LUT/generic slot; rows in key order
     for (uint32_t e = tid; e < nA; e += kFBlock) {
-        const uint32_t c = cor[e];
+        const uint32_t c = cor_ld(typed, e);
         if (!cor_neg(c)) atomicOr(&s_bits[cor_key(c) >> 5], 1u << (cor_key(c) & 31u));
     }
     if (tid < nref)
@@ -886,7 +955,6 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         for (uint32_t j = tid; j < K; j += kFBlock)
             if (!A.slot_mfma[j / n_inner]) atomicOr(&s_bits[j >> 5], 1u << (j & 31u));
     __syncthreads();
-    uint32_t T = 0;
     {
         constexpr uint32_t per = kPerW;
         uint32_t mine = 0;
@@ -905,6 +973,9 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             }
         }
     }
+    };
+    if (in_lds && runs_lds) lists_and_rows(KfTyped{});
+    else lists_and_rows(KfAny{});
     stamp(5, wall_clock64());
     auto row_of = [&](uint32_t j) { return s_rbase[j >> 5] + __popc(s_bits[j >> 5] & ((1u << (j & 31)) - 1u)); };
     // the counter block: LDS chunks of rows x U, or -- when that would take more than
@@ -920,11 +991,12 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     // never borrows or carries
     const bool half = 4 * (s_lmax + 64) < 65536 && A.cor_lds != 0;
     uint32_t rows_per = min((half ? 2 : 1) * kFCnt / U, kFRows);
-    uint32_t *cnt = s_cnt;
     uint16_t *const cnt16 = reinterpret_cast<uint16_t *>(s_cnt);
-    bool h16 = half;
+    bool h16 = half, cnt_arena = false;
+    uint32_t *cnt_g = A.cor_arena;  // (the counters' arena share: global memory)
     if ((T + rows_per - 1) / rows_per > 32 || A.cor_lds == 0) {  // (cor_lds 0: the tests' all-global path)
         h16 = false;
+        cnt_arena = true;
         pw |= TFBS_PATH_CNT_ARENA;
         rows_per = min(T, kFRows);
         if (tid == 0) {
@@ -934,7 +1006,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         }
         __syncthreads();
         if (s_arena == kFNone) return give_up(5);  // the host grows the arena for the next call
-        cnt = A.cor_arena + s_arena;
+        cnt_g = A.cor_arena + s_arena;
     }
     pw |= (h16 ? 0u : TFBS_PATH_U32) | (U > kFHapLds ? TFBS_PATH_HAP_GLOBAL : 0u);
     // untouched keys: no match -- no key in the reference's HashMap
@@ -944,15 +1016,41 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             A.key_flags[ko + j] = 0;
         }
     const uint64_t dense_base = A.dense_base ? A.haps[hb].count_off : 0;
+    uint64_t t_atomics = 0;  // (TFBS_KF_PROF)
+    // the counter chunks, compiled twice: for corrections in LDS and packed u16 counters
+    // (typed: h16 is a constant there), and for any placement of either
+    auto chunks = [&](auto typed) {
+    constexpr bool kTyped = decltype(typed)::value;
+    // where correction e sits: the list, or the dirty ones at the top of s_cor
+    auto cor_top = [&](uint32_t e) -> uint32_t { return kFCor - nB + (e - nA); };
+    auto cor_at = [&](uint32_t e) -> uint32_t {
+        if constexpr (kTyped) return s_cor[e < nA ? e : cor_top(e)];
+        else return e < nA ? cor_ld(typed, e) : s_cor[cor_top(e)];
+    };
+    auto cnt_set = [&](uint32_t x, uint32_t v) {
+        if (kTyped || h16) cnt16[x] = (uint16_t)v;
+        else if (cnt_arena) st_global(cnt_g + x, v);
+        else s_cnt[x] = v;
+    };
+    auto cnt_add = [&](uint32_t x, uint32_t d) {  // d: +1 | -1
+        if (kTyped || h16) atomicAdd(&s_cnt[x >> 1], d << (16 * (x & 1u)));
+        else if (cnt_arena) atomicAdd(&cnt_g[x], d);
+        else atomicAdd(&s_cnt[x], d);
+    };
+    auto count_at = [&](uint32_t x) -> uint32_t {
+        if (kTyped || h16) return (uint32_t)cnt16[x];
+        if (cnt_arena) return ld_global(cnt_g + x);
+        return s_cnt[x];
+    };
     // the corrections by row (key << 12 becomes row << 12: no row_of per chunk)
     for (uint32_t e = tid; e < ncor; e += kFBlock) {
-        uint32_t &c = cor_at(e);
-        c = (row_of(cor_key(c)) << 12) | (c & 4095u);
+        const uint32_t c = cor_at(e), v = (row_of(cor_key(c)) << 12) | (c & 4095u);
+        if (e < nA) cor_st(typed, e, v);
+        else s_cor[cor_top(e)] = v;
     }
     uint32_t dedup_bits = 0;  // bit i: haplotype lane + 64 i takes the reference's counts as its base
     for (uint32_t i = 0, l = lane; l < U; i++, l += 64)
         if (hap_info(l) != kFNone) dedup_bits |= 1u << i;
-    uint64_t t_atomics = 0;  // (TFBS_KF_PROF)
     for (uint32_t t0 = 0; t0 < T; t0 += rows_per) {
         const uint32_t nrow = min(rows_per, T - t0);
         __syncthreads();  // s_rbase / cor rows written, the previous chunk's readers done
@@ -983,22 +1081,16 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             for (uint32_t i = 0, l = lane; l < U; i++, l += 64) {
                 const uint32_t v = dense ? A.counts[dense_base + (uint64_t)j * rg.count_stride + l]
                                          : ((dedup_bits >> i) & 1u ? R : 0u);
-                if (h16) cnt16[rr * U + l] = (uint16_t)v;
-                else cnt[rr * U + l] = v;
+                cnt_set(rr * U + l, v);
             }
         }
         __syncthreads();
         for (uint32_t e = tid; e < ncor; e += kFBlock) {
             const uint32_t c = cor_at(e);
             const uint32_t t = cor_key(c) - t0;  // (its row)
-            if (t < nrow) {
-                const uint32_t x = t * U + cor_hap(c);
-                if (h16) atomicAdd(&cnt[x >> 1], (cor_neg(c) ? 0xFFFFFFFFu : 1u) << (16 * (x & 1u)));
-                else atomicAdd(&cnt[x], cor_neg(c) ? 0xFFFFFFFFu : 1u);
-            }
+            if (t < nrow) cnt_add(t * U + cor_hap(c), cor_neg(c) ? 0xFFFFFFFFu : 1u);
         }
         __syncthreads();
-        auto count_at = [&](uint32_t x) -> uint32_t { return h16 ? (uint32_t)cnt16[x] : cnt[x]; };
         // classify: one wave per row
         for (uint32_t rr = wave; rr < nrow; rr += kFWaves) {
             const uint32_t c0 = count_at(rr * U);
@@ -1033,6 +1125,9 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             for (uint32_t l = lane; l < U; l += 64) A.var_counts[off + l] = count_at(rr * U + l);
         }
     }
+    };
+    if (in_lds && h16) chunks(KfTyped{});
+    else chunks(KfAny{});
     stamp(6, wall_clock64());
     stamp(7, t_atomics);
     stamp(8, U);
