@@ -52,6 +52,16 @@ VAR_SCORED, VAR_MULTIALLELIC, VAR_NO_CARRIER, VAR_UNPATCHED = 0, 1, 2, 3
 EFFECT_MODES = {"sites": 0, "all": 1}
 EFFECTS_HEADER = ("#chrom\tregion\tvariant\tpos\tref\talt\tcarriers\tkind\tname\tpattern_id\tstrand\tref_start\t"
                   "ref_end\tref_score\talt_start\talt_end\talt_score\tdelta\n")
+# tfbs_mutation as a numpy dtype (RegionBatch.mutscan), the kinds' mask bits and codes, the TSV's header line
+MUTATION_DTYPE = [("region", "<u4"), ("column", "<u4"), ("pattern", "<u4"), ("ref", "u1"), ("alt", "u1"), ("kind", "u1"),
+                  ("reserved", "u1"), ("pos", "<u8"), ("n_windows", "<u4"), ("ref_score", "<i4"), ("ref_window", "<u4"),
+                  ("alt_score", "<i4"), ("alt_window", "<u4"), ("reserved1", "<u4"), ("ref_start", "<u8"),
+                  ("ref_end", "<u8"), ("alt_start", "<u8"), ("alt_end", "<u8")]
+MUT_GAIN, MUT_LOSS, MUT_CHANGE, MUT_SAME, MUT_NONE = 1, 2, 4, 8, 16
+MUT_SITES, MUT_ALL = 7, 31
+MUT_KINDS = ("gain", "loss", "change", "same", "none")  # a record's kind code indexes it; bit 1 << code in a mask
+MUTSCAN_HEADER = ("#chrom\tregion\tpos\tref\talt\tkind\tname\tpattern_id\tstrand\tref_start\tref_end\tref_score\t"
+                  "alt_start\talt_end\talt_score\tdelta\n")
 
 Range = namedtuple("Range", "start end")  # range.rs:4-8, inclusive
 NucleotidePos = namedtuple("NucleotidePos", "nuc pos")  # types.rs:23-27 (nuc as 'A'..'N')
@@ -478,6 +488,29 @@ class Scanner:
         out = (C.c_double * 3)()
         check(lib().tfbs_ctx_last_effects_ms(self.h, out))
         return out[0], out[1], out[2]
+
+    def last_mutscan_ms(self):
+        """tfbs_ctx_last_mutscan_ms: (host packing ms, count pass + offset scan ms, fill pass ms from HIP
+        events, copy-back + host ms) of the last mutscan() or mutscan_count()."""
+        out = (C.c_double * 4)()
+        check(lib().tfbs_ctx_last_mutscan_ms(self.h, out))
+        return tuple(out)
+
+
+def mutscan_ring_max_length():
+    """tfbs_mutscan_ring_max_length: the longest strand the mutation-scan kernel's ring serves."""
+    return lib().tfbs_mutscan_ring_max_length()
+
+
+def mutscan_kinds_mask(kinds):
+    """A mask of MUT_* from an int or from names ("gain,loss" or a list of them)."""
+    if isinstance(kinds, int):
+        return kinds
+    names = kinds.split(",") if isinstance(kinds, str) else list(kinds)
+    mask = 0
+    for k in names:
+        mask |= 1 << MUT_KINDS.index(k)
+    return mask
 
 
 def matches(pattern, haplotype, haplotype_ids=(), verbose=False):
@@ -1050,6 +1083,47 @@ class RegionBatch:
             lib().tfbs_free(p)
         return (EFFECTS_HEADER if header else "") + text
 
+    def mutscan(self, scanner, r0=None, r1=None, kinds=MUT_SITES):
+        """tfbs_batch_mutscan: per (pattern strand, column of the region's reference window, other
+        base) of regions [r0, r1) the best site covering the column before and after the substitution
+        and the record's kind, for the kinds in the mask, on a scanner made from this batch's patterns
+        (no upload, no scan needed; needs keep_variants): a sparse numpy structured array
+        (MUTATION_DTYPE) sorted by (region, pattern, column, alt)."""
+        import numpy as np
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_mutscan(scanner.h, self.h, 0 if r0 is None else r0,
+                                       self.num_regions if r1 is None else r1, mutscan_kinds_mask(kinds), C.byref(p),
+                                       C.byref(n)))
+        try:
+            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_mutation)), dtype=MUTATION_DTYPE).copy()
+        finally:
+            lib().tfbs_free(p)
+        return out
+
+    def mutscan_count(self, scanner, r0=None, r1=None, kinds=MUT_SITES):
+        """tfbs_batch_mutscan_count: len(mutscan(...)) from the count pass alone."""
+        n = C.c_uint64()
+        check(lib().tfbs_batch_mutscan_count(scanner.h, self.h, 0 if r0 is None else r0,
+                                             self.num_regions if r1 is None else r1, mutscan_kinds_mask(kinds),
+                                             C.byref(n)))
+        return n.value
+
+    def mutscan_tsv(self, m, chromosome, header=False):
+        """tfbs_batch_mutscan_tsv: one line per record of a mutscan() result (any subset, in its
+        order); header: MUTSCAN_HEADER first."""
+        import numpy as np
+        m = np.ascontiguousarray(m, dtype=MUTATION_DTYPE)
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_mutscan_tsv(self.h, m.ctypes.data_as(C.c_void_p), len(m), _u(chromosome), C.byref(p),
+                                           C.byref(n)))
+        try:
+            text = C.string_at(p, n.value).decode()
+        finally:
+            lib().tfbs_free(p)
+        return (MUTSCAN_HEADER if header else "") + text
+
     def rows(self, chromosome, min_maf=0, fake_position=1):
         """Rows for every region (main.rs:415-429); returns (text, next fake_position)."""
         fp = C.c_uint32(fake_position)
@@ -1119,7 +1193,8 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
         pwm_threshold, wanted_pwms, output_file, forward_only=False, run_tabix=False, min_maf=0, threads=1,
         after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None,
         hits_output=None, hits_mode="diff", best_output=None, best_mode="diff", effects_output=None,
-        effects_mode="sites", scores_output=None, scores_min_spread=1, pwm_pvalue=None):
+        effects_mode="sites", scores_output=None, scores_min_spread=1, pwm_pvalue=None, mutscan_output=None,
+        mutscan_kinds=0):
     """main.rs:234-393 `run` with the reference's argument order; writes the BGZF VCF.
     devices: list of HIP devices; batch g of merged regions runs on devices[g % n] (same
     text for any list; a device may repeat).  hits_output: also write every region's hit
@@ -1130,7 +1205,10 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     scores_output: also write the score rows (RegionBatch.score_rows with min_maf and
     scores_min_spread, POS from 1) there as a second BGZF VCF under the main output's #CHROM line;
     the main output does not change.  pwm_pvalue: the patterns load as parse_pwm_files(pvalue=...)
-    loads them, on the run's first device; pwm_threshold_directory may then be None."""
+    loads them, on the run's first device; pwm_threshold_directory may then be None.  mutscan_output:
+    also write every region's mutation scan there as BGZF TSV (MUTSCAN_HEADER, then
+    RegionBatch.mutscan_tsv's lines for the kinds of mutscan_kinds: a mask of MUT_* or names; 0 means
+    gain and loss)."""
     a = _capi.tfbs_run_args()
     keep = [_u(x) if x is not None else None for x in (chromosome, bcf, ",".join(bed_files), reference_genome_file,
                                                         wanted_samples, pwm_file, pwm_threshold_directory,
@@ -1156,7 +1234,13 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     bo = _u(best_output) if best_output is not None else None
     a.best_output = bo
     a.best_mode = BEST_MODES[best_mode]
-    if pwm_pvalue is None:
+    mo = _u(mutscan_output) if mutscan_output is not None else None
+    if mutscan_output is not None:
+        x = _capi.tfbs_run_ext_mutscan()
+        x.pwm_pvalue = pwm_pvalue or 0.0
+        x.mutscan_output = mo
+        x.mutscan_kinds = mutscan_kinds_mask(mutscan_kinds)
+    elif pwm_pvalue is None:
         x = _capi.tfbs_run_ext_scores()
     else:
         x = _capi.tfbs_run_ext_pvalue()

@@ -78,6 +78,14 @@ class tfbs_effect(C.Structure):
                 ("ref_start", C.c_uint64), ("ref_end", C.c_uint64), ("alt_start", C.c_uint64), ("alt_end", C.c_uint64)]
 
 
+class tfbs_mutation(C.Structure):
+    _fields_ = [("region", C.c_uint32), ("column", C.c_uint32), ("pattern", C.c_uint32), ("ref", C.c_uint8),
+                ("alt", C.c_uint8), ("kind", C.c_uint8), ("reserved", C.c_uint8), ("pos", C.c_uint64),
+                ("n_windows", C.c_uint32), ("ref_score", C.c_int32), ("ref_window", C.c_uint32),
+                ("alt_score", C.c_int32), ("alt_window", C.c_uint32), ("reserved1", C.c_uint32),
+                ("ref_start", C.c_uint64), ("ref_end", C.c_uint64), ("alt_start", C.c_uint64), ("alt_end", C.c_uint64)]
+
+
 class tfbs_run_ext(C.Structure):
     _fields_ = [("size", C.c_uint32), ("effects_output", C.c_char_p), ("effects_mode", C.c_int)]
 
@@ -91,6 +99,11 @@ class tfbs_run_ext_scores(C.Structure):
 class tfbs_run_ext_pvalue(C.Structure):
     """tfbs_run_ext as the header has it since the p-value thresholds (pwm_pvalue at the end)."""
     _fields_ = tfbs_run_ext_scores._fields_ + [("pwm_pvalue", C.c_double)]
+
+
+class tfbs_run_ext_mutscan(C.Structure):
+    """tfbs_run_ext as the header has it since the mutation scan (its two fields at the end)."""
+    _fields_ = tfbs_run_ext_pvalue._fields_ + [("mutscan_output", C.c_char_p), ("mutscan_kinds", C.c_uint32)]
 
 
 # (name, restype, argtypes) for every symbol in include/tfbs_amd.h
@@ -220,6 +233,13 @@ SIGNATURES = [
     ("tfbs_batch_effects", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     ("tfbs_ctx_last_effects_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
     ("tfbs_batch_effects_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_size_t)]),
+    ("tfbs_batch_mutscan", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_size_t)]),
+    ("tfbs_batch_mutscan_count", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_uint32, u64p]),
+    ("tfbs_mutscan_ring_max_length", C.c_uint32, []),
+    ("tfbs_ctx_last_mutscan_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
+    ("tfbs_batch_mutscan_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_size_t)]),
     ("tfbs_scores_as_genotypes", C.c_int, [i32p, i32p, C.c_size_t, C.c_uint64, u32p, C.c_char_p, C.c_size_t,
                                            C.c_char_p, C.c_size_t]),

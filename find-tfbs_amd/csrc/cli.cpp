@@ -1,6 +1,7 @@
 // find-tfbs-amd: the find-tfbs command line (main.rs:163-232) over tfbs_run_ex.
 // Long flags are the reference's; the short ones it binds twice (-n, -t,
 // main.rs:174/179, 177/181) are accepted in their first meaning only.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,6 +18,7 @@ static void usage() {
             "       [--best_output FILE [--best_mode all|diff]]\n"
             "       [--effects_output FILE [--effects_mode sites|all]]\n"
             "       [--scores_output FILE [--scores_min_spread N]]\n"
+            "       [--mutscan_output FILE [--mutscan_kinds gain,loss,change,same,none]]\n"
             "       [--forward_only] [--threads N] [--min_maf N] [--after_position P] [--samples FILE]\n"
             "       [--tabix] [--verbose] [--device D | --devices D1,D2,.. | --gpus N] [--regions_per_batch N]\n"
             "  --devices: one contiguous block of merged regions per listed HIP device (a device may repeat);\n"
@@ -42,7 +44,11 @@ static void usage() {
             "  --scores_output FILE: also write how strongly each sample binds, as a second BGZF VCF: per (bed, inner\n"
             "  range) and pattern_id one row whose per-sample GT:DS comes from the sum of the sample's two haplotypes'\n"
             "  best scores (INFO SCORES=<lowest>,<highest>), whatever the threshold; rows whose sums span less than\n"
-            "  --scores_min_spread N (milli-log-odds, default 1) are left out.  --min_maf applies to both files.\n");
+            "  --scores_min_spread N (milli-log-odds, default 1) are left out.  --min_maf applies to both files.\n"
+            "  --mutscan_output FILE: also write which substitutions would create or destroy a site, as BGZF TSV: per\n"
+            "  merged region, pattern strand, reference base and other base the best site covering the base before and\n"
+            "  after the substitution (range, score) and the score's delta, whatever the BCF holds.\n"
+            "  --mutscan_kinds: the kinds of lines written, a comma list (default gain,loss).\n");
 }
 
 int main(int argc, char **argv) {
@@ -100,6 +106,25 @@ int main(int argc, char **argv) {
                 return 2;
             }
             x.effects_mode = m == "all" ? TFBS_EFFECTS_ALL : TFBS_EFFECTS_SITES;
+        }
+        else if (k == "--mutscan_output") x.mutscan_output = val("--mutscan_output");
+        else if (k == "--mutscan_kinds") {
+            const std::string list = val("--mutscan_kinds");
+            static const char *const names[5] = {"gain", "loss", "change", "same", "none"};
+            x.mutscan_kinds = 0;
+            for (size_t at = 0; at <= list.size();) {
+                const size_t end = std::min(list.find(',', at), list.size());
+                const std::string name = list.substr(at, end - at);
+                int bit = -1;
+                for (int q = 0; q < 5; q++)
+                    if (name == names[q]) bit = q;
+                if (bit < 0) {
+                    fprintf(stderr, "error: --mutscan_kinds is a comma list of gain, loss, change, same, none\n");
+                    return 2;
+                }
+                x.mutscan_kinds |= 1u << bit;
+                at = end + 1;
+            }
         }
         else if (k == "--scores_output") x.scores_output = val("--scores_output");
         else if (k == "--scores_min_spread") x.scores_min_spread = strtoull(val("--scores_min_spread"), nullptr, 10);

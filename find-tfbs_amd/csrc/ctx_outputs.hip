@@ -1,5 +1,6 @@
-// The entry points of the hit lists, best sites, score rows and variant effects: the resident
-// image handed to their drivers (scan_hits.hip, scan_best.hip, score_rows.hip, scan_effects.hip).
+// The entry points of the hit lists, best sites, score rows, variant effects and mutation scans: the
+// resident image handed to their drivers (scan_hits.hip, scan_best.hip, score_rows.hip); the last two
+// (scan_effects.hip, scan_mutscan.hip) read the batch's kept variants instead.
 #include "ctx.hpp"
 
 using namespace tfbs;
@@ -105,6 +106,39 @@ int tfbs_ctx_last_effects_ms(const tfbs_ctx *ctx, double out[3]) {
     effects_last_ms(ctx->effects_state, out);
     return TFBS_OK;
 }
+
+// Mutation scan (scan_mutscan.hip): as the variant effects, the batch need not be resident.
+static int mutscan_call(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, uint32_t kinds, bool null_out,
+                        std::vector<tfbs_mutation> *v, uint64_t *total) {
+    if (!ctx || !b || null_out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (b->b.pats != ctx->pats) return tfbs::fail(TFBS_E_ARG, "batch and ctx use different pattern sets");
+    if (!b->b.keep_variants) return tfbs::fail(TFBS_E_STATE, "batch built without tfbs_batch_keep_variants");
+    if (b->b.open) return tfbs::fail(TFBS_E_STATE, "region still open");
+    if (r0 > r1 || r1 > b->b.rh.size()) return tfbs::fail(TFBS_E_ARG, "bad region range");
+    if (kinds == 0 || kinds > TFBS_MUT_ALL) return tfbs::fail(TFBS_E_ARG, "kinds is a non-empty mask of TFBS_MUT_*");
+    return mutscan_run(&ctx->mutscan_state, ctx->device, ctx->stream, *ctx->pats, b->b, r0, r1, kinds, v, total);
+}
+
+int tfbs_batch_mutscan(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, uint32_t kinds, tfbs_mutation **out,
+                       size_t *n) {
+    std::vector<tfbs_mutation> v;
+    uint64_t total = 0;
+    if (int rc = mutscan_call(ctx, b, r0, r1, kinds, !out || !n, &v, &total)) return rc;
+    if (total != v.size()) return tfbs::fail(TFBS_E_STATE, "mutation scan: the count and the fill disagree");
+    return hand_out(v, out, n);
+}
+
+int tfbs_batch_mutscan_count(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, uint32_t kinds, uint64_t *n) {
+    return mutscan_call(ctx, b, r0, r1, kinds, !n, nullptr, n);
+}
+
+int tfbs_ctx_last_mutscan_ms(const tfbs_ctx *ctx, double out[4]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    mutscan_last_ms(ctx->mutscan_state, out);
+    return TFBS_OK;
+}
+
+uint32_t tfbs_mutscan_ring_max_length(void) { return tfbs::kMutRingMax; }
 
 
 }  // extern "C"

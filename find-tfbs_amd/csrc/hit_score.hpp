@@ -1,5 +1,6 @@
 // What the brute-force kernels (scan_hits.hip, scan_best.hip), the variant-effect kernel
-// (scan_effects.hip: pair_head, the scoring, the drivers' base) and their drivers share.  A HIP
+// (scan_effects.hip: pair_head, the scoring, the drivers' base), the mutation-scan kernel
+// (scan_mutscan.hip: pair_head_at, the scoring of one window, the drivers' base) and their drivers share.  A HIP
 // header: only .hip sources include it.
 //  * Device: the exact scoring code (bases16, score_mono, score_dinuc), the kernels' prologue
 //    in two steps (pair_head, PAIR_OPEN), what a wave knows of its pair (PairScan) and the walk
@@ -145,24 +146,32 @@ struct PairScan {  // what a wave knows of its pair to score it (wave-uniform)
 // chunk haplotypes [k0, k1) (pairs are haplotype-major: the first is k0 * n_strands); the wave
 // takes pair blockIdx.x * kHitWaves + wave of them, loads its strand through scalar loads and
 // stages a dinucleotide strand's rows.  An inactive wave (the last workgroup's tail) takes the
-// last pair, so that every wave of the workgroup reaches the barrier.
+// last pair, so that every wave of the workgroup reaches the barrier.  pair_head_at is the same
+// for the chunk's pairs [p0, p0 + n_pairs), which need not be whole haplotypes (scan_mutscan.hip's
+// fill pass).  The two share their body as a macro, for the reason given below.
+#define PAIR_HEAD_BODY(T, N_PAIRS, P0, s_rows)                                                                  \
+    const uint32_t lane = threadIdx.x & 63;                                                                     \
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                     \
+    const uint64_t n_pairs = (N_PAIRS);                                                                         \
+    const uint64_t pl = (uint64_t)blockIdx.x * kHitWaves + wave;                                                \
+    const bool active = pl < n_pairs;                                                                           \
+    const uint64_t p = (P0) + (active ? pl : n_pairs - 1);                                                      \
+    const uint32_t k = (uint32_t)(p / (T).n_strands);                                                           \
+    const uint32_t sidx = (uint32_t)(p - (uint64_t)k * (T).n_strands);                                          \
+    CStrand &S = ((CStrand *)(T).strands)[sidx];                                                                \
+    const uint32_t kind = S.kind, L = S.len, w_off = S.w_off;                                                   \
+    const int32_t min_score = S.min_score;                                                                      \
+    const bool di = kind == TFBS_KIND_DIPWM;                                                                    \
+    if (di) stage_dinuc_rows((s_rows)[wave], (T).weights, w_off, L, lane); /* (L <= kDiMaxLen: check_dipwm_length) */ \
+    __syncthreads();                                                                                            \
+    return PairHead{lane, pl, p, active, k, sidx, kind, L, w_off, min_score, di, (s_rows)[wave]}
 __device__ __forceinline__ PairHead pair_head(const PairSrc &T, uint32_t k0, uint32_t k1,
                                               int32_t (&s_rows)[kHitWaves][kHitDiInts]) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t n_pairs = (uint64_t)(k1 - k0) * T.n_strands;
-    const uint64_t pl = (uint64_t)blockIdx.x * kHitWaves + wave;
-    const bool active = pl < n_pairs;
-    const uint64_t p = (uint64_t)k0 * T.n_strands + (active ? pl : n_pairs - 1);
-    const uint32_t k = (uint32_t)(p / T.n_strands);
-    const uint32_t sidx = (uint32_t)(p - (uint64_t)k * T.n_strands);
-    CStrand &S = ((CStrand *)T.strands)[sidx];
-    const uint32_t kind = S.kind, L = S.len, w_off = S.w_off;
-    const int32_t min_score = S.min_score;
-    const bool di = kind == TFBS_KIND_DIPWM;
-    if (di) stage_dinuc_rows(s_rows[wave], T.weights, w_off, L, lane);  // (L <= kDiMaxLen: check_dipwm_length)
-    __syncthreads();
-    return PairHead{lane, pl, p, active, k, sidx, kind, L, w_off, min_score, di, s_rows[wave]};
+    PAIR_HEAD_BODY(T, (uint64_t)(k1 - k0) * T.n_strands, (uint64_t)k0 * T.n_strands, s_rows);
+}
+__device__ __forceinline__ PairHead pair_head_at(const PairSrc &T, uint64_t p0, uint64_t np,
+                                                 int32_t (&s_rows)[kHitWaves][kHitDiInts]) {
+    PAIR_HEAD_BODY(T, np, p0, s_rows);
 }
 
 // The three pieces below are macros, not functions: a function is simplified on its own

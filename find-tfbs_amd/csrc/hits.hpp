@@ -1,7 +1,8 @@
-// Hit lists (tfbs_batch_hits), best sites (tfbs_batch_best) and variant effects
-// (tfbs_batch_effects): the interfaces of scan_hits.hip, scan_best.hip and scan_effects.hip to
-// ctx_outputs.hip, what they share on the host (the tables, ScanImage, site_range, text_out) and the
-// host-only helpers of hits.cpp, best.cpp and effects.cpp.
+// Hit lists (tfbs_batch_hits), best sites (tfbs_batch_best), variant effects (tfbs_batch_effects)
+// and mutation scans (tfbs_batch_mutscan): the interfaces of scan_hits.hip, scan_best.hip,
+// scan_effects.hip and scan_mutscan.hip to ctx_outputs.hip, what they share on the host (the tables,
+// ScanImage, site_range, text_out) and the host-only helpers of hits.cpp, best.cpp, effects.cpp and
+// mutscan.cpp.
 #pragma once
 
 #include <cstdint>
@@ -132,5 +133,42 @@ int effects_run(EffectsState **state, int device, void *stream, const Patterns &
 void effects_last_ms(const EffectsState *s, double out[3]);
 // tfbs_batch_effects_tsv's text appended to out (no header line); the records are whole regions.
 int effects_tsv(const Batch &B, const tfbs_effect *e, size_t n, const std::string &chrom, int mode, std::string &out);
+
+// ---- mutation scan (tfbs_batch_mutscan): scan_mutscan.hip's interface to ctx_outputs.hip, mutscan.cpp's formatter
+// The longest strand the kernel's ring of window scores serves (a ring of 128 scores holds
+// the 64 windows of a chunk and the 64 before them: a column's windows reach back L - 1);
+// a longer strand takes the slow path.  tfbs_mutscan_ring_max_length() returns it.
+constexpr uint32_t kMutRingMax = 65;
+// One region of a chunk as the kernel reads it: R packed into the chunk's words (and N-mask
+// words, has_n).
+struct DevMutRegion {
+    uint32_t word_off, nmask_off;  // R's first word / N-mask word
+    uint32_t len;                  // columns of R
+    uint32_t has_n;
+};
+// One mutation record as the fill pass writes it: 32 bytes, two vector stores.  The host adds
+// the region, the positions and n_windows.
+struct alignas(16) DevMutRec {
+    uint32_t region;  // of the chunk
+    uint32_t pattern, column;
+    uint32_t rak;  // ref | alt << 8 | kind << 16
+    int32_t ref_score;
+    uint32_t ref_window;
+    int32_t alt_score;
+    uint32_t alt_window;
+};
+struct MutscanState;
+void mutscan_state_destroy(MutscanState *s);
+// The mutation records of regions [r0, r1) of B (built with keep_variants) whose kind is in
+// `kinds`, appended to *out, sorted by (region, pattern, column, alt base); out null: the count
+// pass alone.  *total: the records.  Reads no resident image.  *state is made on the first
+// call.  Synchronises `stream` (a hipStream_t).
+int mutscan_run(MutscanState **state, int device, void *stream, const Patterns &P, const Batch &B, size_t r0, size_t r1,
+                uint32_t kinds, std::vector<tfbs_mutation> *out, uint64_t *total);
+// The last mutscan_run's times (ms): host packing (wall), count pass + offset scan, fill pass
+// (HIP events, summed over the chunks), copy-back + host expansion (wall).
+void mutscan_last_ms(const MutscanState *s, double out[4]);
+// tfbs_batch_mutscan_tsv's text appended to out (no header line); any records of the batch.
+int mutscan_tsv(const Batch &B, const tfbs_mutation *m, size_t n, const std::string &chrom, std::string &out);
 
 }  // namespace tfbs

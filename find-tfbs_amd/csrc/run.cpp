@@ -169,6 +169,8 @@ struct RunSetup {
     TextOut *best = nullptr;  // null without --best_output: the same
     TextOut *effects = nullptr;  // null without --effects_output: the same (the batches keep no variants)
     int effects_mode = TFBS_EFFECTS_SITES;
+    TextOut *mutscan = nullptr;  // null without --mutscan_output: the same (variants are kept for either of the two)
+    uint32_t mutscan_kinds = TFBS_MUT_GAIN | TFBS_MUT_LOSS;
     ScoresOut *scores = nullptr;  // null without --scores_output: the same
     std::string chrom;
     tfbs_patterns *pp;
@@ -268,7 +270,7 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
         if (rc) return err = tfbs_last_error(), rc;
         p.bp = BatchPtr(bb, tfbs_batch_destroy);
         Batch &B = bb->b;
-        B.keep_variants = S.effects != nullptr;
+        B.keep_variants = S.effects != nullptr || S.mutscan != nullptr;
         for (auto &b : S.beds) B.beds.push_back(b.first);
         p.ins.clear();
         p.ins.reserve(b1 - b0);
@@ -445,6 +447,22 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
                 q0 = q1;
             }
             if ((rc = S.effects->submit(g, std::move(text)))) return rc;
+        }
+        if (S.mutscan) {  // the batch's mutation scan: whole regions at a time, bounded as the effects are
+            std::string text;
+            const size_t np = B.pats->pats.size();
+            auto records_of = [&](size_t r) { return (size_t)B.kept[r].ref.size() * 3 * np; };  // (at most)
+            for (size_t q0 = 0; q0 < B.rh.size();) {
+                size_t q1 = q0 + 1, recs = records_of(q0);  // regions [q0, q1): one at least
+                while (q1 < B.rh.size() && recs + records_of(q1) <= kEffectsRunRecords) recs += records_of(q1++);
+                tfbs_mutation *mut = nullptr;
+                size_t nmut = 0;
+                if ((rc = tfbs_batch_mutscan(ctx, bb, q0, q1, S.mutscan_kinds, &mut, &nmut))) return rc;
+                std::unique_ptr<tfbs_mutation, void (*)(void *)> mguard(mut, free);
+                if ((rc = mutscan_tsv(B, mut, nmut, strip_chr(S.chrom), text))) return rc;
+                q0 = q1;
+            }
+            if ((rc = S.mutscan->submit(g, std::move(text)))) return rc;
         }
         if (S.scores) {  // the batch's score rows: counted, then numbered from the chain and written as text
             uint64_t n_rows = 0, n_text = 0;
@@ -655,7 +673,13 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     const char *scores_output = nullptr;
     uint64_t scores_min_spread = 1;
     double pwm_pvalue = 0;
+    const char *mutscan_output = nullptr;
+    uint32_t mutscan_kinds = 0;
     if (ext) {
+        if (ext->size >= offsetof(tfbs_run_ext, mutscan_output) + sizeof ext->mutscan_output)
+            mutscan_output = ext->mutscan_output;
+        if (ext->size >= offsetof(tfbs_run_ext, mutscan_kinds) + sizeof ext->mutscan_kinds)
+            mutscan_kinds = ext->mutscan_kinds;
         if (ext->size >= offsetof(tfbs_run_ext, pwm_pvalue) + sizeof ext->pwm_pvalue) pwm_pvalue = ext->pwm_pvalue;
         if (ext->size >= offsetof(tfbs_run_ext, scores_output) + sizeof ext->scores_output)
             scores_output = ext->scores_output;
@@ -782,6 +806,13 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
         if ((rc = effects_out.open(effects_output, threads, TFBS_EFFECTS_HEADER))) return rc;
         S.effects = &effects_out;
         S.effects_mode = effects_mode;
+    }
+    TextOut mutscan_out;
+    if (mutscan_output) {
+        if (mutscan_kinds > TFBS_MUT_ALL) return fail(TFBS_E_ARG, "mutscan_kinds is a mask of TFBS_MUT_*");
+        if ((rc = mutscan_out.open(mutscan_output, threads, TFBS_MUTSCAN_HEADER))) return rc;
+        S.mutscan = &mutscan_out;
+        if (mutscan_kinds) S.mutscan_kinds = mutscan_kinds;
     }
     ScoresOut scores_out;
     if (scores_output) {
@@ -951,6 +982,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     if (S.hits && (rc = hits_out.finish())) return rc;
     if (S.best && (rc = best_out.finish())) return rc;
     if (S.effects && (rc = effects_out.finish())) return rc;
+    if (S.mutscan && (rc = mutscan_out.finish())) return rc;
     if (S.scores && (rc = scores_out.out.finish())) return rc;
     const double t_close = now() - t0;
     if (timing)

@@ -899,6 +899,83 @@ int tfbs_batch_effects_tsv(const tfbs_batch *b, const tfbs_effect *e, size_t n, 
                            char **text, size_t *len);
 
 /* ------------------------------------------------------------------ */
+/* Mutation scan: every possible SNV of a region's reference window,    */
+/* per pattern strand                                                   */
+/* ------------------------------------------------------------------ */
+/* For a region of a batch made with tfbs_batch_keep_variants let R = patch_haplotype((es,
+ * ee), [], ref), n columns of (code, pos): the R of the variant effects.  A substitution is
+ * (c, b): a column c with R[c] in {A,C,G,T} and a base b in {A,C,G,T}, b != R[c]; an N column
+ * has none.  The mutation record of (region, pattern strand p of L bases, c, b) is, field for
+ * field, the effect record tfbs_batch_effects gives for a scored bi-allelic SNV record
+ * (pos_R[c], REF = R[c], ALT = b) of that region and strand:
+ *   n_windows               the affected windows i: i + L <= n and c - L + 1 <= i <= c (the
+ *                           effects' rule with a = c, z = n - 1 - c); the same on both sides
+ *   ref_score, ref_window   the maximum of their scores on R (signed int32), the lowest i
+ *                           attaining it
+ *   alt_score, alt_window   the same on R with column c set to b
+ *   ref_start .. alt_end    pos_R[window] and that plus L - 1
+ *   kind                    the effects TSV's: a side passes iff score > the strand's
+ *                           min_score; 0 gain (only alt passes), 1 loss (only ref), 2 change
+ *                           (both, scores differ), 3 same (both, equal), 4 none (neither)
+ * Scores are the hit list's (wrapping int32 column sum, an N column adding 0, any L; wrapping
+ * int32 pair sum, a pair holding an N adding 0).  A record exists iff the strand is
+ * TFBS_KIND_PWM or TFBS_KIND_DIPWM, n_windows > 0 and its kind is in the call's `kinds` mask.
+ * The result is sparse and sorted by (region, pattern, column, alt base).  Inner ranges, the
+ * bed multiplicity and the region's BCF records play no part. */
+#define TFBS_MUT_GAIN 1
+#define TFBS_MUT_LOSS 2
+#define TFBS_MUT_CHANGE 4
+#define TFBS_MUT_SAME 8
+#define TFBS_MUT_NONE 16
+#define TFBS_MUT_SITES 7
+#define TFBS_MUT_ALL 31
+typedef struct tfbs_mutation {
+    uint32_t region, column, pattern; /* offsets 0, 4, 8 */
+    uint8_t ref, alt, kind, reserved; /* 12 .. 15: codes 0-3; kind 0 gain .. 4 none */
+    uint64_t pos;                     /* 16: pos_R[column] */
+    uint32_t n_windows;               /* 24 */
+    int32_t ref_score;                /* 28 */
+    uint32_t ref_window;              /* 32 */
+    int32_t alt_score;                /* 36 */
+    uint32_t alt_window;              /* 40 */
+    uint32_t reserved1;               /* 44 */
+    uint64_t ref_start, ref_end, alt_start, alt_end; /* 48, 56, 64, 72 */
+} tfbs_mutation; /* 80 bytes */
+/* The mutation records of regions [r0, r1) whose kind is in `kinds`, on a ctx made from the
+ * batch's pattern set (needs neither upload nor scan; leaves every scan / reduce / encode /
+ * rows / hits / best / scores / effects result and the step graph untouched).  *out is
+ * malloc'd (tfbs_free).  The host packs each region's R once; the kernel (scan_mutscan.hip)
+ * scores every reference window once, keeps the scores in a ring in LDS and forms each alt
+ * score as the reference score plus one weight difference (two pair-weight differences for a
+ * dinucleotide strand), one wave per (region, strand); a count pass, an exclusive scan and a
+ * fill pass place the records without atomics or a sort.  Strands longer than
+ * tfbs_mutscan_ring_max_length() bases take a slower exact path.  It works in chunks of
+ * whole regions, and fills in runs of whole (region, strand) pairs, that fit
+ * TFBS_MUTSCAN_SCRATCH_MB (default 256, fractions allowed; one region and one pair at least;
+ * read at the call); the result does not depend on it.  TFBS_E_STATE without
+ * tfbs_batch_keep_variants; TFBS_E_ARG for r0 > r1, r1 > num_regions, kinds == 0,
+ * kinds > TFBS_MUT_ALL or a ctx of another pattern set; an empty range of regions or an empty
+ * pattern set gives *n = 0. */
+int tfbs_batch_mutscan(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, uint32_t kinds, tfbs_mutation **out,
+                       size_t *n);
+/* The count pass alone: *n = the records tfbs_batch_mutscan would give. */
+int tfbs_batch_mutscan_count(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, uint32_t kinds, uint64_t *n);
+/* The longest strand (bases) that the kernel's ring of window scores serves. */
+uint32_t tfbs_mutscan_ring_max_length(void);
+/* The last mutation scan's times (ms): out[0] the host's packing (wall), out[1] the count
+ * pass and the offset scan, out[2] the fill pass (HIP events on the ctx stream, summed over
+ * the scratch chunks), out[3] the copy-back and the host's expansion (wall). */
+int tfbs_ctx_last_mutscan_ms(const tfbs_ctx *ctx, double out[4]);
+/* Host only.  Formats mutation records (any records of the batch, in list order: they are
+ * self-contained) as TSV, tab-separated, one line per record, under the header
+ *   #chrom region pos ref alt kind name pattern_id strand ref_start ref_end ref_score alt_start alt_end alt_score delta
+ * chrom, region, name and strand are the effects TSV's; delta is alt_score - ref_score as a
+ * signed 64-bit difference.  The header line is not part of *text (malloc'd, tfbs_free). */
+#define TFBS_MUTSCAN_HEADER "#chrom\tregion\tpos\tref\talt\tkind\tname\tpattern_id\tstrand\tref_start\tref_end\tref_score\talt_start\talt_end\talt_score\tdelta\n"
+int tfbs_batch_mutscan_tsv(const tfbs_batch *b, const tfbs_mutation *m, size_t n, const char *chromosome, char **text,
+                           size_t *len);
+
+/* ------------------------------------------------------------------ */
 /* Score rows: per-sample best-score genotypes as a second VCF          */
 /* ------------------------------------------------------------------ */
 /* The rows of the main output count the sites above min_score; a score row carries how
@@ -1010,7 +1087,8 @@ typedef struct tfbs_run_ext {
     uint32_t size;                  /* sizeof(tfbs_run_ext) of the caller */
     const char *effects_output;     /* --effects_output: the batches' variant effects as BGZF TSV
                                        (tfbs_batch_effects_tsv under TFBS_EFFECTS_HEADER), NULL = none: the run
-                                       does nothing more than without it (its batches keep no variants) */
+                                       does nothing more than without it (its batches keep no variants, unless
+                                       mutscan_output asks for them) */
     int effects_mode;               /* --effects_mode: TFBS_EFFECTS_SITES / TFBS_EFFECTS_ALL */
     const char *scores_output;      /* --scores_output: the batches' score rows (tfbs_batch_score_rows) as a second
                                        BGZF VCF under the main output's #CHROM line, POS from 1, min_maf as the
@@ -1019,6 +1097,10 @@ typedef struct tfbs_run_ext {
     double pwm_pvalue;              /* --pwm_pvalue: > 0: the patterns load by tfbs_patterns_from_files_pvalue on the
                                        run's first device; pwm_threshold_dir may then be NULL and pwm_threshold is
                                        ignored.  0: thresholds come from the directory as before */
+    const char *mutscan_output;     /* --mutscan_output: the batches' mutation scans as BGZF TSV
+                                       (tfbs_batch_mutscan_tsv under TFBS_MUTSCAN_HEADER), NULL = none: the run
+                                       does nothing more than without it */
+    uint32_t mutscan_kinds;         /* --mutscan_kinds: a mask of TFBS_MUT_*; 0 = TFBS_MUT_GAIN | TFBS_MUT_LOSS */
 } tfbs_run_ext;
 int tfbs_run_ex(const tfbs_run_args *args, const tfbs_run_ext *ext);
 
