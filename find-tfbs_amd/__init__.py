@@ -43,6 +43,12 @@ BEST_DTYPE = [("region", "<u4"), ("haplotype", "<u4"), ("pattern", "<u4"), ("ran
 BEST_MODES = {"all": 0, "diff": 1}
 BEST_HEADER = ("#chrom\tregion\tbed\tinner_start\tinner_end\tname\tpattern_id\thaplotype\tcarriers\tkind\tstrand\t"
                "start\tend\tscore\tdelta\tcarrier_ids\n")
+# tfbs_affinity as a numpy dtype (RegionBatch.affinity), the affinity TSV's modes and header line
+AFFINITY_DTYPE = [("region", "<u4"), ("haplotype", "<u4"), ("pattern", "<u4"), ("range", "<u4"), ("n_windows", "<u4"),
+                  ("n_nonzero", "<u4"), ("sum", "<u8")]
+AFFINITY_MODES = {"all": 0, "diff": 1}
+AFFINITY_HEADER = ("#chrom\tregion\tbed\tinner_start\tinner_end\tname\tpattern_id\thaplotype\tcarriers\tkind\ttop\t"
+                   "n_windows\taffinity\tdelta\tcarrier_ids\n")
 # tfbs_effect as a numpy dtype (RegionBatch.effects), a record's statuses, the effect TSV's modes and header line
 EFFECT_DTYPE = [("region", "<u4"), ("variant", "<u4"), ("pattern", "<u4"), ("status", "<u4"), ("n_ref", "<u4"),
                 ("ref_score", "<i4"), ("ref_window", "<u4"), ("n_alt", "<u4"), ("alt_score", "<i4"),
@@ -271,6 +277,15 @@ class PatternSet:
         check(lib().tfbs_patterns_pvalue_thresholds(self.h, device, p, out))
         return list(out[:n])
 
+    def affinity_tops(self):
+        """tfbs_patterns_affinity_tops: one value per strand in creation order, its pattern_id's
+        reference score top (the highest sum any strand of the id can reach, an N adding 0), 0 for
+        an OtherPattern; TfbsError (TFBS_E_ARG) when a strand's sums can wrap int32."""
+        n = len(self)
+        out = (C.c_int32 * max(1, n))()
+        check(lib().tfbs_patterns_affinity_tops(self.h, out))
+        return list(out[:n])
+
     def with_min_scores(self, ms):
         """A copy whose strand k has min_score ms[k]; ids, names, order and weights stay."""
         if len(ms) != len(self):
@@ -279,6 +294,11 @@ class PatternSet:
         h = C.c_void_p()
         check(lib().tfbs_patterns_with_min_scores(self.h, arr, C.byref(h)))
         return PatternSet(h)
+
+
+def affinity_weight(d):
+    """tfbs_affinity_weight: a(d) = floor(2^40 * exp(-d / 1000)) for an integer 0 <= d < 2^64."""
+    return lib().tfbs_affinity_weight(d)
 
 
 def pvalue_tile_widths():
@@ -473,6 +493,12 @@ class Scanner:
         """tfbs_ctx_last_best_ms: (kernel ms from HIP events, copy-back + host ms) of the last best()."""
         out = (C.c_double * 2)()
         check(lib().tfbs_ctx_last_best_ms(self.h, out))
+        return out[0], out[1]
+
+    def last_affinity_ms(self):
+        """tfbs_ctx_last_affinity_ms: (kernel ms from HIP events, copy-back + host ms) of the last affinity()."""
+        out = (C.c_double * 2)()
+        check(lib().tfbs_ctx_last_affinity_ms(self.h, out))
         return out[0], out[1]
 
     def last_scores_ms(self):
@@ -1030,6 +1056,54 @@ class RegionBatch:
         counts = mine["n_windows"].reshape(nh, npat, nr)
         return scores[memb], counts[memb]
 
+    def affinity(self, scanner, r0=None, r1=None):
+        """tfbs_batch_affinity: the total binding affinity per (distinct haplotype, pattern strand,
+        inner range) of regions [r0, r1) of this batch, resident on the scanner (after an upload; no
+        scan needed): a dense numpy structured array (AFFINITY_DTYPE) sorted by (region, haplotype,
+        pattern, range); `sum` is the exact integer sum of affinity_weight(top - score) over the
+        range's windows."""
+        import numpy as np
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_affinity(scanner.h, self.h, 0 if r0 is None else r0,
+                                        self.num_regions if r1 is None else r1, C.byref(p), C.byref(n)))
+        try:
+            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_affinity)), dtype=AFFINITY_DTYPE).copy()
+        finally:
+            lib().tfbs_free(p)
+        return out
+
+    def affinity_tsv(self, aff, chromosome, mode="diff", header=False):
+        """tfbs_batch_affinity_tsv: the TSV of an affinity() result over whole regions; mode "all"
+        (one `aff` line per (key, pattern_id, haplotype)) or "diff" (`hap` lines, then `base` and
+        `alt` lines where a haplotype's sum differs from the baseline's); header: AFFINITY_HEADER first."""
+        import numpy as np
+        aff = np.ascontiguousarray(aff, dtype=AFFINITY_DTYPE)
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(lib().tfbs_batch_affinity_tsv(self.h, aff.ctypes.data_as(C.c_void_p), len(aff), _u(chromosome),
+                                            AFFINITY_MODES[mode], C.byref(p), C.byref(n)))
+        try:
+            text = C.string_at(p, n.value).decode()
+        finally:
+            lib().tfbs_free(p)
+        return (AFFINITY_HEADER if header else "") + text
+
+    def affinity_by_sample(self, aff, region):
+        """(sums, n_windows): uint64 / uint32 arrays [2 * n_samples][n_patterns][n_ranges] of one
+        region, row id = the records of the distinct haplotype that haplotype id 2 * sample + side
+        carries (membership); `aff` must hold that region in full."""
+        import numpy as np
+        mine = aff[aff["region"] == region]
+        nh, nr = self.region_stats(region)[0], len(self.ranges(region))
+        npat = len(mine) // (nh * nr) if nh * nr else 0
+        if npat * nh * nr != len(mine) or (nh * nr and npat != len(self.patterns)):
+            raise ValueError("aff does not hold region %d in full" % region)
+        memb = np.asarray(self.membership(region), dtype=np.int64)
+        sums = mine["sum"].reshape(nh, npat, nr)
+        counts = mine["n_windows"].reshape(nh, npat, nr)
+        return sums[memb], counts[memb]
+
     def variants(self, region):
         """tfbs_batch_region_variant: the region's records in BCF order as (pos, ref, alt, n_alleles,
         carriers, status) -- ref / alt as ACGTN text, carriers the number of carrier ids, status one
@@ -1194,7 +1268,7 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
         after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None,
         hits_output=None, hits_mode="diff", best_output=None, best_mode="diff", effects_output=None,
         effects_mode="sites", scores_output=None, scores_min_spread=1, pwm_pvalue=None, mutscan_output=None,
-        mutscan_kinds=0):
+        mutscan_kinds=0, affinity_output=None, affinity_mode="diff"):
     """main.rs:234-393 `run` with the reference's argument order; writes the BGZF VCF.
     devices: list of HIP devices; batch g of merged regions runs on devices[g % n] (same
     text for any list; a device may repeat).  hits_output: also write every region's hit
@@ -1208,7 +1282,8 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     loads them, on the run's first device; pwm_threshold_directory may then be None.  mutscan_output:
     also write every region's mutation scan there as BGZF TSV (MUTSCAN_HEADER, then
     RegionBatch.mutscan_tsv's lines for the kinds of mutscan_kinds: a mask of MUT_* or names; 0 means
-    gain and loss)."""
+    gain and loss).  affinity_output: also write every region's binding affinities there as BGZF TSV
+    (AFFINITY_HEADER, then RegionBatch.affinity_tsv's lines in affinity_mode "all" or "diff")."""
     a = _capi.tfbs_run_args()
     keep = [_u(x) if x is not None else None for x in (chromosome, bcf, ",".join(bed_files), reference_genome_file,
                                                         wanted_samples, pwm_file, pwm_threshold_directory,
@@ -1235,7 +1310,15 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     a.best_output = bo
     a.best_mode = BEST_MODES[best_mode]
     mo = _u(mutscan_output) if mutscan_output is not None else None
-    if mutscan_output is not None:
+    ao = _u(affinity_output) if affinity_output is not None else None
+    if affinity_output is not None:
+        x = _capi.tfbs_run_ext_affinity()
+        x.pwm_pvalue = pwm_pvalue or 0.0
+        x.mutscan_output = mo
+        x.mutscan_kinds = mutscan_kinds_mask(mutscan_kinds)
+        x.affinity_output = ao
+        x.affinity_mode = AFFINITY_MODES[affinity_mode]
+    elif mutscan_output is not None:
         x = _capi.tfbs_run_ext_mutscan()
         x.pwm_pvalue = pwm_pvalue or 0.0
         x.mutscan_output = mo

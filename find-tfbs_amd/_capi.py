@@ -71,6 +71,11 @@ class tfbs_best(C.Structure):
                 ("start", C.c_uint64), ("end", C.c_uint64)]
 
 
+class tfbs_affinity(C.Structure):
+    _fields_ = [("region", C.c_uint32), ("haplotype", C.c_uint32), ("pattern", C.c_uint32), ("range", C.c_uint32),
+                ("n_windows", C.c_uint32), ("n_nonzero", C.c_uint32), ("sum", C.c_uint64)]
+
+
 class tfbs_effect(C.Structure):
     _fields_ = [("region", C.c_uint32), ("variant", C.c_uint32), ("pattern", C.c_uint32), ("status", C.c_uint32),
                 ("n_ref", C.c_uint32), ("ref_score", C.c_int32), ("ref_window", C.c_uint32),
@@ -104,6 +109,11 @@ class tfbs_run_ext_pvalue(C.Structure):
 class tfbs_run_ext_mutscan(C.Structure):
     """tfbs_run_ext as the header has it since the mutation scan (its two fields at the end)."""
     _fields_ = tfbs_run_ext_pvalue._fields_ + [("mutscan_output", C.c_char_p), ("mutscan_kinds", C.c_uint32)]
+
+
+class tfbs_run_ext_affinity(C.Structure):
+    """tfbs_run_ext as the header has it since the binding affinity (its two fields at the end)."""
+    _fields_ = tfbs_run_ext_mutscan._fields_ + [("affinity_output", C.c_char_p), ("affinity_mode", C.c_int)]
 
 
 # (name, restype, argtypes) for every symbol in include/tfbs_amd.h
@@ -227,6 +237,12 @@ SIGNATURES = [
     ("tfbs_ctx_last_best_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
     ("tfbs_batch_best_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_size_t)]),
+    ("tfbs_affinity_weight", C.c_uint64, [C.c_uint64]),
+    ("tfbs_patterns_affinity_tops", C.c_int, [vp, i32p]),
+    ("tfbs_batch_affinity", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    ("tfbs_ctx_last_affinity_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
+    ("tfbs_batch_affinity_tsv", C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_char_p, C.c_int, C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_size_t)]),
     ("tfbs_batch_keep_variants", C.c_int, [vp, C.c_int]),
     ("tfbs_batch_region_variant", C.c_int, [vp, C.c_size_t, C.c_size_t, u64p, u8p, u8p, C.c_size_t,
                                             C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), u32p, u32p, u32p]),

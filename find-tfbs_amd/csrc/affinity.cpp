@@ -1,0 +1,195 @@
+// Host side of the binding affinity (include/tfbs_amd.h, "Binding affinity"): the weight
+// a(d) from the committed tables, the pattern_ids' reference scores and the TSV of affinity
+// records.
+#include <algorithm>
+#include <cinttypes>
+#include <cstdio>
+#include <cstdlib>
+#include <map>
+#include <string>
+
+#include "affinity_tables.hpp"
+#include "hits.hpp"
+#include "score_dist.hpp"
+
+namespace tfbs {
+
+uint64_t affinity_weight(uint64_t d) {
+    if (d > kAffLast) return 0;
+    return (uint64_t)(((unsigned __int128)kAffT1[d % 1000] * kAffT2[d / 1000]) >> 64) >> 22;
+}
+
+int affinity_tops(const Patterns &P, std::vector<int32_t> *tops) {
+    std::map<uint16_t, int64_t> top;  // per pattern_id
+    for (const Pat &p : P.pats) {
+        if (p.kind != TFBS_KIND_PWM && p.kind != TFBS_KIND_DIPWM) continue;
+        const bool di = p.kind == TFBS_KIND_DIPWM;
+        const uint32_t steps = di ? (p.len ? p.len - 1 : 0) : p.len, width = di ? 16 : 4;
+        const int32_t *w = di ? p.w16.data() : p.w5.data();
+        const size_t stride = di ? 16 : 5;
+        uint64_t mag = 0;
+        int64_t c = 0;
+        for (uint32_t j = 0; j < steps; j++) {
+            const int32_t *col = w + stride * j;
+            const int64_t lo = *std::min_element(col, col + width), hi = *std::max_element(col, col + width);
+            mag += (uint64_t)std::max(std::llabs(lo), std::llabs(hi));
+            if (mag > (uint64_t)INT32_MAX)
+                return fail(TFBS_E_ARG, "the scores of strand " + strand_label(p) + " can wrap int32");
+            c += std::max<int64_t>(0, hi);
+        }
+        int64_t &t = top[p.pattern_id];  // (0 at first: no strand's sum is below it)
+        t = std::max(t, c);
+    }
+    tops->clear();
+    for (const Pat &p : P.pats)
+        tops->push_back(p.kind == TFBS_KIND_PWM || p.kind == TFBS_KIND_DIPWM ? (int32_t)top[p.pattern_id] : 0);
+    return TFBS_OK;
+}
+
+uint32_t affinity_max_strands(const Patterns &P) {
+    std::map<uint16_t, uint32_t> n;
+    uint32_t most = 0;
+    for (const Pat &p : P.pats) most = std::max(most, ++n[p.pattern_id]);
+    return most;
+}
+
+namespace {
+
+struct Value {  // of (haplotype, pattern_id, key): the fold over the pattern_id's strands
+    uint64_t a = 0, n = 0;
+    bool none() const { return n == 0; }
+};
+
+Value value_of(const tfbs_affinity *hap_block, const std::vector<uint32_t> &strands, uint32_t nr, uint32_t slot) {
+    Value v;
+    for (uint32_t p : strands) {
+        const tfbs_affinity &x = hap_block[(size_t)p * nr + slot];
+        v.a += x.sum;
+        v.n += x.n_windows;
+    }
+    return v;
+}
+
+inline bool differs(const Value &a, const Value &b) { return a.none() != b.none() || a.a != b.a; }
+
+struct AffLine {
+    std::string &out;
+    const std::string &chrom;
+    const Batch &B;
+    char region[48];
+    void hap(uint32_t h, uint32_t carriers, const std::string &ids) {
+        char buf[64];
+        tsv_key_head(out, chrom, region, B, nullptr, nullptr);
+        out.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%u\t%u\thap\t.\t.\t.\t.\t", h, carriers));
+        out += ids;
+        out += '\n';
+    }
+    void value(const InnerKey &k, const Pat &first, uint32_t h, uint32_t carriers, const char *kind, int32_t top,
+               const Value &v, const Value *base) {
+        char buf[160];
+        tsv_key_head(out, chrom, region, B, &k, &first);
+        out.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%u\t%u\t%s\t%d\t", h, carriers, kind, top));
+        if (!v.none()) out.append(buf, (size_t)snprintf(buf, sizeof buf, "%" PRIu64 "\t%" PRIu64 "\t", v.n, v.a));
+        else out += ".\t.\t";
+        if (base && !v.none() && !base->none())
+            out.append(buf, (size_t)snprintf(buf, sizeof buf, "%" PRId64, (int64_t)(v.a - base->a)));
+        else out += '.';
+        out += "\t.\n";
+    }
+};
+
+}  // namespace
+
+int affinity_tsv(const Batch &B, const tfbs_affinity *aff, size_t n, const std::string &chrom, int mode,
+                 std::string &out) {
+    if (mode != TFBS_AFFINITY_ALL && mode != TFBS_AFFINITY_DIFF)
+        return fail(TFBS_E_ARG, "affinity mode is TFBS_AFFINITY_ALL or TFBS_AFFINITY_DIFF");
+    const Patterns &P = *B.pats;
+    const uint32_t np = (uint32_t)P.pats.size();
+    std::vector<int32_t> tops;
+    if (int rc = affinity_tops(P, &tops)) return rc;
+    std::map<uint16_t, std::vector<uint32_t>> by_pid;  // ascending pattern_id -> its strands in creation order
+    for (uint32_t p = 0; p < np; p++) by_pid[P.pats[p].pattern_id].push_back(p);
+    AffLine L{out, chrom, B, {0}};
+    size_t at = 0;
+    uint32_t prev = 0;
+    bool any = false;
+    while (at < n) {
+        const uint32_t r = aff[at].region;
+        if (r >= B.rh.size() || (any && r <= prev))
+            return fail(TFBS_E_ARG, "affinity records: regions not ascending inside the batch");
+        any = true;
+        prev = r;
+        const RegionH &R = B.rh[r];
+        const uint32_t U = R.hap_count, nr = (uint32_t)R.ranges.size();
+        const size_t block = (size_t)U * np * nr;
+        if (block == 0 || n - at < block) return fail(TFBS_E_ARG, "affinity records: not a whole region");
+        const tfbs_affinity *blk = aff + at;
+        size_t x = 0;
+        for (uint32_t h = 0; h < U; h++)  // dense and sorted: the block reshapes to [h][p][k]
+            for (uint32_t p = 0; p < np; p++)
+                for (uint32_t k = 0; k < nr; k++, x++)
+                    if (blk[x].region != r || blk[x].haplotype != h || blk[x].pattern != p || blk[x].range != k)
+                        return fail(TFBS_E_ARG,
+                                    "affinity records: not a whole region sorted by (haplotype, pattern, range)");
+        at += block;
+        snprintf(L.region, sizeof L.region, "%" PRIu64 "-%" PRIu64, R.ms, R.me);
+        auto val = [&](uint32_t h, const std::vector<uint32_t> &strands, const InnerKey &k) {
+            return value_of(blk + (size_t)h * np * nr, strands, nr, (uint32_t)k.slot);
+        };
+        auto carriers = [&](uint32_t h) { return B.hap_carriers[R.hap_begin + h]; };
+        uint32_t base = 0;
+        if (mode == TFBS_AFFINITY_DIFF) {
+            std::vector<std::vector<uint32_t>> ids;
+            if (int rc = region_baseline(B, R, ids, &base)) return rc;
+            for (uint32_t h = 0; h < U; h++) L.hap(h, carriers(h), carrier_id_text(B, ids, h, base));
+        }
+        for (const InnerKey &k : R.keys) {  // sorted by (s, e, bed): the rows' order; each once
+            if (k.slot < 0) continue;       // an empty inner range
+            for (const auto &ps : by_pid) {
+                const Pat &first = P.pats[ps.second[0]];
+                const int32_t top = tops[ps.second[0]];
+                if (mode == TFBS_AFFINITY_ALL) {
+                    for (uint32_t h = 0; h < U; h++)
+                        L.value(k, first, h, carriers(h), "aff", top, val(h, ps.second, k), nullptr);
+                    continue;
+                }
+                const Value vb = val(base, ps.second, k);
+                bool wrote = false;
+                for (uint32_t h = 0; h < U; h++) {
+                    if (h == base) continue;
+                    const Value vh = val(h, ps.second, k);
+                    if (!differs(vh, vb)) continue;
+                    if (!wrote) L.value(k, first, base, carriers(base), "base", top, vb, nullptr);
+                    wrote = true;
+                    L.value(k, first, h, carriers(h), "alt", top, vh, &vb);
+                }
+            }
+        }
+    }
+    return TFBS_OK;
+}
+
+}  // namespace tfbs
+
+extern "C" {
+
+uint64_t tfbs_affinity_weight(uint64_t d) { return tfbs::affinity_weight(d); }
+
+int tfbs_patterns_affinity_tops(const tfbs_patterns *p, int32_t *out) {
+    if (!p || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    std::vector<int32_t> tops;
+    if (int rc = tfbs::affinity_tops(tfbs::patterns_of(p), &tops)) return rc;
+    std::copy(tops.begin(), tops.end(), out);
+    return TFBS_OK;
+}
+
+int tfbs_batch_affinity_tsv(const tfbs_batch *b, const tfbs_affinity *aff, size_t n, const char *chromosome,
+                            int mode, char **text, size_t *len) {
+    if (!b || !chromosome || !text || !len || (n && !aff)) return tfbs::fail(TFBS_E_ARG, "null argument");
+    std::string out;
+    if (int rc = tfbs::affinity_tsv(b->b, aff, n, chromosome, mode, out)) return rc;
+    return tfbs::text_out(out, text, len);
+}
+
+}  // extern "C"

@@ -31,22 +31,7 @@ struct BestLine {
     const std::string &chrom;
     const Batch &B;
     char region[48];
-    // bed / inner range / name / pattern_id, or "." for all of them (a `hap` line)
-    void head(const InnerKey *k, const Pat *p) {
-        char buf[96];
-        out += chrom;
-        out += '\t';
-        out += region;
-        if (!k) {
-            out += "\t.\t.\t.\t.\t.";
-            return;
-        }
-        out += '\t';
-        out += B.beds[k->bed];
-        out.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%" PRIu64 "\t%" PRIu64 "\t", k->s, k->e));
-        out += p->name;
-        out.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%u", (unsigned)p->pattern_id));
-    }
+    void head(const InnerKey *k, const Pat *p) { tsv_key_head(out, chrom, region, B, k, p); }
     void hap(uint32_t h, uint32_t carriers, const std::string &ids) {
         char buf[64];
         head(nullptr, nullptr);
@@ -72,6 +57,23 @@ struct BestLine {
 };
 
 }  // namespace
+
+void tsv_key_head(std::string &out, const std::string &chrom, const char *region, const Batch &B, const InnerKey *k,
+                  const Pat *p) {
+    char buf[96];
+    out += chrom;
+    out += '\t';
+    out += region;
+    if (!k) {
+        out += "\t.\t.\t.\t.\t.";
+        return;
+    }
+    out += '\t';
+    out += B.beds[k->bed];
+    out.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%" PRIu64 "\t%" PRIu64 "\t", k->s, k->e));
+    out += p->name;
+    out.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%u", (unsigned)p->pattern_id));
+}
 
 int best_tsv(const Batch &B, const tfbs_best *best, size_t n, const std::string &chrom, int mode, std::string &out) {
     if (mode != TFBS_BEST_ALL && mode != TFBS_BEST_DIFF) return fail(TFBS_E_ARG, "best mode is TFBS_BEST_ALL or TFBS_BEST_DIFF");

@@ -19,6 +19,7 @@ static void usage() {
             "       [--effects_output FILE [--effects_mode sites|all]]\n"
             "       [--scores_output FILE [--scores_min_spread N]]\n"
             "       [--mutscan_output FILE [--mutscan_kinds gain,loss,change,same,none]]\n"
+            "       [--affinity_output FILE [--affinity_mode all|diff]]\n"
             "       [--forward_only] [--threads N] [--min_maf N] [--after_position P] [--samples FILE]\n"
             "       [--tabix] [--verbose] [--device D | --devices D1,D2,.. | --gpus N] [--regions_per_batch N]\n"
             "  --devices: one contiguous block of merged regions per listed HIP device (a device may repeat);\n"
@@ -48,7 +49,12 @@ static void usage() {
             "  --mutscan_output FILE: also write which substitutions would create or destroy a site, as BGZF TSV: per\n"
             "  merged region, pattern strand, reference base and other base the best site covering the base before and\n"
             "  after the substitution (range, score) and the score's delta, whatever the BCF holds.\n"
-            "  --mutscan_kinds: the kinds of lines written, a comma list (default gain,loss).\n");
+            "  --mutscan_kinds: the kinds of lines written, a comma list (default gain,loss).\n"
+            "  --affinity_output FILE: also write each haplotype's total binding affinity, as BGZF TSV: per (bed, inner\n"
+            "  range), pattern_id and distinct haplotype the sum over every window of floor(2^40 exp((score - top) / 1000)),\n"
+            "  top the pattern_id's highest possible score: exact integers, ln(affinity) = top / 1000 + ln(sum) - 40 ln 2.\n"
+            "  --affinity_mode all: one `aff` line each; diff (default): `hap` lines, then where a haplotype's sum\n"
+            "  differs from the most carried haplotype's a `base` line and `alt` lines with the sum's delta.\n");
 }
 
 int main(int argc, char **argv) {
@@ -61,6 +67,7 @@ int main(int argc, char **argv) {
     memset(&x, 0, sizeof x);
     x.size = (uint32_t)sizeof x;
     x.effects_mode = TFBS_EFFECTS_SITES;
+    x.affinity_mode = TFBS_AFFINITY_DIFF;
     bool have_thr = false;
     std::string gpus;
     for (int i = 1; i < argc; i++) {
@@ -125,6 +132,15 @@ int main(int argc, char **argv) {
                 x.mutscan_kinds |= 1u << bit;
                 at = end + 1;
             }
+        }
+        else if (k == "--affinity_output") x.affinity_output = val("--affinity_output");
+        else if (k == "--affinity_mode") {
+            const std::string m = val("--affinity_mode");
+            if (m != "all" && m != "diff") {
+                fprintf(stderr, "error: --affinity_mode is all or diff\n");
+                return 2;
+            }
+            x.affinity_mode = m == "all" ? TFBS_AFFINITY_ALL : TFBS_AFFINITY_DIFF;
         }
         else if (k == "--scores_output") x.scores_output = val("--scores_output");
         else if (k == "--scores_min_spread") x.scores_min_spread = strtoull(val("--scores_min_spread"), nullptr, 10);

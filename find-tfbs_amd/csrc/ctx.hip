@@ -44,13 +44,14 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
         if (ctx->asmb.var_owner->var_ctx == ctx) ctx->asmb.var_owner->var_ctx = nullptr;
         ctx->asmb.var_owner = nullptr;
     }
-    // the five lazily made driver states; everything else frees itself, in reverse order of
+    // the six lazily made driver states; everything else frees itself, in reverse order of
     // its declaration (ctx.hpp): the step graph, the stages' buffers and events, then the stream
     tfbs::hits_state_destroy(ctx->hits_state);
     tfbs::best_state_destroy(ctx->best_state);
     tfbs::scores_state_destroy(ctx->scores_state);
     tfbs::effects_state_destroy(ctx->effects_state);
     tfbs::mutscan_state_destroy(ctx->mutscan_state);
+    tfbs::affinity_state_destroy(ctx->affinity_state);
     delete ctx;
 }
 

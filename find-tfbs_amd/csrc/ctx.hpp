@@ -346,13 +346,14 @@ struct tfbs_ctx {
     tfbs::EncState enc;
     tfbs::RowsBgzf rows;
     tfbs::StepGraph step;
-    // hit lists, best sites, score rows, variant effects and mutation scans: tables, scratch and
+    // hit lists, best sites, score rows, variant effects, mutation scans and affinities: tables, scratch and
     // timers, each made by its entry point's first call (deleted by tfbs_ctx_destroy)
     tfbs::HitsState *hits_state = nullptr;
     tfbs::BestState *best_state = nullptr;
     tfbs::ScoresState *scores_state = nullptr;
     tfbs::EffectsState *effects_state = nullptr;
     tfbs::MutscanState *mutscan_state = nullptr;
+    tfbs::AffinityState *affinity_state = nullptr;
 };
 
 namespace tfbs {

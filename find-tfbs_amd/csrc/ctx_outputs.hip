@@ -1,5 +1,5 @@
-// The entry points of the hit lists, best sites, score rows, variant effects and mutation scans: the
-// resident image handed to their drivers (scan_hits.hip, scan_best.hip, score_rows.hip); the last two
+// The entry points of the hit lists, best sites, affinities, score rows, variant effects and mutation scans: the
+// resident image handed to their drivers (scan_hits.hip, scan_best.hip, scan_affinity.hip, score_rows.hip); the last two
 // (scan_effects.hip, scan_mutscan.hip) read the batch's kept variants instead.
 #include "ctx.hpp"
 
@@ -61,6 +61,22 @@ int tfbs_batch_best(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_bes
 int tfbs_ctx_last_best_ms(const tfbs_ctx *ctx, double out[2]) {
     if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
     best_last_ms(ctx->best_state, out);
+    return TFBS_OK;
+}
+
+// Binding affinity (scan_affinity.hip): as the best sites, the batch resident and no scan needed.
+int tfbs_batch_affinity(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_affinity **out, size_t *n) {
+    ScanImage img;
+    std::vector<tfbs_affinity> v;
+    if (ctx && b && b->b.pats != ctx->pats) return tfbs::fail(TFBS_E_ARG, "batch and ctx use different pattern sets");
+    if (int rc = resident_image(ctx, b, r0, r1, !out || !n, &img)) return rc;
+    if (int rc = affinity_run(&ctx->affinity_state, ctx->device, ctx->stream, *ctx->pats, img, b->b, r0, r1, &v)) return rc;
+    return hand_out(v, out, n);
+}
+
+int tfbs_ctx_last_affinity_ms(const tfbs_ctx *ctx, double out[2]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    affinity_last_ms(ctx->affinity_state, out);
     return TFBS_OK;
 }
 

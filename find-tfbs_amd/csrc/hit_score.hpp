@@ -1,4 +1,4 @@
-// What the brute-force kernels (scan_hits.hip, scan_best.hip), the variant-effect kernel
+// What the brute-force kernels (scan_hits.hip, scan_best.hip, scan_affinity.hip), the variant-effect kernel
 // (scan_effects.hip: pair_head, the scoring, the drivers' base), the mutation-scan kernel
 // (scan_mutscan.hip: pair_head_at, the scoring of one window, the drivers' base) and their drivers share.  A HIP
 // header: only .hip sources include it.

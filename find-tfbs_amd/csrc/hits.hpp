@@ -1,8 +1,8 @@
-// Hit lists (tfbs_batch_hits), best sites (tfbs_batch_best), variant effects (tfbs_batch_effects)
-// and mutation scans (tfbs_batch_mutscan): the interfaces of scan_hits.hip, scan_best.hip,
-// scan_effects.hip and scan_mutscan.hip to ctx_outputs.hip, what they share on the host (the tables,
-// ScanImage, site_range, text_out) and the host-only helpers of hits.cpp, best.cpp, effects.cpp and
-// mutscan.cpp.
+// Hit lists (tfbs_batch_hits), best sites (tfbs_batch_best), binding affinities (tfbs_batch_affinity),
+// variant effects (tfbs_batch_effects) and mutation scans (tfbs_batch_mutscan): the interfaces of
+// scan_hits.hip, scan_best.hip, scan_affinity.hip, scan_effects.hip and scan_mutscan.hip to
+// ctx_outputs.hip, what they share on the host (the tables, ScanImage, site_range, text_out) and the
+// host-only helpers of hits.cpp, best.cpp, affinity.cpp, effects.cpp and mutscan.cpp.
 #pragma once
 
 #include <cstdint>
@@ -101,8 +101,38 @@ int best_run(BestState **state, int device, void *stream, const Patterns &P, con
              size_t r0, size_t r1, std::vector<tfbs_best> *out);
 // The last best_run's times (ms): the kernel (HIP events, summed over the chunks), copy-back + host part (wall).
 void best_last_ms(const BestState *s, double out[2]);
+// The first seven columns of a line of the best and the affinity TSV (best.cpp): chrom, region,
+// then bed / inner range / name / pattern_id, or "." for all five (k null: a `hap` line).
+void tsv_key_head(std::string &out, const std::string &chrom, const char *region, const Batch &B, const InnerKey *k,
+                  const Pat *p);
 // tfbs_batch_best_tsv's text appended to out (no header line); the records are whole regions.
 int best_tsv(const Batch &B, const tfbs_best *best, size_t n, const std::string &chrom, int mode, std::string &out);
+
+// ---- binding affinity (tfbs_batch_affinity): scan_affinity.hip's interface to ctx_outputs.hip, affinity.cpp's host side
+// One (haplotype, strand, range) as the kernel writes it: 16 bytes, one vector store.
+struct alignas(16) DevAffRec {
+    uint64_t sum;
+    uint32_t n_windows, n_nonzero;
+};
+// a(d) = floor(2^40 * exp(-d / 1000)) from affinity_tables.hpp (tfbs_affinity_weight).
+uint64_t affinity_weight(uint64_t d);
+// One value per strand in creation order: its pattern_id's top, 0 for a TFBS_KIND_OTHER strand;
+// TFBS_E_ARG naming a strand whose sums can wrap int32 (tfbs_patterns_affinity_tops).
+int affinity_tops(const Patterns &P, std::vector<int32_t> *tops);
+// The most strands one pattern_id has (0 for an empty set).
+uint32_t affinity_max_strands(const Patterns &P);
+struct AffinityState;
+void affinity_state_destroy(AffinityState *s);
+// The dense affinity records of regions [r0, r1) of B (resident as img on `device`) appended
+// to *out, sorted by (region, haplotype, pattern, range).  *state is made on the first call
+// (the two tables and the tops uploaded).  Synchronises `stream` (a hipStream_t).
+int affinity_run(AffinityState **state, int device, void *stream, const Patterns &P, const ScanImage &img,
+                 const Batch &B, size_t r0, size_t r1, std::vector<tfbs_affinity> *out);
+// The last affinity_run's times (ms): the kernel (HIP events, summed over the chunks), copy-back + host part (wall).
+void affinity_last_ms(const AffinityState *s, double out[2]);
+// tfbs_batch_affinity_tsv's text appended to out (no header line); the records are whole regions.
+int affinity_tsv(const Batch &B, const tfbs_affinity *aff, size_t n, const std::string &chrom, int mode,
+                 std::string &out);
 
 // ---- variant effects (tfbs_batch_effects): scan_effects.hip's interface to ctx_outputs.hip, effects.cpp's formatter
 // One scored record of a chunk as the kernel reads it: R and A packed into one run of the

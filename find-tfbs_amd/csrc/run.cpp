@@ -97,8 +97,8 @@ struct Shard {
     double t_setup = 0, t_boot = 0, t_end = 0;  // readers + ctx + grouper; the first batches' stages; flush + ctx release
 };
 
-// --hits_output, --best_output, --effects_output: the batches' texts (tfbs_batch_hits_tsv,
-// tfbs_batch_best_tsv, tfbs_batch_effects_tsv) written in batch order by the host BGZF writer, whichever shard hands them in first.
+// --hits_output, --best_output, --effects_output, --affinity_output: the batches' texts (tfbs_batch_hits_tsv,
+// tfbs_batch_best_tsv, tfbs_batch_effects_tsv, tfbs_batch_affinity_tsv) written in batch order by the host BGZF writer, whichever shard hands them in first.
 struct TextOut {
     std::mutex mu;
     tfbs::BgzfWriter w;
@@ -162,6 +162,8 @@ struct ScoresOut {
 constexpr size_t kBestRunRecords = 1u << 20;
 // The same for effect records (72 bytes each; tfbs_batch_effects_tsv takes whole regions too).
 constexpr size_t kEffectsRunRecords = 1u << 20;
+// The same for affinity records (32 bytes each; tfbs_batch_affinity_tsv takes whole regions too).
+constexpr size_t kAffinityRunRecords = 1u << 20;
 
 struct RunSetup {
     const tfbs_run_args *a;
@@ -172,6 +174,8 @@ struct RunSetup {
     TextOut *mutscan = nullptr;  // null without --mutscan_output: the same (variants are kept for either of the two)
     uint32_t mutscan_kinds = TFBS_MUT_GAIN | TFBS_MUT_LOSS;
     ScoresOut *scores = nullptr;  // null without --scores_output: the same
+    TextOut *affinity = nullptr;  // null without --affinity_output: the same
+    int affinity_mode = TFBS_AFFINITY_DIFF;
     std::string chrom;
     tfbs_patterns *pp;
     std::vector<std::pair<std::string, std::vector<std::pair<uint64_t, uint64_t>>>> beds;
@@ -464,6 +468,22 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
             }
             if ((rc = S.mutscan->submit(g, std::move(text)))) return rc;
         }
+        if (S.affinity) {  // the batch's binding affinities: dense records as the best sites', whole regions at a time
+            std::string text;
+            const size_t np = B.pats->pats.size();
+            auto records_of = [&](size_t r) { return (size_t)B.rh[r].hap_count * np * B.rh[r].ranges.size(); };
+            for (size_t q0 = 0; q0 < B.rh.size();) {
+                size_t q1 = q0 + 1, recs = records_of(q0);  // regions [q0, q1): one at least
+                while (q1 < B.rh.size() && recs + records_of(q1) <= kAffinityRunRecords) recs += records_of(q1++);
+                tfbs_affinity *aff = nullptr;
+                size_t naff = 0;
+                if ((rc = tfbs_batch_affinity(ctx, bb, q0, q1, &aff, &naff))) return rc;
+                std::unique_ptr<tfbs_affinity, void (*)(void *)> aguard(aff, free);
+                if ((rc = affinity_tsv(B, aff, naff, strip_chr(S.chrom), S.affinity_mode, text))) return rc;
+                q0 = q1;
+            }
+            if ((rc = S.affinity->submit(g, std::move(text)))) return rc;
+        }
         if (S.scores) {  // the batch's score rows: counted, then numbered from the chain and written as text
             uint64_t n_rows = 0, n_text = 0;
             uint32_t fk = 0;
@@ -675,7 +695,13 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     double pwm_pvalue = 0;
     const char *mutscan_output = nullptr;
     uint32_t mutscan_kinds = 0;
+    const char *affinity_output = nullptr;
+    int affinity_mode = TFBS_AFFINITY_ALL;
     if (ext) {
+        if (ext->size >= offsetof(tfbs_run_ext, affinity_output) + sizeof ext->affinity_output)
+            affinity_output = ext->affinity_output;
+        if (ext->size >= offsetof(tfbs_run_ext, affinity_mode) + sizeof ext->affinity_mode)
+            affinity_mode = ext->affinity_mode;
         if (ext->size >= offsetof(tfbs_run_ext, mutscan_output) + sizeof ext->mutscan_output)
             mutscan_output = ext->mutscan_output;
         if (ext->size >= offsetof(tfbs_run_ext, mutscan_kinds) + sizeof ext->mutscan_kinds)
@@ -813,6 +839,14 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
         if ((rc = mutscan_out.open(mutscan_output, threads, TFBS_MUTSCAN_HEADER))) return rc;
         S.mutscan = &mutscan_out;
         if (mutscan_kinds) S.mutscan_kinds = mutscan_kinds;
+    }
+    TextOut affinity_out;
+    if (affinity_output) {
+        if (affinity_mode != TFBS_AFFINITY_ALL && affinity_mode != TFBS_AFFINITY_DIFF)
+            return fail(TFBS_E_ARG, "affinity_mode is TFBS_AFFINITY_ALL or TFBS_AFFINITY_DIFF");
+        if ((rc = affinity_out.open(affinity_output, threads, TFBS_AFFINITY_HEADER))) return rc;
+        S.affinity = &affinity_out;
+        S.affinity_mode = affinity_mode;
     }
     ScoresOut scores_out;
     if (scores_output) {
@@ -983,6 +1017,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     if (S.best && (rc = best_out.finish())) return rc;
     if (S.effects && (rc = effects_out.finish())) return rc;
     if (S.mutscan && (rc = mutscan_out.finish())) return rc;
+    if (S.affinity && (rc = affinity_out.finish())) return rc;
     if (S.scores && (rc = scores_out.out.finish())) return rc;
     const double t_close = now() - t0;
     if (timing)

@@ -13,7 +13,7 @@ namespace tfbs {
 
 typedef unsigned __int128 u128;
 
-static std::string strand_label(const Pat &p) {
+std::string strand_label(const Pat &p) {
     return "'" + p.name + "' (" + (p.direction == TFBS_DIR_N ? "-" : "+") + ")";
 }
 

@@ -34,6 +34,8 @@ struct DistStrand {
     uint32_t tables() const { return di() ? 4 : 1; }
 };
 
+// A strand as an error message names it: 'name' (+) or 'name' (-).
+std::string strand_label(const Pat &p);
 // The limits of a strand (TFBS_E_ARG naming it) and, when it passes, its steps.
 int dist_strand(const Patterns &P, size_t i, DistStrand *out);
 int dist_check_pvalue(double p);

@@ -807,6 +807,77 @@ int tfbs_batch_best_tsv(const tfbs_batch *b, const tfbs_best *best, size_t n, co
                         char **text, size_t *len);
 
 /* ------------------------------------------------------------------ */
+/* Binding affinity: per distinct haplotype, pattern strand and inner  */
+/* range the sum over every window of exp(score), in exact fixed point */
+/* ------------------------------------------------------------------ */
+/* The weight of a window d >= 0 milli-log-odds below the reference score, in Q40:
+ *   a(d) = floor(2^40 * exp(-d / 1000))
+ * a mathematical definition: a(0) = 2^40, a(27725) = 1, a(d) = 0 for every d >= 27726
+ * (1000 ln 2^40 = 27725.89).  Host and device realise it from two committed tables,
+ * T1[r] = floor(2^63 exp(-r / 1000)), r < 1000, and T2[q] = floor(2^63 exp(-q)), q < 28, as
+ * umul64hi(T1[d % 1000], T2[d / 1000]) >> 22, which equals the definition on all of
+ * [0, 27726] (tools/gen_affinity_tables.py writes the tables with 80-digit decimals). */
+uint64_t tfbs_affinity_weight(uint64_t d);
+/* The reference score top(q) of a pattern_id q: the maximum over q's TFBS_KIND_PWM and
+ * TFBS_KIND_DIPWM strands of sum_j max(0, max_b w_j[b]) (b over A, C, G, T; a dinucleotide
+ * strand: over its rows of 16), the C of the matrix-core bound: an N column or a pair holding
+ * an N adds 0, so top(q) - score >= 0 for every window of every strand of q.  out takes one
+ * value per strand in creation order (tfbs_patterns_count entries): its pattern_id's top, 0
+ * for a TFBS_KIND_OTHER strand.  TFBS_E_ARG naming the strand when a strand's sums can wrap
+ * int32 (sum_j max(|lo_j|, |hi_j|) > INT32_MAX, tfbs_patterns_score_tails' rule). */
+int tfbs_patterns_affinity_tops(const tfbs_patterns *p, int32_t *out);
+/* One (distinct haplotype h, pattern strand p, inner range k) of a region; h, p, k, window
+ * existence, match range and range membership are the best sites', scores the hit list's.
+ *   n_windows  the windows that belong to k (tfbs_best.n_windows)
+ *   n_nonzero  those of them with a(d) > 0, d = top(pattern_id of p) - score
+ *   sum        the sum of a(d) over them
+ * A TFBS_KIND_OTHER strand, a haplotype shorter than L and a range without a window give
+ * zeros.  No floating point takes part: the sum is the same for any lane order, chunking,
+ * scratch budget and device.  The strands of a pattern_id share one top, so their records
+ * add, and so do a sample's two haplotypes: ln(affinity) = top / 1000 + ln(sum) - 40 ln 2.
+ * Dense and sorted by (region, haplotype, pattern, range) as the best records; min_score and
+ * the bed multiplicity play no part; empty inner ranges have no record. */
+typedef struct tfbs_affinity {
+    uint32_t region, haplotype, pattern, range;
+    uint32_t n_windows, n_nonzero;
+    uint64_t sum;
+} tfbs_affinity; /* 32 bytes */
+/* The affinity records of regions [r0, r1) of the batch resident on ctx (after
+ * tfbs_batch_upload; needs no scan; leaves every scan / reduce / encode / rows / hits / best /
+ * scores / effects / mutscan result and the step graph untouched).  *out is malloc'd
+ * (tfbs_free).  Its own kernel (scan_affinity.hip) walks every window as the best-site kernel
+ * does and sums the weights per range; chunks of whole haplotypes whose device records fit
+ * TFBS_AFFINITY_SCRATCH_MB (default 256; at least one haplotype; read at the call), and the
+ * result does not depend on it.  The ctx's first call uploads the two tables and the tops.
+ * Errors as tfbs_batch_best; TFBS_E_ARG also for a batch of another pattern set than the
+ * ctx's, when a strand's sums can wrap int32 (tfbs_patterns_affinity_tops) and for a region
+ * whose longest haplotype times the most strands of one pattern_id reaches 2^23 (every fold
+ * stays below 2^63). */
+int tfbs_batch_affinity(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, tfbs_affinity **out, size_t *n);
+/* The last tfbs_batch_affinity's times (ms): out[0] the kernel (HIP events on the ctx stream,
+ * summed over the scratch chunks), out[1] the copy-back and host part (wall). */
+int tfbs_ctx_last_affinity_ms(const tfbs_ctx *ctx, double out[2]);
+/* Host only.  Formats affinity records as TSV, tab-separated, under the header
+ *   #chrom region bed inner_start inner_end name pattern_id haplotype carriers kind top n_windows affinity delta carrier_ids
+ * The records are whole regions, as tfbs_batch_best_tsv's; a region without a record writes
+ * nothing.  Lines are per pattern_id: the value of (haplotype, pattern_id, key) is A = the sum
+ * of `sum` and N = the sum of n_windows over the pattern_id's strands; N == 0: "none".  Keys,
+ * their order, chrom, region, bed, name, haplotype, carriers, the baseline and the `hap`
+ * lines (the seven columns bed .. pattern_id and top .. delta ".") are the best TSV's.
+ * TFBS_AFFINITY_ALL: one `aff` line per (key, pattern_id, haplotype) with top, N and A; a
+ * "none" value writes "." for n_windows and affinity; delta and carrier_ids are ".".
+ * TFBS_AFFINITY_DIFF: the `hap` lines first; then for each (key, pattern_id) where some
+ * haplotype differs from the baseline in A or in being "none" one `base` line and one `alt`
+ * line per differing haplotype in index order; delta on an `alt` line is A - A_base as a
+ * signed 64-bit number, "." when either is "none"; elsewhere ".".
+ * The header line is not part of *text (malloc'd, tfbs_free). */
+#define TFBS_AFFINITY_ALL 0
+#define TFBS_AFFINITY_DIFF 1
+#define TFBS_AFFINITY_HEADER "#chrom\tregion\tbed\tinner_start\tinner_end\tname\tpattern_id\thaplotype\tcarriers\tkind\ttop\tn_windows\taffinity\tdelta\tcarrier_ids\n"
+int tfbs_batch_affinity_tsv(const tfbs_batch *b, const tfbs_affinity *aff, size_t n, const char *chromosome,
+                            int mode, char **text, size_t *len);
+
+/* ------------------------------------------------------------------ */
 /* Variant effects: per record the best site touching it on the REF and */
 /* on the ALT allele, per pattern strand                                */
 /* ------------------------------------------------------------------ */
@@ -1101,6 +1172,10 @@ typedef struct tfbs_run_ext {
                                        (tfbs_batch_mutscan_tsv under TFBS_MUTSCAN_HEADER), NULL = none: the run
                                        does nothing more than without it */
     uint32_t mutscan_kinds;         /* --mutscan_kinds: a mask of TFBS_MUT_*; 0 = TFBS_MUT_GAIN | TFBS_MUT_LOSS */
+    const char *affinity_output;    /* --affinity_output: the batches' binding affinities as BGZF TSV
+                                       (tfbs_batch_affinity_tsv under TFBS_AFFINITY_HEADER), NULL = none: the run
+                                       does nothing more than without it */
+    int affinity_mode;              /* --affinity_mode: TFBS_AFFINITY_ALL / TFBS_AFFINITY_DIFF */
 } tfbs_run_ext;
 int tfbs_run_ex(const tfbs_run_args *args, const tfbs_run_ext *ext);
 
