@@ -294,6 +294,7 @@ SIGNATURES = [
                                         C.POINTER(u32p), C.POINTER(C.c_size_t)]),
     ("tfbs_synth_fill_batch", C.c_int, [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
     ("tfbs_ctx_group_pairs", C.c_int, [vp, C.c_int, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("tfbs_ctx_share_entries", C.c_int, [vp, C.c_int, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
 ]
 
 _lib = None

@@ -429,6 +429,24 @@ int tfbs_ctx_group_pairs(tfbs_ctx *ctx, int cls, uint32_t *pairs, size_t cap, si
     return TFBS_OK;
 }
 
+int tfbs_ctx_share_entries(tfbs_ctx *ctx, int cls, uint32_t *entries, size_t cap, size_t *n_haps) {
+    if (!ctx || !n_haps || cls < 0 || cls > 1 || (cap && !entries)) return tfbs::fail(TFBS_E_ARG, "bad argument");
+    const uint32_t n = ctx->lists.wl_n_haps;
+    *n_haps = n;
+    if (n > cap) return cap ? tfbs::fail(TFBS_E_ARG, "share entries: the array is too small") : TFBS_OK;
+    // (as the scan takes them, launch_scan: shared lists, a list of the class, an entry in it)
+    if (!ctx->lists.wl_share || !ctx->lists.wl_off[cls].p || !ctx->lists.sh_entries[cls]) {
+        for (size_t h = 0; h < n; h++) entries[h] = 0;
+        return TFBS_OK;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<uint64_t> off((size_t)n + 1);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(off.data(), ctx->lists.sh_off[cls].p, off.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t h = 0; h < n; h++) entries[h] = (uint32_t)(off[h + 1] - off[h]);
+    return TFBS_OK;
+}
+
 int tfbs_batch_upload(tfbs_ctx *ctx, tfbs_batch *b) {
     if (!ctx || !b) return tfbs::fail(TFBS_E_ARG, "null argument");
     Batch &B = b->b;

@@ -59,7 +59,10 @@ struct ScanArgs {
     // their number at hitn[8 g + wave]; the excess goes to the spill list.
     // Invariant: wave list w of haplotype group g of the resident batch is list
     // g * kMBlockWaves + w, in every launch (launch_mfma_all: region_base = the launch's
-    // first group); the key assembly (key_kernels.hip) reads a region's lists by that index
+    // first group); the key assembly (key_kernels.hip) reads a region's lists by that index.
+    // The order of the pairs inside a wave list is free: their only reader, the key
+    // assembly, takes a region's lists flat and keeps pairs by haplotype (a list holds a
+    // pass's own pairs first, then its donors' sharers' in rounds of 64 share entries)
     uint32_t *hitl;
     uint32_t hit_cap;
     uint32_t *hitn;

@@ -182,6 +182,10 @@ __shared__ uint32_t s_hnext;  // the workgroup's next pair of window tiles (scan
 __shared__ uint4 s_hd[kMMaxHapsPerBlock];   // the group's haplotypes: LaneHap
 __shared__ uint4 s_hd2[kMMaxHapsPerBlock];  // and (region, pos_off, drun_off, n_druns) for the rescoring
 extern __shared__ __attribute__((aligned(16))) int32_t s_mdyn[];  // one-hot table | image | words
+// The unit kernel's resident descriptors (scan_pool): s_hd / s_hd2 of every haplotype of
+// the unit, haplotype h0 + t of the unit at t.
+__shared__ uint4 s_hdu[kMMaxUnit * kMMaxHapsPerBlock];
+__shared__ uint4 s_hd2u[kMMaxUnit * kMMaxHapsPerBlock];  // (the rescoring's half: rescore_list<true>)
 
 
 // What the firing path of a round needs: the group's window list (wl, nw
@@ -217,33 +221,6 @@ struct CandHap {
     }
 };
 
-// Exact score of window i of haplotype hp for a strand of length L (i + L <= len):
-// one load per column of the strand's blocks of 8 (zero-padded), all issued
-// before the first is summed (the rescoring runs where no accumulator is
-// live), N columns masked out.
-__device__ __forceinline__ int32_t exact_score(const uint32_t *words, const CandHap &hp, uint32_t i, uint32_t L,
-                                               const int32_t *wt, uint32_t live) {
-    const uint32_t *w = words + hp.word_off + (i >> 4);
-    const uint32_t sh = 2 * (i & 15);
-    const uint32_t img[2] = {__builtin_amdgcn_alignbit(w[1], w[0], sh), __builtin_amdgcn_alignbit(w[2], w[1], sh)};
-    const uint32_t keep = live & (L >= 32 ? ~0u : (1u << L) - 1);  // columns < L that are not N
-    int32_t v[32];
-#pragma unroll
-    for (uint32_t jb = 0; jb < 32; jb += 8) {
-        if (jb < L) {  // a lane loads only its strand's blocks
-#pragma unroll
-            for (uint32_t j = jb; j < jb + 8; j++) v[j] = wt[4 * j + ((img[j >> 4] >> (2 * (j & 15))) & 3u)];
-        } else {
-#pragma unroll
-            for (uint32_t j = jb; j < jb + 8; j++) v[j] = 0;
-        }
-    }
-    int32_t s = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < 32; j++) s += v[j] & -(int32_t)((keep >> j) & 1u);  // N scores 0
-    return s;
-}
-
 // Appends a record to the spill list (rare: hits past a wave's list, reference
 // hits past a region's list, inner ranges past 32).
 __device__ __forceinline__ void spill_record(const ScanArgs &A, uint32_t head, uint32_t x, uint32_t y) {
@@ -272,49 +249,148 @@ __device__ __forceinline__ uint32_t strand_class(const ScanArgs &A, uint32_t g) 
     return A.mmeta[(size_t)(g >> 6) * kGMetaInts + kGDepth] > 2 ? 1u : 0u;
 }
 
+// What the rescoring loads before it knows that it needs it: the first diff runs of a
+// HAP_DEDUP haplotype with round A (3.4 runs per haplotype on average at C3, at most 16,
+// profiles/r16 Part 0: four cover most haplotypes whole) and the first inner ranges of
+// the region with round B (C3's regions have one, the test regions up to 40).
+constexpr uint32_t kRunsUpFront = 4;
+constexpr uint32_t kInnerUpFront = 2;
+
+// A rescored candidate: the hit's inner ranges k < 32 (mask bit k; key = key0 + k), to
+// be listed by the caller, and for a donor's hit (shared windows) its depth class sc and
+// its sn sharer entries share[sc][se ..].
+struct CandHit {
+    uint32_t mask, key0, sc, sn;
+    uint64_t se;
+};
+
+// The loads of one round have arrived (one wait per round) and stay where they were
+// issued: without a use here the compiler sinks a load into the branch that needs it,
+// behind that branch's own chain of loads.
+__device__ __forceinline__ void arrived(uint32_t &x) { asm volatile("" : "+v"(x)); }
+__device__ __forceinline__ void arrived(int32_t &x) { asm volatile("" : "+v"(x)); }
+
 // Exact rescoring of one candidate: window i of haplotype hp (hits index hap)
-// for the strand g = global tile * 64 + strand in tile.  A HAP_DEDUP haplotype's
+// for the strand g = global tile * 64 + strand in tile: the exact score (one weight per
+// column of the strand's blocks of 8, zero-padded, N columns masked out), strict against
+// the strand's minimum (pattern.rs:125-151).  A HAP_DEDUP haplotype's
 // window read because it meets a diff run within the class span, but whose strand
 // columns [i, i + L) meet none, is the reference's window for that strand: not
 // listed (the key assembly adds the reference's hit, tfbs_internal.hpp).  Returns the hit's
-// inner ranges k < 32 (bit k; key = *key0 + k) to be listed by the caller;
+// inner ranges k < 32 to be listed by the caller;
 // ranges past 32 go to the spill list here.  A hit of the region's reference
 // haplotype is also listed for the reuse of its window by the HAP_DEDUP
 // haplotypes; a helper reference haplotype (past the region's distinct
-// haplotypes) has no counts of its own.  The loads are issued in three
-// dependent rounds (strand fields | weights, region, position, N mask | inner
-// ranges).
-__device__ __forceinline__ uint32_t score_candidate(const ScanArgs &A, const uint32_t *words, const CandHap &hp,
-                                                    uint32_t hap, uint32_t g, uint32_t i, uint32_t *key0) {
+// haplotypes) has no counts of its own.
+// Every load is issued as soon as its address is known, in two rounds behind the
+// descriptor's, each awaited once: round A (addresses from the candidate and hp) the
+// strand fields, the tile's depth, the region, the position, the N mask, the packed
+// words and the first kRunsUpFront diff runs; round B the weights, the first
+// kInnerUpFront inner ranges and, for a possible donor, its share offsets (speculative:
+// in range for every haplotype of the launch).  The tests follow in the order of
+// pattern.rs; only what lies past the batches (runs 5-16, ranges 3-32) is loaded later,
+// by a lane that is still undecided.
+__device__ __forceinline__ CandHit score_candidate(const ScanArgs &A, const uint32_t *words, const CandHap &hp,
+                                                   uint32_t hap, uint32_t g, uint32_t i) {
+    CandHit R{0, 0, 0, 0, 0};
     const int32_t *meta = A.mmeta + (size_t)(g >> 6) * kGMetaInts;
     const uint32_t sn = g & 63u;
-    const int4 sf = *reinterpret_cast<const int4 *>(meta + kGStrandInts * sn);  // min, woff, len, slot
-    const DevRegion rg = A.regions[hp.region];
-    const uint32_t ic = min(i, hp.len - 1);  // i + L > len: no hit (below), reads stay in range
-    const int32_t p = (hp.flags & HAP_HAS_POS) ? A.posrel[hp.pos_off + ic] : (int32_t)i;
-    uint32_t live = 0xFFFFFFFFu;  // bit j: base i + j is not N
+    const bool dedup = (hp.flags & HAP_DEDUP) && A.dedup;
+    const bool donor = (hp.flags & HAP_DEDUP) && (A.share_off[0] || A.share_off[1]);  // its sharers hit too
+    // round A
+    int4 sf = *reinterpret_cast<const int4 *>(meta + kGStrandInts * sn);  // min, woff, len, slot
+    int32_t depth = meta[kGDepth];
+    const DevRegion *rgp = A.regions + hp.region;
+    uint32_t inner_off = rgp->inner_off, n_inner = rgp->n_inner, hap_begin = rgp->hap_begin, hap_count = rgp->hap_count;
+    const uint32_t ic = min(i, max(hp.len, 1u) - 1);  // i + L > len: no hit (below), reads stay in range
+    int32_t p = (int32_t)i;
+    if (hp.flags & HAP_HAS_POS) p = A.posrel[hp.pos_off + ic];
+    uint32_t m0 = 0, m1 = 0;
     if (hp.flags & HAP_HAS_N) {
         const uint32_t *m = A.nmask + hp.nmask_off + (ic >> 5);
-        live = ~__builtin_amdgcn_alignbit(m[1], m[0], ic & 31);
+        m0 = m[0];
+        m1 = m[1];
     }
+    const uint32_t *w = words + hp.word_off + (ic >> 4);
+    uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
+    uint32_t ra[kRunsUpFront], rb[kRunsUpFront];  // (no run: [~0, 0] meets no window)
+    const uint32_t n_runs = dedup ? hp.n_druns : 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < kRunsUpFront; j++) {
+        ra[j] = 0xFFFFFFFFu;
+        rb[j] = 0;
+        if (j < n_runs) {
+            ra[j] = A.druns[2 * (size_t)(hp.drun_off + j)];
+            rb[j] = A.druns[2 * (size_t)(hp.drun_off + j) + 1];
+        }
+    }
+    arrived(sf.x), arrived(sf.y), arrived(sf.z), arrived(sf.w), arrived(depth);
+    arrived(inner_off), arrived(n_inner), arrived(hap_begin), arrived(hap_count);
+    arrived(p), arrived(m0), arrived(m1), arrived(w0), arrived(w1), arrived(w2);
+#pragma unroll
+    for (uint32_t j = 0; j < kRunsUpFront; j++) arrived(ra[j]), arrived(rb[j]);
+    // round B
     const uint32_t L = (uint32_t)sf.z;
-    if (i + L > hp.len) return 0;                       // past the end (pattern.rs:147-150)
-    const int32_t sc = exact_score(words, hp, i, L, A.mweights + sf.y, live);
-    if (!(sc > sf.x)) return 0;                         // strict (pattern.rs:151)
-    if ((hp.flags & HAP_DEDUP) && A.dedup) {  // columns [i, i + L) the reference's: its hit (key assembly)
-        bool dirty = false;
-        for (uint32_t k = hp.drun_off; k < hp.drun_off + hp.n_druns && !dirty; k++)
-            dirty = run_meets(A.druns[2 * k], A.druns[2 * k + 1], i, L);
-        if (!dirty) return 0;
+    const uint32_t sh = 2 * (ic & 15);
+    const uint32_t img[2] = {__builtin_amdgcn_alignbit(w1, w0, sh), __builtin_amdgcn_alignbit(w2, w1, sh)};
+    const int32_t *wt = A.mweights + sf.y;
+    int32_t v[32];
+#pragma unroll
+    for (uint32_t jb = 0; jb < 32; jb += 8) {
+        if (jb < L) {  // a lane loads only its strand's blocks
+#pragma unroll
+            for (uint32_t j = jb; j < jb + 8; j++) v[j] = wt[4 * j + ((img[j >> 4] >> (2 * (j & 15))) & 3u)];
+        } else {
+#pragma unroll
+            for (uint32_t j = jb; j < jb + 8; j++) v[j] = 0;
+        }
     }
-    const bool donor = (hp.flags & HAP_DEDUP) && (A.share_off[0] || A.share_off[1]);  // its sharers hit too
+    const int32_t *inner = A.inner + 2 * (size_t)inner_off;
+    const uint32_t nk = min(n_inner, 32u);
+    int32_t rs[kInnerUpFront], re[kInnerUpFront];
+#pragma unroll
+    for (uint32_t k = 0; k < kInnerUpFront; k++) {
+        rs[k] = re[k] = 0;
+        if (k < nk) {
+            rs[k] = inner[2 * k];
+            re[k] = inner[2 * k + 1];
+        }
+    }
+    R.sc = depth > 2 ? 1u : 0u;  // (strand_class)
+    const uint64_t *so = A.share_off[R.sc];
+    uint32_t e0l = 0, e0h = 0, e1l = 0, e1h = 0;
+    if (donor && so) {
+        const uint64_t e0 = so[hap], e1 = so[hap + 1];
+        e0l = (uint32_t)e0, e0h = (uint32_t)(e0 >> 32), e1l = (uint32_t)e1, e1h = (uint32_t)(e1 >> 32);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 32; j++) arrived(v[j]);
+#pragma unroll
+    for (uint32_t k = 0; k < kInnerUpFront; k++) arrived(rs[k]), arrived(re[k]);
+    arrived(e0l), arrived(e0h), arrived(e1l), arrived(e1h);
+    // the tests
+    if (i + L > hp.len) return R;                       // past the end (pattern.rs:147-150)
+    const uint32_t live = ~__builtin_amdgcn_alignbit(m1, m0, ic & 31);  // bit j: base i + j is not N
+    const uint32_t keep = live & (L >= 32 ? ~0u : (1u << L) - 1);      // columns < L that are not N
+    int32_t sc = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 32; j++) sc += v[j] & -(int32_t)((keep >> j) & 1u);  // N scores 0
+    if (!(sc > sf.x)) return R;                         // strict (pattern.rs:151)
+    if (dedup) {  // columns [i, i + L) the reference's: its hit (key assembly)
+        bool dirty = false;
+#pragma unroll
+        for (uint32_t j = 0; j < kRunsUpFront; j++) dirty = dirty || run_meets(ra[j], rb[j], i, L);
+        for (uint32_t k = hp.drun_off + kRunsUpFront; k < hp.drun_off + hp.n_druns && !dirty; k++)
+            dirty = run_meets(A.druns[2 * (size_t)k], A.druns[2 * (size_t)k + 1], i, L);
+        if (!dirty) return R;
+    }
     if (A.hits && i / 64 < A.hits_wpp) {
         auto mark = [&](uint32_t x) {
             atomicOr(A.hits + ((size_t)x * A.n_patterns_total + (uint32_t)meta[kGOrig + sn]) * A.hits_wpp + i / 64,
                      1ull << (i & 63));
         };
         mark(hap);
-        if (donor) for_sharers(A, strand_class(A, g), hap, i, mark);
+        if (donor) for_sharers(A, R.sc, hap, i, mark);
     }
     if ((hp.flags & HAP_REF) && A.dedup) {  // for the HAP_DEDUP haplotypes' unscanned windows
         const uint32_t at = atomicAdd(A.ref_count + hp.region, 1u);
@@ -325,29 +401,36 @@ __device__ __forceinline__ uint32_t score_candidate(const ScanArgs &A, const uin
             spill_record(A, hp.region | 0x80000000u, g, i);
         }
     }
-    if (hap >= rg.hap_begin + rg.hap_count) return 0;  // a helper reference haplotype: no keys
-    const uint32_t off0 = (uint32_t)sf.w * rg.n_inner;
-    const int32_t *inner = A.inner + 2 * (size_t)rg.inner_off;
+    if (hap >= hap_begin + hap_count) return R;  // a helper reference haplotype: no keys
+    const uint32_t off0 = (uint32_t)sf.w * n_inner;
     // range.rs:18-21 as main.rs:503 uses it
-    uint32_t mask = 0;
-    const uint32_t nk = min(rg.n_inner, 32u);
-    for (uint32_t k = 0; k < nk; k++) {
-        const int2 r = *reinterpret_cast<const int2 *>(inner + 2 * k);
-        const uint32_t span = (uint32_t)(r.y - r.x);
-        if ((uint32_t)(p - r.x) <= span || (uint32_t)(p + (int32_t)L - 1 - r.x) <= span) mask |= 1u << k;
-    }
-    for (uint32_t k = 32; k < rg.n_inner; k++) {        // ranges past 32 (rare)
-        const int32_t s = inner[2 * k], en = inner[2 * k + 1];
+    auto overlaps = [&](int32_t s, int32_t en) {
         const uint32_t span = (uint32_t)(en - s);
-        if ((uint32_t)(p - s) <= span || (uint32_t)(p + (int32_t)L - 1 - s) <= span) {
+        return (uint32_t)(p - s) <= span || (uint32_t)(p + (int32_t)L - 1 - s) <= span;
+    };
+    uint32_t mask = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kInnerUpFront; k++)
+        if (k < nk && overlaps(rs[k], re[k])) mask |= 1u << k;
+    for (uint32_t k = kInnerUpFront; k < nk; k++) {
+        const int2 r = *reinterpret_cast<const int2 *>(inner + 2 * k);
+        if (overlaps(r.x, r.y)) mask |= 1u << k;
+    }
+    for (uint32_t k = 32; k < n_inner; k++) {           // ranges past 32 (rare)
+        if (overlaps(inner[2 * k], inner[2 * k + 1])) {
             spill_record(A, hp.region, A.hap_base + hap, off0 + k);
             if (donor)
-                for_sharers(A, strand_class(A, g), hap, i,
+                for_sharers(A, R.sc, hap, i,
                             [&](uint32_t x) { spill_record(A, hp.region, A.hap_base + x, off0 + k); });
         }
     }
-    *key0 = off0;
-    return mask;
+    R.key0 = off0;
+    R.mask = mask;
+    if (mask) {  // the donor's entries, for the caller's expansion
+        R.se = (uint64_t)e0l | ((uint64_t)e0h << 32);
+        R.sn = (uint32_t)(((uint64_t)e1l | ((uint64_t)e1h << 32)) - R.se);
+    }
+    return R;
 }
 
 // The candidate lists' room per wave (A.cand_cap per workgroup; the hit lists':
@@ -364,17 +447,57 @@ __device__ __forceinline__ WaveCands unit_cands(const ScanArgs &A, uint32_t slot
     return WaveCands{ccap, reinterpret_cast<uint2 *>(A.cands) + (size_t)slot * A.cand_cap + (size_t)wave * ccap};
 }
 
+#ifdef TFBS_SCAN_PROF
+// per wave of the workgroup's (unit's) first slot: [0] s_memtime at the kernel's start,
+// [1] after the staging barrier, [2] after the scan loops, [3] cycles waited at the super
+// tiles' barriers (TFBS_ROUND_PROF, else 0), [4] after the rescoring, [5] / [6]
+// s_memrealtime (100 MHz, one clock for the chip) at the start and the end, [7] pairs
+// scored | candidates << 32; [8, 16) TFBS_ROUND_PROF's split, or without it the
+// rescoring's (rescore_list): [8] cycles from a pass's start to its candidates scored
+// and its donors' entry ranges known, summed over the passes, [9] cycles in the
+// expansion's rounds, [10] donor hits, [11] the entries they span (T), [13] passes, [14]
+// cycles in the hits' own appends (with the entries' prefix and the first round's fetch
+// issued in front of them); [12] stays 0: tools/scan_prof.py tells the builds apart by it
+#define SCAN_STAMP(k, v) \
+    do { if (A.prof && lane == 0) A.prof[((size_t)slot * kMBlockWaves + wave) * kScanProfWords + (k)] = (v); } while (0)
+#else
+#define SCAN_STAMP(k, v) do { } while (0)
+#endif
+#if defined(TFBS_SCAN_PROF) && !defined(TFBS_ROUND_PROF)
+#define RESCORE_T() ({ __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
+                       __builtin_amdgcn_sched_barrier(0); t_; })
+#define RESCORE_PROF(...) __VA_ARGS__
+#else
+#define RESCORE_PROF(...)
+#endif
+
 // The wave's listed candidates, one per lane (after its scan: no accumulator
 // is live, and the other waves keep the matrix cores busy); each hit's
 // (haplotype, key) pairs are appended to the wave's part of its group's hit
-// list in lane order (ballot prefix: no atomics), the excess spilled.
+// list (ballot prefix: no atomics), the excess spilled.
 // UNIT: the candidates of a unit of ngu groups (first haplotype h0, first slot `slot`),
-// rescored once -- the descriptors and words from global memory (A.hd, A.hd2, words =
-// A.words: the LDS copies are the last group's), one more load in the chain but one
-// chain per unit --; a hit goes to the wave list of its haplotype's group (slot + the
-// group in the unit), the ballot prefix taken over that group's lanes, one count per
-// group (hnv: lane u holds group u's).  candn likewise: a group's are its candidates
-// in the lists; those past the lists (cn - n) are counted at the unit's first slot.
+// rescored once -- the descriptors from the unit's resident copies (s_hdu, s_hd2u), the
+// words from global memory (words = A.words) --; a hit goes to the wave list of its
+// haplotype's group (slot + the group in the unit), the ballot prefix taken over that
+// group's lanes, one count per group (hnv: lane u holds group u's).  candn likewise: a
+// group's are its candidates in the lists; those past the lists (cn - n) are counted at
+// the unit's first slot.
+// A pass (64 candidates) is: the scores (score_candidate: the descriptor from LDS, then
+// two rounds of loads); the hits' own pairs, per group; the expansion of the donors'
+// hits to their sharers (shared windows) over the pass's flattened entry space -- the
+// donor lanes' entry counts sn in a wave prefix, total T, and in each round of 64 lane j
+// owns entry t0 + j: it finds the donor lane whose range holds it, takes that lane's
+// hit by shuffle, loads the one share entry and tests the hit's window against it; the
+// covering entries append the hit's pairs for their sharers to the list of the DONOR's
+// group, by the same ballot prefix, one key bit per ballot.  One load round per 64
+// entries of however many donors, ceil(T / 64) rounds a pass, and a round's load is issued a
+// round ahead: the first before the hits' own pairs are listed, the next before this
+// round's pairs are appended.  The donor of an entry:
+// the donors whose ranges start inside the round write their lane at the start's place
+// in a 64-word table (the wave's queue LDS, empty once the scan is over: s_qdata is only
+// touched by its own wave's queue_tile / drain_queue, and by the fused post-scan behind a
+// barrier); a lane's donor is the last start at or before it, or the donor that the
+// round before ended in.
 template <bool UNIT>
 __device__ __forceinline__ void rescore_list(const ScanArgs &A, const uint32_t *words, uint32_t h0, uint32_t slot,
                                              uint32_t ngu, uint32_t wave, uint32_t lane, uint32_t cn) {
@@ -382,85 +505,122 @@ __device__ __forceinline__ void rescore_list(const ScanArgs &A, const uint32_t *
     const WaveCands W = unit_cands(A, slot, ngu, wave);
     const uint32_t lcap = min(W.ccap, kWaveCands), n = min(cn, lcap + W.ccap);
     const uint2 *glist = W.clist;
-    const bool shared = A.share_off[0] || A.share_off[1];
+    // the round's range starts (64 words); volatile: lanes read what OTHER lanes of the wave wrote, which the
+    // compiler would otherwise replace by the lane's own store (the wave's LDS accesses are executed in order)
+    volatile uint32_t *s_start = reinterpret_cast<volatile uint32_t *>(&s_qdata[wave][0]);
     uint32_t hnv = 0, cnv = lane == 0 ? cn - n : 0u;
+    RESCORE_PROF(unsigned long long p_score = 0, p_exp = 0, p_own = 0, p_don = 0, p_T = 0, p_pass = 0;)
+    auto list_of = [&](uint32_t u) {
+        return reinterpret_cast<uint2 *>(A.hitl) + (size_t)(slot + u) * A.hit_cap + (size_t)wave * cap;
+    };
+    // the pairs (x, key0 + bit) of every set bit of m, behind the list's hn entries (uniform)
+    auto append = [&](uint2 *out, uint32_t &hn, uint32_t m, uint32_t x, uint32_t key0, uint32_t region) {
+        uint64_t act;
+        while ((act = __ballot(m != 0)) != 0) {
+            if (m) {
+                const uint32_t at = hn + __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32),
+                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0));
+                const uint32_t key = key0 + __builtin_ctz(m);
+                m &= m - 1;
+                if (at < cap) out[at] = make_uint2(A.hap_base + x, key);
+                else spill_record(A, region, A.hap_base + x, key);
+            }
+            hn += (uint32_t)__popcll(act);
+        }
+    };
     for (uint32_t k0 = 0; k0 < n; k0 += 64) {
+        RESCORE_PROF(const unsigned long long tp0 = RESCORE_T();)
         const uint32_t k = k0 + lane;
-        uint32_t mask = 0, key0 = 0, hap = h0, g = 0, win = 0, gi = 0, flags = 0, region = 0;
+        CandHit R{0, 0, 0, 0, 0};
+        uint32_t hap = h0, win = 0, gi = 0, region = 0;
         if (k < n) {
             const uint2 c = k < lcap ? s_cand[wave][k] : glist[k - lcap];
             const uint32_t hl = c.x >> 24;  // the haplotype in the group (unit)
             hap = h0 + hl;
-            g = c.x & 0xFFFFFFu;
             win = c.y;
-            // the haplotype's descriptors: staged in LDS, a unit's from global memory
-            const CandHap hp = UNIT ? CandHap::of(A.hd[hap], A.hd2[hap]) : CandHap::of(s_hd[hl], s_hd2[hl]);
+            const CandHap hp = UNIT ? CandHap::of(s_hdu[hl], s_hd2u[hl]) : CandHap::of(s_hd[hl], s_hd2[hl]);
             if (UNIT)  // its group in the unit (no division: its reciprocal would live across the scan)
                 for (uint32_t u = 1; u < kMMaxUnit; u++) gi += hl >= u * A.haps_per_block ? 1u : 0u;
-            flags = hp.flags;
             region = hp.region;
-            mask = score_candidate(A, words, hp, hap, g, win, &key0);
+            R = score_candidate(A, words, hp, hap, c.x & 0xFFFFFFu, win);
         }
-        // a donor's hit is its sharers' too (shared windows): the lane's class and entries
-        uint32_t sc = 0, sn = 0;
-        uint64_t se = 0;
-        if (shared && mask && (flags & HAP_DEDUP)) {
-            sc = strand_class(A, g);
-            if (A.share_off[sc]) {
-                se = A.share_off[sc][hap];
-                sn = (uint32_t)(A.share_off[sc][hap + 1] - se);
-            }
+        const uint32_t sn = R.sn;
+#if defined(TFBS_SCAN_PROF) && !defined(TFBS_ROUND_PROF)
+        {   // (the scores and the donors' ranges awaited: the ballots' operands)
+            const uint64_t don = __ballot(sn != 0), hit = __ballot(R.mask != 0);
+            asm volatile("" ::"s"(don), "s"(hit));
+            p_score += RESCORE_T() - tp0;
+            p_don += (uint32_t)__popcll(don);
+            p_pass++;
         }
+        const unsigned long long tu0 = RESCORE_T();
+#endif
+        // the expansion: the donor lanes' entries [se, se + sn) laid end to end, entry t of
+        // the pass = entry t - excl of the lane whose [excl, excl + sn) holds t
+        uint32_t incl = sn;
+#pragma unroll
+        for (uint32_t o = 1; o < 64; o <<= 1) {
+            const uint32_t t = (uint32_t)__shfl_up((int)incl, o);
+            if (lane >= o) incl += t;
+        }
+        const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63), excl = incl - sn;
+        const uint64_t ebase = R.se - excl;  // + t: the lane's entry t (mod 2^64)
+        const uint32_t meta = R.sc | (gi << 1);
+        uint32_t carry = 0;  // the donor lane that the round before ended in
+        // round t0's entry of this lane (its load issued) and the hit it belongs to
+        struct Entry {
+            uint2 s;
+            uint32_t meta, win, key0, mask, region;
+        };
+        auto fetch = [&](uint32_t t0) {
+            const uint32_t t = t0 + lane;
+            s_start[lane] = 0xFFFFFFFFu;
+            if (sn != 0 && excl - t0 < 64u) s_start[excl - t0] = lane;
+            const uint32_t sv = s_start[lane];
+            const uint64_t starts = __ballot(sv != 0xFFFFFFFFu);
+            const uint64_t below = starts & ((2ull << lane) - 1);  // the starts at or before this lane
+            const uint32_t from = (uint32_t)__shfl((int)sv, below ? 63 - __builtin_clzll(below) : 0);
+            const uint32_t src = below ? from : carry;
+            carry = (uint32_t)__builtin_amdgcn_readlane((int)src, 63);
+            const uint64_t d_e = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)ebase, (int)src) |
+                                  ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(ebase >> 32), (int)src) << 32)) + t;
+            Entry E;
+            E.meta = (uint32_t)__shfl((int)meta, (int)src);
+            E.win = (uint32_t)__shfl((int)win, (int)src);
+            E.key0 = (uint32_t)__shfl((int)R.key0, (int)src);
+            E.mask = (uint32_t)__shfl((int)R.mask, (int)src);
+            E.region = (uint32_t)__shfl((int)region, (int)src);
+            E.s = make_uint2(0, 0);
+            if (t < T) E.s = A.share[E.meta & 1u][d_e];
+            return E;
+        };
+        Entry cur{make_uint2(0, 0), 0, 0, 0, 0, 0};
+        if (T) cur = fetch(0);  // (in flight while the hits' own pairs are listed)
         for (uint32_t u = 0; u < ngu; u++) {  // the lanes of group u (wave-uniform loop)
             const bool in = !UNIT || gi == u;
-            uint2 *out = reinterpret_cast<uint2 *>(A.hitl) + (size_t)(slot + u) * A.hit_cap + (size_t)wave * cap;
             uint32_t hn = (uint32_t)__builtin_amdgcn_readlane((int)hnv, (int)u);  // wave-uniform
             const uint32_t listed = (uint32_t)__popcll(__ballot(k < n && in));  // (by the whole wave)
             if (lane == u) cnv += listed;
-            uint32_t m = in ? mask : 0u;
-            uint64_t act;
-            while ((act = __ballot(m != 0)) != 0) {
-                if (m) {
-                    const uint32_t at = hn + __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32),
-                                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0));
-                    const uint32_t key = key0 + __builtin_ctz(m);
-                    m &= m - 1;
-                    if (at < cap) out[at] = make_uint2(A.hap_base + hap, key);
-                    else spill_record(A, region, A.hap_base + hap, key);
-                }
-                hn += (uint32_t)__popcll(act);
-            }
-            // expansion, one hit at a time: 64 lanes test 64 of the donor's entries, each
-            // covering entry's sharer gets the hit's pairs (the same ballot-prefix append)
-            for (uint64_t todo = __ballot(in && sn != 0); todo; todo &= todo - 1) {
-                const int src = __builtin_ctzll(todo);
-                const uint32_t d_c = (uint32_t)__shfl((int)sc, src), d_n = (uint32_t)__shfl((int)sn, src);
-                const uint64_t d_e = (uint64_t)(uint32_t)__shfl((int)(uint32_t)se, src) |
-                                     ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(se >> 32), src) << 32);
-                const uint32_t d_i = (uint32_t)__shfl((int)win, src), d_key0 = (uint32_t)__shfl((int)key0, src);
-                const uint32_t d_mask = (uint32_t)__shfl((int)mask, src);
-                const uint32_t d_region = (uint32_t)__shfl((int)region, src);
-                for (uint32_t e0 = 0; e0 < d_n; e0 += 64) {
-                    uint2 s = make_uint2(0, 0);
-                    if (e0 + lane < d_n) s = A.share[d_c][d_e + e0 + lane];
-                    const bool mine = d_i >= (s.y & 0xFFFFu) && d_i < (s.y >> 16);  // (no entry: [0, 0))
-                    const uint64_t cov = __ballot(mine);
-                    if (!cov) continue;
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(cov >> 32),
-                                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)cov, 0));
-                    for (uint32_t dm = d_mask; dm; dm &= dm - 1) {
-                        if (mine) {
-                            const uint32_t at = hn + rank, key = d_key0 + __builtin_ctz(dm);
-                            if (at < cap) out[at] = make_uint2(A.hap_base + s.x, key);
-                            else spill_record(A, d_region, A.hap_base + s.x, key);
-                        }
-                        hn += (uint32_t)__popcll(cov);
-                    }
-                }
-            }
+            append(list_of(u), hn, in ? R.mask : 0u, hap, R.key0, region);
             if (lane == u) hnv = hn;
         }
+        RESCORE_PROF(const unsigned long long tu1 = RESCORE_T(); p_own += tu1 - tu0;)
+        for (uint32_t t0 = 0; t0 < T; t0 += 64) {
+            Entry nx = cur;
+            if (t0 + 64 < T) nx = fetch(t0 + 64);  // the next round's entries, in flight behind this round's
+            const bool mine = cur.win >= (cur.s.y & 0xFFFFu) && cur.win < (cur.s.y >> 16);  // (no entry: [0, 0))
+            for (uint32_t u = 0; u < ngu; u++) {  // the entries of group u's donors
+                uint32_t hn = (uint32_t)__builtin_amdgcn_readlane((int)hnv, (int)u);
+                append(list_of(u), hn, mine && (!UNIT || (cur.meta >> 1) == u) ? cur.mask : 0u, cur.s.x, cur.key0,
+                       cur.region);
+                if (lane == u) hnv = hn;
+            }
+            cur = nx;
+        }
+        RESCORE_PROF(p_exp += RESCORE_T() - tu1; p_T += T;)
     }
+    RESCORE_PROF(SCAN_STAMP(8, p_score); SCAN_STAMP(9, p_exp); SCAN_STAMP(10, p_don); SCAN_STAMP(11, p_T);
+                 SCAN_STAMP(13, p_pass); SCAN_STAMP(14, p_own);)
     if (lane < ngu) {  // every slot of the unit, also a group's without a window
         A.hitn[(size_t)(slot + lane) * kMBlockWaves + wave] = min(hnv, cap);
         // (the list counters: per-wave stores summed on the host -- one atomic per wave on a
@@ -781,7 +941,6 @@ __device__ __forceinline__ void entry_onehot(const ScanArgs &A, const uint32_t *
 // class, or past the unit's last, adds none: x of the last entry is the pool's size),
 // y = the entries of its list | narrow << 31, (z, w) = the list's first entry in
 // wlist / wlist16.
-__shared__ uint4 s_hdu[kMMaxUnit * kMMaxHapsPerBlock];
 __shared__ uint4 s_pool[2][kMMaxUnit];
 static_assert(kMMaxUnit * kMMaxHapsPerBlock <= kMBlock, "one thread per descriptor of a unit");
 constexpr uint32_t kPoolNarrow = 1u << 31;
@@ -930,18 +1089,6 @@ __device__ __forceinline__ uint32_t scan_pool(const ScanArgs &A, const DevMSuper
 // handed to the waves two at a time from an LDS counter -- the waves finish
 // together however the windows fall -- and the next pair's list entries are
 // loaded while the current pair is scored.
-#ifdef TFBS_SCAN_PROF
-// per wave of the workgroup's (unit's) first slot: [0] s_memtime at the kernel's start,
-// [1] after the staging barrier, [2] after the scan loops, [3] cycles waited at the super
-// tiles' barriers (TFBS_ROUND_PROF, else 0), [4] after the rescoring, [5] / [6]
-// s_memrealtime (100 MHz, one clock for the chip) at the start and the end, [7] pairs
-// scored | candidates << 32; [8, 16) TFBS_ROUND_PROF's split
-#define SCAN_STAMP(k, v) \
-    do { if (A.prof && lane == 0) A.prof[((size_t)slot * kMBlockWaves + wave) * kScanProfWords + (k)] = (v); } while (0)
-#else
-#define SCAN_STAMP(k, v) do { } while (0)
-#endif
-
 // One super tile's window pairs over the group's list of its depth class, then the
 // wave's last queue records decoded (qn, cn: the wave's queued records and listed
 // candidates, carried over super tiles).  Returns the pairs this wave scored.
@@ -1107,7 +1254,10 @@ __global__ __launch_bounds__(kMBlock, 4) void scan_mfma_all_kernel(ScanArgs A) {
         words = stage_group<STAGED>(A, smem, h0, min(h0 + hpb, A.n_haps) - h0);
     } else {
         const uint32_t hn = min(h0 + ngu * hpb, A.n_haps) - h0;
-        if (threadIdx.x < hn) s_hdu[threadIdx.x] = A.hd[h0 + threadIdx.x];
+        if (threadIdx.x < hn) {
+            s_hdu[threadIdx.x] = A.hd[h0 + threadIdx.x];
+            s_hd2u[threadIdx.x] = A.hd2[h0 + threadIdx.x];
+        }
         if (STAGED) words = stage_unit_words(A, smem, h0, hn, min(A.unit_lds, ngu), &nlds);
         if (threadIdx.x < 64) pool_fill(A, hg0, h0, ngu, threadIdx.x);
     }
@@ -1187,9 +1337,9 @@ __global__ __launch_bounds__(256) void cand_over_kernel(ScanArgs A) {
     for (uint32_t k = blockIdx.x * 256 + threadIdx.x; k < n; k += gridDim.x * 256) {
         const uint32_t hap = A.cand_over[3 * (size_t)k], g = A.cand_over[3 * (size_t)k + 1];
         const DevHap hp = A.haps[hap];
-        uint32_t key0 = 0;
         const uint32_t i = A.cand_over[3 * (size_t)k + 2];
-        const uint32_t m0 = score_candidate(A, A.words, CandHap::of(hp), hap, g, i, &key0);
+        const CandHit R = score_candidate(A, A.words, CandHap::of(hp), hap, g, i);
+        const uint32_t m0 = R.mask, key0 = R.key0;
         for (uint32_t m = m0; m; m &= m - 1) spill_record(A, hp.region, hap, key0 + __builtin_ctz(m));
         if (m0 && (hp.flags & HAP_DEDUP))  // shared windows: the sharers' pairs
             for_sharers(A, strand_class(A, g), hap, i, [&](uint32_t x) {
@@ -1265,7 +1415,9 @@ __device__ void post_candidates(const ScanArgs &A, uint32_t tid, uint32_t blk, u
             const DevHap hp = A.haps[hap];
             region = hp.region;
             si = A.cand_over[3 * (size_t)k + 2];
-            m = score_candidate(A, A.words, CandHap::of(hp), hap, g, si, &key0);
+            const CandHit R = score_candidate(A, A.words, CandHap::of(hp), hap, g, si);
+            m = R.mask;
+            key0 = R.key0;
             if (m && (hp.flags & HAP_DEDUP)) {
                 sc = strand_class(A, g);
                 for_sharers(A, sc, hap, si, [&](uint32_t) { ns++; });
@@ -1461,7 +1613,7 @@ int launch_mfma_all(const ScanArgs &a0, const DevMSuper *supers, uint32_t n_supe
     uint32_t unit_lds = 0;
     size_t unit_bytes = base;
     if (G > 1) {
-        const size_t static_unit = static_lds - sizeof(s_hd) - sizeof(s_hd2) + sizeof(s_hdu) + sizeof(s_pool) + 64;
+        const size_t static_unit = static_lds - sizeof(s_hd) - sizeof(s_hd2) + sizeof(s_hdu) + sizeof(s_hd2u) + sizeof(s_pool) + 64;
         const size_t gw = std::max<size_t>(((size_t)group_words * 4 + 15) / 16 * 16, 16);
         const size_t room = kMStagedMax > base + static_unit ? kMStagedMax - base - static_unit : 0;
         // (the host's choice is global words: measured as fast as the LDS copy or faster for every G

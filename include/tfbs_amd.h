@@ -1252,6 +1252,13 @@ int tfbs_synth_fill_batch(tfbs_batch *b, uint64_t seed, uint64_t first, uint64_t
  * asks for it.  Waits for the stream.  Zeros for a class without tiles. */
 int tfbs_ctx_group_pairs(tfbs_ctx *ctx, int cls, uint32_t *pairs, size_t cap, size_t *n_groups);
 
+/* The resident batch's shared windows (debug API, as tfbs_ctx_group_pairs): entries[h] =
+ * the sharer entries of haplotype h (batch order) as a donor in depth class cls -- what
+ * the rescoring's expansion walks for each of h's hits.  *n_haps receives the haplotype
+ * count; cap = 0 only asks for it.  Waits for the stream.  Zeros when nothing is shared
+ * in the class (TFBS_SHARE=0, or no tile or no sharer of the class). */
+int tfbs_ctx_share_entries(tfbs_ctx *ctx, int cls, uint32_t *entries, size_t cap, size_t *n_haps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,11 @@ split and, as shares of the loop, the super tiles' restaging (images after the f
 from the barrier before the copy to the barrier after it) and the wave's wait at the
 super tiles' two barriers (`barrier_wait`, every super tile: the part of the staging
 and restaging that is waiting for the workgroup's slowest wave, not copying; inside a
-super tile there is no barrier).  The last scan in the file is read.
+super tile there is no barrier).  A TFBS_SCAN_PROF build without TFBS_ROUND_PROF adds the
+rescoring's split (`rescore_split`, per wave: mean, p50, p90, and the share of the
+`rescore` phase): the candidates' scoring pass (a pass's start to its scores and donor
+ranges known), the hits' own appends, the sharers' expansion, the donor hits, the share
+entries they span (T) and the passes.  The last scan in the file is read.
 
 Usage: python tools/scan_prof.py FILE [OUT_JSON]
 """
@@ -84,6 +88,22 @@ def main():
                 "barrier_wait": {"cycles_mean_per_wave": float(bw / live.sum()),
                                  "of_staging_and_loop": float(bw / (loop + ph["staging"][live].sum()))},
                 "cycles_mean_per_wave": {"restaging": float(rs / live.sum())},
+            }
+        elif w[:, :, 13].sum() > 0:  # the rescoring's split (words 8-11, 13, 14; 12 is ROUND_PROF's)
+            res = ph["rescore"][live]
+
+            def stat(v, share=True):
+                v = v[live]
+                r = {"mean": float(v.mean()), "p50": float(np.percentile(v, 50)), "p90": float(np.percentile(v, 90))}
+                if share:
+                    r["of_rescore"] = float(v.sum() / max(1, res.sum()))
+                return r
+            rec["rescore_split"] = {
+                "scoring_pass_cycles": stat(w[:, :, 8]), "own_append_cycles": stat(w[:, :, 14]),
+                "expansion_cycles": stat(w[:, :, 9]),
+                "rescore_cycles": stat(ph["rescore"], False), "donor_hits": stat(w[:, :, 10], False),
+                "entries_T": stat(w[:, :, 11], False), "passes": stat(w[:, :, 13], False),
+                "rescore_of_wave": float(res.sum() / tot[live].sum()),
             }
         out["launches"].append(rec)
     if len(sys.argv) > 2:
