@@ -1,7 +1,8 @@
 // What the brute-force kernels (scan_hits.hip, scan_best.hip, scan_affinity.hip), the variant-effect kernel
 // (scan_effects.hip: pair_head, the scoring, the drivers' base), the mutation-scan kernel
 // (scan_mutscan.hip: pair_head_at, the scoring of one window, the drivers' base) and their drivers share.  A HIP
-// header: only .hip sources include it.
+// header: only .hip sources include it.  What scan_best.hip and scan_affinity.hip share beyond it -- the
+// range sweeps, the dense records' places, the chunk driver -- is range_sweep.hpp's, on top of this one.
 //  * Device: the exact scoring code (bases16, score_mono, score_dinuc), the kernels' prologue
 //    in two steps (pair_head, PAIR_OPEN), what a wave knows of its pair (PairScan) and the walk
 //    over the pair's windows (WALK_CHUNKS, scored_window, SCORE_WINDOWS).  A kernel keeps what
