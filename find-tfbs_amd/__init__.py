@@ -436,6 +436,17 @@ class Scanner:
         (RegionBatch.assembly_paths)."""
         check(lib().tfbs_ctx_assembly_trace(self.h, 1 if on else 0))
 
+    def region_asm(self):
+        """tfbs_ctx_region_asm: the key assembly's static records of what was last uploaded --
+        (region_asm, hap_reuse): per region (run0, nruns, lmax, 0), per haplotype its reuse
+        descriptor (0xFFFFFFFF: none, else (run offset - run0) | runs << 16)."""
+        nr, nh = C.c_size_t(0), C.c_size_t(0)
+        check(lib().tfbs_ctx_region_asm(self.h, None, 0, None, 0, C.byref(nr), C.byref(nh)))
+        ra = (C.c_uint32 * (4 * max(nr.value, 1)))()
+        hr = (C.c_uint32 * max(nh.value, 1))()
+        check(lib().tfbs_ctx_region_asm(self.h, ra, max(nr.value, 1), hr, max(nh.value, 1), C.byref(nr), C.byref(nh)))
+        return ([tuple(ra[4 * r:4 * r + 4]) for r in range(nr.value)], list(hr[:nh.value]))
+
     def assembly_figures(self):
         """tfbs_ctx_assembly_figures of the last checked assembly: {"left" (regions left to
         key_asm_kernel), "arena" (arena words asked for), "spill" (spill records), "wide" /

@@ -196,6 +196,8 @@ SIGNATURES = [
     ("tfbs_ctx_last_assemble_ms", C.c_float, [vp]),
     ("tfbs_ctx_assembly_trace", C.c_int, [vp, C.c_int]),
     ("tfbs_batch_assembly_paths", C.c_int, [vp, vp, u32p, C.c_uint32]),
+    ("tfbs_ctx_region_asm", C.c_int, [vp, u32p, C.c_size_t, u32p, C.c_size_t, C.POINTER(C.c_size_t),
+                                     C.POINTER(C.c_size_t)]),
     ("tfbs_ctx_assembly_figures", C.c_int, [vp, u64p]),
     ("tfbs_ctx_post_figures", C.c_int, [vp, u64p]),
     ("tfbs_batch_region_layout", C.c_int, [vp, C.c_size_t, u32p]),

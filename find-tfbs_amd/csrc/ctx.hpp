@@ -100,6 +100,9 @@ struct BatchImage {
     DevBuf<DevHap> haps;
     DevBuf<uint32_t> druns;  // HAP_DEDUP haplotypes' diff runs
     DevBuf<DevRegion> regions;
+    // key_fast_kernel's static records (AsmArgs::hap_reuse, region_asm), made by build_lists
+    DevBuf<uint32_t> hap_reuse;
+    DevBuf<uint4> region_asm;
     uint32_t n_regions = 0;
     const tfbs_batch *resident = nullptr;
     uint64_t upload_gen = 0;        // tfbs_batch_upload calls (a new batch image: a new graph)
@@ -107,6 +110,7 @@ struct BatchImage {
     template <class F>
     void each_buf(F &&f) const {
         f(words), f(nmask), f(counts), f(posrel), f(inner), f(haps), f(druns), f(regions);
+        f(hap_reuse), f(region_asm);
     }
 };
 

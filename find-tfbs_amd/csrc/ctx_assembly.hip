@@ -10,6 +10,8 @@ AsmArgs tfbs::asm_args(tfbs_ctx *ctx, const Batch &B, int mode) {
     a.haps = ctx->img.haps.p;
     a.druns = ctx->img.druns.p;
     a.regions = ctx->img.regions.p;
+    a.hap_reuse = ctx->img.hap_reuse.p;
+    a.region_asm = ctx->img.region_asm.p;
     a.inner = ctx->img.inner.p;
     a.mmeta = ctx->tabs.m_meta.p;
     a.slot_mfma = ctx->tabs.slot_mfma.p;
@@ -25,6 +27,10 @@ AsmArgs tfbs::asm_args(tfbs_ctx *ctx, const Batch &B, int mode) {
     a.spill_sorted = ctx->scan.spill_sorted.p;
     a.spill_off = ctx->scan.spill_boff.p;
     a.spill_cnt = ctx->scan.spill_cnt_ctr ? ctx->asmb.asm_ctr.p + kAsmCtrWords : ctx->scan.spill_bcnt.p;
+    // (key_fast_kernel loads spill_cnt[r] and spill_off[r] with a region's first loads whenever
+    // spill_count is not null, whatever the count: with matrix-core tiles launch_scan sizes
+    // spill_bcnt and spill_boff for every region + 1, and asm_ctr holds the buckets behind its
+    // counter words (enqueue_assembly); without tiles spill_count is null)
     a.spill_count = ctx->plan.m_supers.empty() ? nullptr : ctx->scan.over.p;
     a.spill_cap = ctx->scan.spill_cap;
     a.counts = ctx->img.counts_live ? ctx->img.counts.p : nullptr;
@@ -130,8 +136,8 @@ static int enqueue_assembly(tfbs_ctx *ctx, Batch &B, bool post) {
         a.path = ctx->asmb.asm_path.p;
     }
     if (ctx->knobs.kf_prof_on && nr) {
-        if ((rc = ctx->asmb.kf_prof.ensure((size_t)nr * 16))) return rc;
-        HIP_TRY(hipMemsetAsync(ctx->asmb.kf_prof.p, 0, (size_t)nr * 128, ctx->stream));
+        if ((rc = ctx->asmb.kf_prof.ensure((size_t)nr * kKfProfWords))) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->asmb.kf_prof.p, 0, (size_t)nr * kKfProfWords * 8, ctx->stream));
         a.prof = ctx->asmb.kf_prof.p;
     }
     if ((rc = launch_key_fast(a, nr, a.order ? ctx->asmb.asm_order_big : 0, ctx->stream, ctx->asmb.side, ctx->asmb.kf_fork,
@@ -151,29 +157,34 @@ static int enqueue_assembly(tfbs_ctx *ctx, Batch &B, bool post) {
 // TFBS_KF_PROF: key_fast_kernel's mean phase cycles and sizes over the regions it
 // finished (debug; synchronises).
 static int kf_prof_report(tfbs_ctx *ctx, uint32_t nr) {
-    std::vector<uint64_t> h((size_t)nr * 16);
+    std::vector<uint64_t> h((size_t)nr * kKfProfWords);
     HIP_TRY(hipMemcpy(h.data(), ctx->asmb.kf_prof.p, h.size() * 8, hipMemcpyDeviceToHost));
     double ph[6] = {0, 0, 0, 0, 0, 0}, sz[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mx = 0, at = 0;
+    double fr[5] = {0, 0, 0, 0, 0};  // the front: 0 -> 16 -> 17 -> 1 -> 18 -> 19 (-> 2: the hits' sort)
+    double tkt = 0;                  // in front of stamp 0: the ticket atomic to the order entry (word 20)
     uint32_t n = 0;
     for (uint32_t r = 0; r < nr; r++) {
-        const uint64_t *p = &h[(size_t)r * 16];
+        const uint64_t *p = &h[(size_t)r * kKfProfWords];
         if (!p[6]) continue;  // empty, or left to key_asm_kernel
         n++;
         for (int k = 0; k < 6; k++) ph[k] += (double)(p[k + 1] - p[k]);
+        const uint64_t f[6] = {p[0], p[16], p[17], p[1], p[18], p[19]};
+        for (int k = 0; k < 5; k++) fr[k] += (double)(f[k + 1] - f[k]);
+        tkt += (double)p[20];
         mx = std::max(mx, (double)(p[6] - p[0]));
         at += (double)p[7];
         for (int k = 0; k < 8; k++) sz[k] += (double)p[8 + k];
     }
     std::vector<std::pair<double, uint32_t>> tot;  // (cycles, region)
     for (uint32_t r = 0; r < nr; r++)
-        if (h[(size_t)r * 16 + 6]) tot.push_back({(double)(h[(size_t)r * 16 + 6] - h[(size_t)r * 16]), r});
+        if (h[(size_t)r * kKfProfWords + 6]) tot.push_back({(double)(h[(size_t)r * kKfProfWords + 6] - h[(size_t)r * kKfProfWords]), r});
     std::sort(tot.begin(), tot.end());
     if (!tot.empty()) {
         auto pct = [&](double f) { return tot[std::min(tot.size() - 1, (size_t)(f * tot.size()))].first; };
         fprintf(stderr, "[kf prof] total ticks p50 %.0f p90 %.0f p99 %.0f max %.0f; slowest regions (ticks U rows chunks "
                         "corrections refs):", pct(0.5), pct(0.9), pct(0.99), tot.back().first);
         for (size_t i = tot.size(); i-- > 0 && i + 6 > tot.size();) {
-            const uint64_t *p = &h[(size_t)tot[i].second * 16];
+            const uint64_t *p = &h[(size_t)tot[i].second * kKfProfWords];
             fprintf(stderr, " [%.0f %llu %llu %llu %llu %llu]", tot[i].first, (unsigned long long)p[8],
                     (unsigned long long)p[12], (unsigned long long)p[13], (unsigned long long)p[11],
                     (unsigned long long)p[15]);
@@ -183,7 +194,7 @@ static int kf_prof_report(tfbs_ctx *ctx, uint32_t nr) {
     uint64_t t_lo = UINT64_MAX, t_hi = 0;
     double busy = 0;
     for (uint32_t r = 0; r < nr; r++) {
-        const uint64_t *p = &h[(size_t)r * 16];
+        const uint64_t *p = &h[(size_t)r * kKfProfWords];
         if (!p[6]) continue;
         t_lo = std::min(t_lo, p[0]);
         t_hi = std::max(t_hi, p[6]);
@@ -192,19 +203,19 @@ static int kf_prof_report(tfbs_ctx *ctx, uint32_t nr) {
     {  // per workgroup: its regions in start order -> gaps between them, late start, early end
         std::vector<std::pair<std::pair<uint64_t, uint64_t>, uint32_t>> ev;  // ((workgroup, start), region)
         for (uint32_t r = 0; r < nr; r++)
-            if (h[(size_t)r * 16 + 6]) ev.push_back({{h[(size_t)r * 16 + 14], h[(size_t)r * 16]}, r});
+            if (h[(size_t)r * kKfProfWords + 6]) ev.push_back({{h[(size_t)r * kKfProfWords + 14], h[(size_t)r * kKfProfWords]}, r});
         std::sort(ev.begin(), ev.end());
         double gap = 0, late = 0, early_end = 0;
         uint32_t n_gap = 0, n_groups = 0;
         for (size_t i = 0; i < ev.size(); i++) {
-            const uint64_t *p = &h[(size_t)ev[i].second * 16];
+            const uint64_t *p = &h[(size_t)ev[i].second * kKfProfWords];
             const bool first = i == 0 || ev[i - 1].first.first != ev[i].first.first;
             const bool last = i + 1 == ev.size() || ev[i + 1].first.first != ev[i].first.first;
             if (first) {
                 n_groups++;
                 late += (double)(p[0] - t_lo);
             } else {
-                gap += (double)(p[0] - h[(size_t)ev[i - 1].second * 16 + 6]);
+                gap += (double)(p[0] - h[(size_t)ev[i - 1].second * kKfProfWords + 6]);
                 n_gap++;
             }
             if (last) early_end += (double)(t_hi - p[6]);
@@ -216,12 +227,17 @@ static int kf_prof_report(tfbs_ctx *ctx, uint32_t nr) {
     }
     uint32_t early = 0;  // regions started in the first 10 us: the workgroups resident at the start
     for (uint32_t r = 0; r < nr; r++)
-        if (h[(size_t)r * 16 + 6] && h[(size_t)r * 16] < t_lo + 1000) early++;
+        if (h[(size_t)r * kKfProfWords + 6] && h[(size_t)r * kKfProfWords] < t_lo + 1000) early++;
     if (t_hi > t_lo)
         fprintf(stderr, "[kf prof] span %.1f us (first region start to last end, 100 MHz ticks), region-time %.1f us: "
                         "%.0f regions in flight on average; %u regions started in the first 10 us\n",
                 (t_hi - t_lo) / 100.0, busy / 100.0, busy / (double)(t_hi - t_lo), early);
     const double d = n ? n : 1;
+    fprintf(stderr,
+            "[kf prof] front ticks/region: region record + reference hit list (round 1) %.0f, descriptors + hitn + "
+            "first runs + meta (round 2) %.0f, hitn scan %.0f, runs staged %.0f, reference hits + barrier %.0f; in front of "
+            "a region, ticket atomic to order entry %.0f\n",
+            fr[0] / d, fr[1] / d, fr[2] / d, fr[3] / d, fr[4] / d, tkt / d);
     fprintf(stderr,
             "[kf prof] regions %u of %u ticks/region: descr+hitn %.0f refs %.0f dirty %.0f lists %.0f keys %.0f "
             "chunks %.0f (of which var-list atomics %.0f) (max total %.0f); per region: U %.1f entries %.1f dirty-refs %.1f corrections %.1f rows "

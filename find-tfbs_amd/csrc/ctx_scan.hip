@@ -48,6 +48,15 @@ int tfbs::build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t>
     ctx->lists.wl_n_haps = n_haps;
     for (int c = 0; c < 2; c++) ctx->lists.sh_entries[c] = ctx->lists.sh_listed[c][0] = ctx->lists.sh_listed[c][1] = 0;
     if (B) B->lists_counted = false;
+    int rc;
+    {  // key_fast_kernel's static records of the haplotypes and regions just put on the device
+        const uint32_t nr = B ? (uint32_t)B->regions.size() : 1u;
+        if ((rc = ctx->img.hap_reuse.ensure(std::max<uint32_t>(n_haps, 1))) ||
+            (rc = ctx->img.region_asm.ensure(std::max<uint32_t>(nr, 1))) ||
+            (rc = launch_region_asm(ctx->img.haps.p, n_haps, ctx->img.regions.p, nr, ctx->img.hap_reuse.p,
+                                    ctx->img.region_asm.p, ctx->stream)))
+            return rc;
+    }
     if (P.m_supers.empty()) return TFBS_OK;
     const auto t0 = std::chrono::steady_clock::now();
     uint32_t lmin[2] = {0, 0}, span[2] = {0, 0};  // per depth class: shortest and longest strand
@@ -56,7 +65,6 @@ int tfbs::build_lists(tfbs_ctx *ctx, uint32_t n_haps, const std::vector<uint8_t>
         l = l ? std::min(l, S.lmin) : S.lmin;
         span[S.nk > 2 ? 1 : 0] = std::max(span[S.nk > 2 ? 1 : 0], S.lmax);
     }
-    int rc;
     for (int c = 0; c < 2; c++)
         if (lmin[c] && (rc = ctx->lists.wl_off[c].ensure((size_t)n_haps + 1))) return rc;
     if ((rc = ctx->lists.wl_tmp.ensure(scan_tmp_words((size_t)n_haps + 1))) ||
@@ -444,6 +452,21 @@ int tfbs_ctx_share_entries(tfbs_ctx *ctx, int cls, uint32_t *entries, size_t cap
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipMemcpy(off.data(), ctx->lists.sh_off[cls].p, off.size() * 8, hipMemcpyDeviceToHost));
     for (size_t h = 0; h < n; h++) entries[h] = (uint32_t)(off[h + 1] - off[h]);
+    return TFBS_OK;
+}
+
+int tfbs_ctx_region_asm(tfbs_ctx *ctx, uint32_t *region_asm, size_t cap_regions, uint32_t *hap_reuse, size_t cap_haps,
+                        size_t *n_regions, size_t *n_haps) {
+    if (!ctx || !n_regions || !n_haps || (cap_regions && !region_asm) || (cap_haps && !hap_reuse))
+        return tfbs::fail(TFBS_E_ARG, "bad argument");
+    *n_regions = ctx->img.n_regions;
+    *n_haps = ctx->lists.wl_n_haps;
+    if (!cap_regions && !cap_haps) return TFBS_OK;
+    if (*n_regions > cap_regions || *n_haps > cap_haps) return tfbs::fail(TFBS_E_ARG, "region asm: the arrays are too small");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (*n_regions) HIP_TRY(hipMemcpy(region_asm, ctx->img.region_asm.p, *n_regions * 16, hipMemcpyDeviceToHost));
+    if (*n_haps) HIP_TRY(hipMemcpy(hap_reuse, ctx->img.hap_reuse.p, *n_haps * 4, hipMemcpyDeviceToHost));
     return TFBS_OK;
 }
 

@@ -78,6 +78,12 @@ __device__ __forceinline__ uint4 make_ref(const AsmArgs &A, const DevRegion &rg,
     return make_uint4(key0, i, L | (dk << 16), ref_overlaps(A, rg, L, i, 0, min(rg.n_inner, 32u)));
 }
 
+// make_ref from the three meta fields already loaded (key_fast_kernel loads them a round early).
+__device__ __forceinline__ uint4 make_ref_loaded(const AsmArgs &A, const DevRegion &rg, uint32_t L, uint32_t depth,
+                                                 uint32_t slot, uint32_t i) {
+    return make_uint4(slot * rg.n_inner, i, L | ((depth - 1) << 16), ref_overlaps(A, rg, L, i, 0, min(rg.n_inner, 32u)));
+}
+
 // Every own hit (local haplotype l < U, key) of region r: the wave lists of the
 // region's haplotype groups (group g's are lists g * kMBlockWaves .. + 7, scan.hpp; one
 // wave per list), then the region's spill records.
@@ -499,6 +505,10 @@ __device__ __forceinline__ void st_global(uint32_t *p, uint32_t v) {
     *(__attribute__((address_space(1))) uint32_t *)p = v;
 }
 
+// The loads of one round have arrived (one wait per round) and stay where they were issued:
+// without a use here the compiler sinks a load into the branch that needs it.
+__device__ __forceinline__ void arrived(uint32_t &x) { asm volatile("" : "+v"(x)); }
+
 // Appends v from the wave's lanes with want set, in lane order (one LDS atomic
 // per wave), with put(slot, v); *n counts every attempt (> cap: overflow).
 template <class Put>
@@ -558,16 +568,44 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     __shared__ uint32_t s_rkey[kFRows], s_rr[kFRows];  // per row of a chunk: its key; R(key), then its varying slot
     __shared__ uint32_t s_loff[kFLists + 1], s_lidx[kFLists];
     __shared__ uint32_t s_w[kFWaves];
-    __shared__ uint32_t s_ncor, s_nref, s_run0, s_run1, s_nvar, s_arena, s_ndirty, s_lmax;
+    __shared__ uint32_t s_ncor, s_nref, s_nvar, s_arena, s_ndirty;
     __shared__ unsigned long long s_vbase, s_obase;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    auto process = [&](const uint32_t r, const uint32_t by_ticket) {  // one region (every exit is workgroup-uniform)
-    // TFBS_KF_PROF: phase times 0-7 (wall_clock64: 100 MHz), then sizes (U, entries, dirty reference hits, rows, chunks)
+    auto process = [&](const uint32_t r, const uint32_t by_ticket, const uint64_t t_ticket) {  // one region (every exit is workgroup-uniform)
+    // TFBS_KF_PROF: phase times 0-7 (wall_clock64: 100 MHz), then sizes (U, entries, dirty reference hits, rows,
+    // chunks), then the first phase's own times 16-19 and, 20, the ticks from the ticket atomic
+    // to the order entry in front of the region (kKfProfWords per region)
     auto stamp = [&](uint32_t k, uint64_t v) {
-        if (A.prof && tid == 0) A.prof[16 * (size_t)r + k] = v;
+        if (A.prof && tid == 0) A.prof[kKfProfWords * (size_t)r + k] = v;
     };
     stamp(0, wall_clock64());
-    const DevRegion rg = A.regions[r];
+    stamp(20, t_ticket);
+    // Round 1: every address from r alone, all issued before the first wait -- the region, its
+    // static record (run0, nruns, lmax: launch_region_asm), its reference hit count and the
+    // thread's reference hit (the buffer always holds it; used only below the count), its spill bucket
+    // (spill_off[r] whatever the count: used only where the count is not 0)
+    // (the front's addresses from a thread index the compiler takes as new per region: built from
+    // tid itself they are hoisted out of the region loop, a register pair each for the kernel's whole run)
+    uint32_t ft = tid;
+    arrived(ft);
+    // (no branch around a load -- a branch ends a round with a wait of its own --: a list this
+    // launch does not have is read at `none`, the region's own record, and its value not used;
+    // every wave reads the 64 reference hits, lane by lane)
+    const uint32_t *const none = reinterpret_cast<const uint32_t *>(A.regions + r);
+    auto have = [&](bool c, const auto *p) { return c ? p : reinterpret_cast<decltype(p)>(none); };
+    const bool spills = A.spill_count != nullptr;
+    uint32_t n_rc = ld_global(have(A.mfma, A.ref_count + r));
+    const uint2 rh = ld_global(have(A.mfma, reinterpret_cast<const uint2 *>(A.ref_hits) + (size_t)r * kRefPerRegion + (ft & 63u)));
+    uint32_t rh_g = rh.x, rh_i = rh.y;
+    uint32_t sp_n = ld_global(have(spills, A.spill_count));
+    uint32_t sp_c = ld_global(have(spills, A.spill_cnt + r));
+    uint32_t sp_o = ld_global(have(spills, A.spill_off + r));
+    DevRegion rg = A.regions[r];
+    uint4 ra = A.region_asm[r];
+    arrived(n_rc), arrived(rh_g), arrived(rh_i), arrived(sp_n), arrived(sp_c), arrived(sp_o);
+    arrived(rg.hap_count), arrived(ra.x);
+    if (!spills) sp_n = 0;
+    stamp(16, wall_clock64());
     const uint32_t U = rg.hap_count, n_inner = rg.n_inner, K = A.n_slots * n_inner;
     const uint64_t ko = (uint64_t)rg.inner_off * A.n_slots;
     // tfbs_ctx_assembly_trace: the region's path word, stored once where the region leaves
@@ -593,70 +631,70 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     if (U > (kFMaxU < A.fast_max_u ? kFMaxU : A.fast_max_u) || K > 32 * kFKeyWords || n_inner > 32) return give_up(0);
     const uint32_t hb = rg.hap_begin;
     const bool refs_on = A.mfma && rg.ref_hap != UINT32_MAX;
-    if (tid == 0) {
-        s_ncor = s_nref = s_run1 = s_ndirty = s_lmax = 0;
-        s_run0 = kFNone;
-    }
-    __syncthreads();
-    // descriptors: which haplotypes reuse the reference's windows, and their runs
-    constexpr uint32_t kPer = kFMaxU / kFBlock;
-    uint32_t roff[kPer], rn[kPer], lmax = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < kPer; q++) {
-        const uint32_t l = tid + q * kFBlock;
-        roff[q] = kFNone;
-        rn[q] = 0;
-        if (l < U) {
-            const DevHap &h = A.haps[hb + l];
-            lmax = max(lmax, h.len);
-            if (h.flags & HAP_DEDUP) {  // its runs in the reference's columns
-                roff[q] = h.rrun_off;
-                rn[q] = h.n_rruns;
-                atomicMin(&s_run0, h.rrun_off);
-                atomicMax(&s_run1, h.rrun_off + h.n_rruns);
-            }
-        }
-    }
+    // (the same in every lane: kept in scalar registers)
+    const uint32_t run0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ra.x);
+    const uint32_t nruns = (uint32_t)__builtin_amdgcn_readfirstlane((int)ra.y);
+    const uint32_t lmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)ra.z);
+    if (tid == 0) s_ncor = s_nref = s_ndirty = 0;  // (read behind block_excl_scan's barriers)
     // own hits: the wave lists of the region's haplotype groups (one hitn load per
     // thread), their entries read flat over the workgroup below
     const uint32_t g_lo = hb / A.hpb, g_hi = (hb + U - 1) / A.hpb;
     const uint32_t nl = A.mfma ? (g_hi + 1 - g_lo) * kMBlockWaves : 0u;
     // list t of the region's: group g's wave lists are g * kMBlockWaves .. + 7 (scan.hpp)
     auto list_idx = [&](uint32_t t) -> uint32_t { return g_lo * kMBlockWaves + t; };
-    uint32_t lcnt = 0, lidx = 0;  // the region's entries (an upper bound of its hits: groups are shared)
-    for (uint32_t t = tid; t < nl; t += kFBlock) {
-        const uint32_t i = list_idx(t);
-        if (t == tid) lidx = i;
-        lcnt += A.hitn[i];
+    const bool lists_staged = nl <= kFLists;  // one list per thread: its offset and index kept for the list pass
+    if (!lists_staged) pw |= TFBS_PATH_LISTS_SLICED;
+    if (nruns >= 65536) return give_up(2);
+    if (nruns > kFRuns) pw |= TFBS_PATH_RUNS_L2;
+    // Round 2, all issued before the next wait: the haplotypes' reuse descriptors
+    // (hap_reuse: what s_hap holds), the hit lists' lengths, the diff runs' first
+    // sweep, the meta fields of the thread's reference hit
+    constexpr uint32_t kHapQ = kFHapLds / kFBlock;
+    // (again no branch around a load: a thread past a list's end reads the list's last entry,
+    // a list that is not there is read at `none`)
+    uint32_t hx[kHapQ];
+#pragma unroll
+    for (uint32_t q = 0; q < kHapQ; q++) hx[q] = ld_global(A.hap_reuse + hb + min(ft + q * kFBlock, U - 1));  // (U >= 1 here)
+    // the region's entries (an upper bound of its hits: groups are shared)
+    const uint32_t lidx = list_idx(min(ft, nl ? nl - 1 : 0u));
+    uint32_t lcnt = ld_global(have(nl != 0, A.hitn + lidx));
+    // the runs in LDS when they fit, else read from global memory (L2)
+    const bool runs_lds = nruns <= kFRuns;
+    const uint2 *const druns = reinterpret_cast<const uint2 *>(A.druns) + (nruns ? run0 : 0u);
+    const uint2 run_first = ld_global(have(runs_lds && nruns != 0, druns + min(ft, nruns ? nruns - 1 : 0u)));
+    uint32_t run_a = run_first.x, run_b = run_first.y;
+    const uint32_t n_list = refs_on ? min(n_rc, kRefPerRegion) : 0u;
+    const uint32_t g_ref = ft < n_list ? rh_g : 0u, sn = g_ref & 63u;
+    const uint32_t *const meta = have(refs_on, reinterpret_cast<const uint32_t *>(A.mmeta) + (size_t)(g_ref >> 6) * kGMetaInts);
+    uint32_t m_len = ld_global(meta + (refs_on ? kGStrandInts * sn + kGLen : 0u));
+    uint32_t m_depth = ld_global(meta + (refs_on ? (uint32_t)kGDepth : 0u));
+    uint32_t m_slot = ld_global(meta + (refs_on ? kGStrandInts * sn + kGSlot : 0u));
+#pragma unroll
+    for (uint32_t q = 0; q < kHapQ; q++) arrived(hx[q]);
+    arrived(lcnt), arrived(run_a), arrived(run_b), arrived(m_len), arrived(m_depth), arrived(m_slot);
+#pragma unroll
+    for (uint32_t q = 0; q < kHapQ; q++)
+        if (ft + q * kFBlock >= U) hx[q] = kFNone;
+    if (ft >= nl) lcnt = 0;
+    for (uint32_t t = ft + kFBlock; t < nl; t += kFBlock) lcnt += ld_global(A.hitn + list_idx(t));  // (past kFBlock lists)
+    stamp(17, wall_clock64());
+#pragma unroll
+    for (uint32_t q = 0; q < kHapQ; q++) {
+        const uint32_t l = tid + q * kFBlock;
+        if (l < U) s_hap[l] = hx[q];
     }
     uint32_t n_ent = 0;
-    const uint32_t loff = block_excl_scan<kFWaves>(lcnt, s_w, n_ent);  // (barriers: s_run0 / s_run1 are final)
-    if (tid == 0 && rg.ref_hap != UINT32_MAX) lmax = max(lmax, A.haps[rg.ref_hap].len);  // (R's haplotype)
-    if (lmax) atomicMax(&s_lmax, lmax);
-    const bool lists_staged = nl <= kFLists;  // one list per thread: its offset and index kept for the list pass
+    const uint32_t loff = block_excl_scan<kFWaves>(lcnt, s_w, n_ent);
     if (lists_staged && tid < nl) {
         s_lidx[tid] = lidx;
         s_loff[tid] = loff;
     }
     if (lists_staged && tid == 0) s_loff[nl] = n_ent;
     stamp(1, wall_clock64());
-    const uint32_t run0 = s_run0, nruns = s_run0 == kFNone ? 0u : s_run1 - s_run0;
-    if (!lists_staged) pw |= TFBS_PATH_LISTS_SLICED;
-    if (nruns >= 65536) return give_up(2);
-    if (nruns > kFRuns) pw |= TFBS_PATH_RUNS_L2;
-#pragma unroll
-    for (uint32_t q = 0; q < kFHapLds / kFBlock; q++) {
-        const uint32_t l = tid + q * kFBlock;
-        if (l < U) s_hap[l] = roff[q] == kFNone ? kFNone : (roff[q] - run0) | (rn[q] << 16);
-    }
     auto hap_info = [&](uint32_t l) -> uint32_t {  // s_hap's entry of any haplotype
         if (l < kFHapLds) return s_hap[l];
-        const DevHap &h = A.haps[hb + l];
-        return (h.flags & HAP_DEDUP) ? (h.rrun_off - run0) | (h.n_rruns << 16) : kFNone;
+        return ld_global(A.hap_reuse + hb + l);
     };
-    // the runs in LDS when they fit, else read from global memory (L2)
-    const bool runs_lds = nruns <= kFRuns;
-    const uint2 *const druns = reinterpret_cast<const uint2 *>(A.druns) + (nruns ? run0 : 0u);
     auto run_at = [&](auto typed, uint32_t k) -> uint2 {  // run k of the region's, by placement
         if constexpr (decltype(typed)::value) {
             return s_run[k];
@@ -665,17 +703,17 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             return ld_global(druns + k);
         }
     };
-    if (runs_lds)
-        for (uint32_t k = tid; k < nruns; k += kFBlock)
-            s_run[k] = make_uint2(A.druns[2 * (run0 + k)], A.druns[2 * (run0 + k) + 1]);
+    if (runs_lds) {
+        if (tid < nruns) s_run[tid] = make_uint2(run_a, run_b);
+        for (uint32_t k = tid + kFBlock; k < nruns; k += kFBlock) s_run[k] = ld_global(druns + k);
+    }
+    stamp(18, wall_clock64());
     // reference hits: the region's list, then its spill records of kind 1
-    const uint2 sp = spill_range(A, r);
+    const uint2 sp = sp_n && sp_c ? make_uint2(sp_o, sp_o + sp_c) : make_uint2(0, 0);  // (spill_range)
     if (refs_on) {
-        const uint32_t n = min(A.ref_count[r], kRefPerRegion);
-        if (tid < n) {
-            const size_t o = 2 * ((size_t)r * kRefPerRegion + tid);
+        if (tid < n_list) {
             const uint32_t at = atomicAdd(&s_nref, 1u);
-            if (at < kFRefs) s_ref[at] = make_ref(A, rg, A.ref_hits[o], A.ref_hits[o + 1]);
+            if (at < kFRefs) s_ref[at] = make_ref_loaded(A, rg, m_len, m_depth, m_slot, rh_i);
         }
         for (uint32_t e = sp.x + tid; e < sp.y; e += kFBlock) {
             const uint32_t *q = A.spill_sorted + 3 * (size_t)e;
@@ -687,6 +725,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     }
     __syncthreads();
     const uint32_t nref = s_nref;
+    stamp(19, wall_clock64());
     if (nref > kFRefs) return give_up(3);
     // D: per HAP_DEDUP haplotype the reference hits in its dirty windows (a run
     // [a, b] meets the columns [w, w + L - 1] of window w).  Up to 64 Ki (haplotype,
@@ -989,7 +1028,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     // 4 x length; the -1 corrections never take a count below 0 (a haplotype's
     // dirty reference hits on a key are some of its base R), so a packed pair
     // never borrows or carries
-    const bool half = 4 * (s_lmax + 64) < 65536 && A.cor_lds != 0;
+    const bool half = 4 * (lmax + 64) < 65536 && A.cor_lds != 0;
     uint32_t rows_per = min((half ? 2 : 1) * kFCnt / U, kFRows);
     uint16_t *const cnt16 = reinterpret_cast<uint16_t *>(s_cnt);
     bool h16 = half, cnt_arena = false;
@@ -1143,16 +1182,22 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     // regions [first, first + count) in A.order's order (most haplotypes first): with
     // A.persist a grid of a few workgroups per CU takes them -- its first region by
     // workgroup index, the next ones from the counter A.next[which] (gridDim.x + ticket),
-    // the ticket for the next region taken as this one starts, so that its latency hides
-    // behind the region's first loads --, else one per workgroup.  A grid with one
+    // the ticket for the next region taken as this one starts (the order entry's load behind it
+    // waits for it: TFBS_KF_PROF's word 20) --, else one per workgroup.  A grid with one
     // workgroup per region takes no ticket (1 000 tickets at once cost microseconds).
     __shared__ uint32_t s_tk;
     const bool tickets = A.persist && gridDim.x < count;
     uint32_t i = blockIdx.x;
     while (i < count) {
         uint32_t tk = 0;
+        uint64_t t_ticket = A.prof ? wall_clock64() : 0;
         if (tickets && tid == 0) tk = gridDim.x + atomicAdd(A.next + which, 1u);
-        process(A.order ? A.order[first + i] : first + i, i == blockIdx.x ? 0u : (uint32_t)TFBS_PATH_TICKET);
+        const uint32_t r = A.order ? A.order[first + i] : first + i;
+        if (A.prof) {
+            asm volatile("" ::"v"(r));  // (the entry has arrived)
+            t_ticket = wall_clock64() - t_ticket;
+        }
+        process(r, i == blockIdx.x ? 0u : (uint32_t)TFBS_PATH_TICKET, t_ticket);
         if (!tickets) break;
         if (tid == 0) s_tk = tk;
         __syncthreads();

@@ -17,6 +17,10 @@ struct AsmArgs {
     const DevHap *haps;
     const uint32_t *druns;  // HAP_DEDUP haplotypes' diff runs (tfbs_internal.hpp)
     const DevRegion *regions;
+    // key_fast_kernel's static records of the uploaded batch (launch_region_asm, scan.hpp):
+    // per haplotype its reuse descriptor, per region (run0, nruns, lmax, spare)
+    const uint32_t *hap_reuse;
+    const uint4 *region_asm;
     const int32_t *inner;
     const int32_t *mmeta;       // matrix-core tiles' rescoring fields (strand length, slot, depth)
     const uint8_t *slot_mfma;   // per slot: 1 = matrix-core hits, 0 = the LUT/generic kernels' dense counts
@@ -76,13 +80,15 @@ struct AsmArgs {
     // else one region per workgroup
     uint32_t persist;
     uint32_t *next;
-    uint64_t *prof;  // debug (TFBS_KF_PROF): key_fast_kernel's phase clocks and sizes, 16 per region, or null
+    uint64_t *prof;  // debug (TFBS_KF_PROF): key_fast_kernel's phase clocks and sizes, kKfProfWords per region, or null
     // tfbs_ctx_assembly_trace: one word per region (TFBS_PATH_* of tfbs_amd.h), written once by
     // thread 0 of the workgroup that takes the region (key_asm_kernel's list pass adds its
     // bits to key_fast_kernel's), or null
     uint32_t *path;
     uint32_t grid_cap;  // TFBS_KF_GRID: at most this many persistent workgroups per shape (0: what fits)
 };
+
+constexpr uint32_t kKfProfWords = 24;  // AsmArgs::prof: 0-7 phase clocks, 8-15 sizes, 16-19 the first phase's clocks, 20 the ticket's wait
 
 // The words of the assembly's counter block (tfbs_ctx's asm_ctr: zeroed by the scan or by one
 // memset, its first kAsmCtrWords copied back once per assembly).  The kernels take pointers to

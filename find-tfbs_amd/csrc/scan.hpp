@@ -238,6 +238,14 @@ int build_window_lists(const DevHap *haps, uint32_t n_haps, const uint32_t *drun
                        const uint32_t *words = nullptr, const ClassTab *tab = nullptr,
                        int (*ensure_share)(void *ctx, int c, uint64_t n, uint2 **p) = nullptr,
                        uint64_t shared[2] = nullptr, uint64_t listed[2][2] = nullptr);
+// The key assembly's static records of an uploaded batch (key_kernels.hip, key_fast_kernel's
+// front reads them instead of the DevHaps): hap_reuse[h], one word per haplotype -- UINT32_MAX
+// unless HAP_DEDUP, else (rrun_off - its region's run0) | n_rruns << 16 --, and region_asm[r] =
+// (run0: the lowest rrun_off of the region's HAP_DEDUP haplotypes, UINT32_MAX if none; nruns:
+// the highest rrun_off + n_rruns minus run0, 0 if none; lmax: the longest of its hap_count
+// haplotypes and of its ref_hap; 0).  hap_reuse holds max(n_haps, 1) words.
+int launch_region_asm(const DevHap *haps, uint32_t n_haps, const DevRegion *regions, uint32_t n_regions,
+                      uint32_t *hap_reuse, uint4 *region_asm, hipStream_t stream);
 size_t mfma_lds_fixed();  // LDS bytes the MFMA kernel needs besides the image and words
 
 }  // namespace tfbs

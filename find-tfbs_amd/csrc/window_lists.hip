@@ -294,6 +294,39 @@ __global__ __launch_bounds__(256) void hd_kernel(const DevHap *__restrict__ haps
     }
 }
 
+// The key assembly's static records (launch_region_asm, scan.hpp): a wave per region,
+// one pass for the region's span of runs and its longest haplotype, one for the
+// haplotypes' descriptors against that span's start.
+__global__ __launch_bounds__(256) void region_asm_kernel(const DevHap *__restrict__ haps,
+                                                          const DevRegion *__restrict__ regions, uint32_t n_regions,
+                                                          uint32_t *__restrict__ hap_reuse, uint4 *__restrict__ region_asm) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6); r < n_regions; r += gridDim.x * 4) {
+        const DevRegion rg = regions[r];
+        uint32_t lo = UINT32_MAX, hi = 0, lmax = 0;
+        for (uint32_t l = lane; l < rg.hap_count; l += 64) {
+            const DevHap &h = haps[rg.hap_begin + l];
+            lmax = max(lmax, h.len);
+            if (h.flags & HAP_DEDUP) {  // its runs in the reference's columns
+                lo = min(lo, h.rrun_off);
+                hi = max(hi, h.rrun_off + h.n_rruns);
+            }
+        }
+        if (lane == 0 && rg.ref_hap != UINT32_MAX) lmax = max(lmax, haps[rg.ref_hap].len);  // (R's haplotype)
+#pragma unroll
+        for (int o = 32; o; o >>= 1) {
+            lo = min(lo, (uint32_t)__shfl_xor((int)lo, o));
+            hi = max(hi, (uint32_t)__shfl_xor((int)hi, o));
+            lmax = max(lmax, (uint32_t)__shfl_xor((int)lmax, o));
+        }
+        for (uint32_t l = lane; l < rg.hap_count; l += 64) {
+            const DevHap &h = haps[rg.hap_begin + l];
+            hap_reuse[rg.hap_begin + l] = (h.flags & HAP_DEDUP) ? (h.rrun_off - lo) | (h.n_rruns << 16) : UINT32_MAX;
+        }
+        if (lane == 0) region_asm[r] = make_uint4(lo, lo == UINT32_MAX ? 0u : hi - lo, lmax, 0u);
+    }
+}
+
 // In-place exclusive scan of u64 values, 4096 per workgroup; sums[b] = tile b's total.
 constexpr uint32_t kScanThreads = 1024, kScanTile = 4 * kScanThreads;
 __global__ __launch_bounds__(kScanThreads) void scan_tile_kernel(uint64_t *__restrict__ x, uint64_t n,
@@ -343,6 +376,19 @@ int exclusive_scan(uint64_t *x, uint64_t n, uint64_t *tmp, hipStream_t stream) {
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("scan kernels: ") + hipGetErrorString(e));
+    return TFBS_OK;
+}
+
+int launch_region_asm(const DevHap *haps, uint32_t n_haps, const DevRegion *regions, uint32_t n_regions,
+                      uint32_t *hap_reuse, uint4 *region_asm, hipStream_t stream) {
+    // (a haplotype of no region's hap_count -- a helper reference -- reuses nothing)
+    hipError_t e = hipMemsetAsync(hap_reuse, 0xFF, (size_t)std::max<uint32_t>(n_haps, 1) * 4, stream);
+    if (e == hipSuccess && n_regions) {
+        hipLaunchKernelGGL(region_asm_kernel, dim3(std::min<uint32_t>((n_regions + 3) / 4, 2048)), dim3(256), 0, stream, haps,
+                           regions, n_regions, hap_reuse, region_asm);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(TFBS_E_HIP, std::string("region_asm_kernel: ") + hipGetErrorString(e));
     return TFBS_OK;
 }
 

@@ -522,6 +522,15 @@ enum {
 #define TFBS_PATH_WHY(word) (((word) >> TFBS_PATH_WHY_SHIFT) & 7u)
 int tfbs_ctx_assembly_trace(tfbs_ctx *ctx, int on);
 int tfbs_batch_assembly_paths(tfbs_ctx *ctx, const tfbs_batch *b, uint32_t *mask, uint32_t n);
+/* The key assembly's static records of what was last uploaded (debug, read-only; made on the
+ * device at every upload, the one-haplotype upload of tfbs_matches included).  region_asm: four
+ * words per region -- run0, the lowest run offset (reference columns) of its haplotypes that
+ * reuse the reference's hits, UINT32_MAX if none; nruns, the highest such offset + count minus
+ * run0, 0 if none; lmax, the longest of its distinct haplotypes and of its reference haplotype;
+ * 0.  hap_reuse: one word per uploaded haplotype -- UINT32_MAX unless it reuses, else (its run
+ * offset - run0) | its runs << 16.  *n_regions / *n_haps get the sizes; both caps 0: only those. */
+int tfbs_ctx_region_asm(tfbs_ctx *ctx, uint32_t *region_asm, size_t cap_regions, uint32_t *hap_reuse, size_t cap_haps,
+                        size_t *n_regions, size_t *n_haps);
 /* The figures of the last checked assembly (any ctx, trace on or off): out[0] regions left to
  * key_asm_kernel, out[1] arena words asked for, out[2] spill records, out[3] / out[4] 1 if it
  * launched the wide spill bucketing kernels / the leftover pass (a lean assembly leaves out
