@@ -244,6 +244,18 @@ static int kf_prof_report(tfbs_ctx *ctx, uint32_t nr) {
             "%.1f chunks %.2f in-LDS %.2f refs %.1f\n",
             n, nr, ph[0] / d, ph[1] / d, ph[2] / d, ph[3] / d, ph[4] / d, ph[5] / d, at / d, mx, sz[0] / d, sz[1] / d,
             sz[2] / d, sz[3] / d, sz[4] / d, sz[5] / d, sz[6] / d, sz[7] / d);
+    double fine[kKfProfFineN] = {}, fine_sum = 0;  // (a kernel built with TFBS_KF_FINE: thread 0's own times)
+    for (uint32_t r = 0; r < nr; r++) {
+        const uint64_t *p = &h[(size_t)r * kKfProfWords];
+        if (!p[6]) continue;
+        for (uint32_t k = 0; k < kKfProfFineN; k++) fine[k] += (double)p[kKfProfFine + k], fine_sum += (double)p[kKfProfFine + k];
+    }
+    if (fine_sum != 0)
+        fprintf(stderr,
+                "[kf prof] fine ticks/region: dirty: pair loop %.0f listing %.0f scan %.0f; chunks: remap %.0f row keys + R "
+                "%.0f base fill %.0f corrections %.0f classification %.0f var atomics %.0f varying rows %.0f\n",
+                fine[0] / d, fine[1] / d, fine[2] / d, fine[3] / d, fine[4] / d, fine[5] / d, fine[6] / d, fine[7] / d,
+                fine[8] / d, fine[9] / d);
     return TFBS_OK;
 }
 

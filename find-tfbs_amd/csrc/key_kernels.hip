@@ -549,8 +549,15 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_w, u
     return pre + x - v;
 }
 
+#ifdef TFBS_KF_FINE
+#define KF_FINE(...) __VA_ARGS__
+#else
+#define KF_FINE(...)
+#endif
+// (the common shape: four workgroups per CU by its LDS, so at least four waves per SIMD -- the
+// register allocator's bound, 128 VGPRs; without it the region body takes 150)
 #ifndef TFBS_KF_WAVES
-#define TFBS_KF_WAVES 1
+#define TFBS_KF_WAVES 4
 #endif
 template <class C>
 __global__ __launch_bounds__(C::kBlock) __attribute__((amdgpu_waves_per_eu(C::kBlock == 1024 ? 1 : TFBS_KF_WAVES)))
@@ -569,7 +576,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     __shared__ uint32_t s_loff[kFLists + 1], s_lidx[kFLists];
     __shared__ uint32_t s_w[kFWaves];
     __shared__ uint32_t s_ncor, s_nref, s_nvar, s_arena, s_ndirty;
-    __shared__ unsigned long long s_vbase, s_obase;
+    __shared__ unsigned long long s_vb[2];  // a chunk's share of the compact lists: first key, first count
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     auto process = [&](const uint32_t r, const uint32_t by_ticket, const uint64_t t_ticket) {  // one region (every exit is workgroup-uniform)
     // TFBS_KF_PROF: phase times 0-7 (wall_clock64: 100 MHz), then sizes (U, entries, dirty reference hits, rows,
@@ -580,6 +587,15 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     };
     stamp(0, wall_clock64());
     stamp(20, t_ticket);
+    // TFBS_KF_FINE (a build of its own: the product kernel's registers stay): thread 0's time in the
+    // parts of the dirty phase and of the chunks, words kKfProfFine.. of the region's record
+    KF_FINE(uint64_t tf[kKfProfFineN] = {}; uint64_t tf_last = 0;
+            auto fine_start = [&]() { tf_last = wall_clock64(); };
+            auto fine = [&](uint32_t k) {
+                const uint64_t t = wall_clock64();
+                tf[k] += t - tf_last;
+                tf_last = t;
+            };)
     // Round 1: every address from r alone, all issued before the first wait -- the region, its
     // static record (run0, nruns, lmax: launch_region_asm), its reference hit count and the
     // thread's reference hit (the buffer always holds it; used only below the count), its spill bucket
@@ -729,10 +745,8 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     if (nref > kFRefs) return give_up(3);
     // D: per HAP_DEDUP haplotype the reference hits in its dirty windows (a run
     // [a, b] meets the columns [w, w + L - 1] of window w).  Up to 64 Ki (haplotype,
-    // reference hit) pairs are tested pairwise, a lane per haplotype: the lane reads
-    // each of its runs (<= 16) once and tries it on 64 reference hits at a time --
-    // s_ref[p] is the same word for the whole wave, a broadcast read with no chain
-    // behind it -- and keeps the dirty hits as a bit mask; past that the hits are sorted
+    // reference hit) pairs are tested pairwise, a lane per haplotype and a lane mask per
+    // hit (dirty_hits below); past that the hits are sorted
     // by window and each haplotype walks its runs over them (a hit in [a - 31, b] of
     // run [a, b] tested once: runs ascend, the cursor only moves forward).
     const bool pairwise = (uint64_t)U * nref <= 65536;
@@ -752,38 +766,86 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         __syncthreads();
     }
     stamp(2, wall_clock64());
-    // f(l, p0, m) by every lane of the wave together: bit p of m says that reference hit
-    // p0 + p is dirty for haplotype l (m = 0 for a lane past U or without reuse)
-    auto dirty_masks = [&](auto typed, auto &&f) {
-        for (uint32_t l0 = wave * 64; l0 < U; l0 += kFBlock) {
+    KF_FINE(fine_start();)
+    // The pairwise test, hit-major: a wave takes 64 haplotypes, a lane each, and a slice of at most
+    // 64 of its share [h0, h1) of the reference hits.  Lane p of the slice holds hit p's record; a
+    // group of kDGroup hits has its first and last column in scalar registers (v_readlane: no LDS
+    // read), each lane reads its runs once per group (the run loop is the wave's: a lane past its
+    // own tries a run that meets nothing), and a (run, hit) test is two vector compares whose lane
+    // mask is OR-ed into the hit's 64-bit scalar mask.  Hit p's mask then sits in lane p; the
+    // slice's corrections are counted in scalars (dirty haplotypes x inner ranges per hit), take one
+    // slot reservation, and are listed hit by hit: every dirty lane stores its entry at the
+    // base + the hits before + its rank among the dirty lanes.  put(slot, entry); returns the
+    // wave's count (the same in every lane).
+    // A region whose haplotype blocks fill at most half of the workgroup's waves gives each block to
+    // several waves, which take shares of the hits.
+    constexpr uint32_t kDGroup = 8;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);
+    const uint32_t nblk = (U + 63) / 64;
+    const uint32_t shares = 2 * nblk <= kFWaves ? kFWaves / nblk : 1u;
+    auto dirty_hits = [&](auto typed, uint32_t *ctr, auto &&put) -> uint32_t {
+        uint32_t total = 0;
+        const uint32_t share = shares > 1 ? wv / nblk : 0u;
+        if (share >= shares) return 0;  // (a wave left over: kFWaves is no multiple of the blocks)
+        const uint32_t per = (nref + shares - 1) / shares;
+        const uint32_t h0 = min(share * per, nref), h1 = min(h0 + per, nref);
+        for (uint32_t l0 = 64 * (shares > 1 ? wv % nblk : wv); l0 < U; l0 += shares > 1 ? 64 * nblk : kFBlock) {
             const uint32_t l = l0 + lane;
             const uint32_t x = l < U ? hap_info(l) : kFNone;
-            const uint32_t k0 = x == kFNone ? 0u : x & 0xFFFFu, k1 = x == kFNone ? 0u : k0 + (x >> 16);
-            for (uint32_t p0 = 0; p0 < nref; p0 += 64) {
-                const uint32_t np = min(64u, nref - p0);
-                // lane p holds hit p0 + p's first and last column; the walk below reads them
-                // lane by lane into scalars (v_readlane: no LDS read, nothing to wait for).
-                // The run loop is the wave's: it goes on while any lane has a run left, a lane
-                // past its own tries a run that meets nothing, so every lane stays switched on
-                uint32_t rw = 0, re = 0;
+            const uint32_t k0 = x == kFNone ? 0u : x & 0xFFFFu, nk = x == kFNone ? 0u : x >> 16;
+            for (uint32_t p0 = h0; p0 < h1; p0 += 64) {
+                const uint32_t np = min(64u, h1 - p0);
+                // (a lane past the slice: a hit no run meets)
+                uint32_t rw = 0xFFFFFFFFu, re = 0, rx = 0, rb = 0;
                 if (lane < np) {
                     const uint4 q = s_ref[p0 + lane];
-                    rw = q.y;
-                    re = q.y + (q.z & 0xFFFFu) - 1;
+                    rw = q.y, re = q.y + (q.z & 0xFFFFu) - 1, rx = q.x, rb = q.w;
                 }
-                uint64_t m = 0;
-                for (uint32_t i = 0; __ballot(i < k1 - k0) != 0; i++) {
-                    uint2 ab = make_uint2(0xFFFFFFFFu, 0u);
-                    if (i < k1 - k0) ab = run_at(typed, k0 + i);
-                    for (uint32_t p = 0; p < np; p++) {  // (run_meets: a <= w + L - 1 and b >= w)
-                        const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)rw, (int)p);
-                        const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)re, (int)p);
-                        if (ab.x <= e && ab.y >= w) m |= 1ull << p;
+                uint32_t mlo = 0, mhi = 0, tot = 0;
+                for (uint32_t g0 = 0; g0 < np; g0 += kDGroup) {
+                    uint32_t w[kDGroup], e[kDGroup];
+                    uint64_t mk[kDGroup];
+#pragma unroll
+                    for (uint32_t g = 0; g < kDGroup; g++) {
+                        w[g] = (uint32_t)__builtin_amdgcn_readlane((int)rw, (int)(g0 + g));
+                        e[g] = (uint32_t)__builtin_amdgcn_readlane((int)re, (int)(g0 + g));
+                        mk[g] = 0;
+                    }
+                    for (uint32_t i = 0; __ballot(i < nk) != 0; i++) {
+                        uint2 ab = make_uint2(0xFFFFFFFFu, 0u);
+                        if (i < nk) ab = run_at(typed, k0 + i);
+#pragma unroll
+                        for (uint32_t g = 0; g < kDGroup; g++)  // (run_meets: a <= w + L - 1 and b >= w)
+                            mk[g] |= __builtin_amdgcn_uicmp(ab.x, e[g], 37) & __builtin_amdgcn_uicmp(ab.y, w[g], 35);  // (ule, uge: lane masks)
+                    }
+#pragma unroll
+                    for (uint32_t g = 0; g < kDGroup; g++) {
+                        if (lane == g0 + g) mlo = (uint32_t)mk[g], mhi = (uint32_t)(mk[g] >> 32);
+                        tot += (uint32_t)__popcll(mk[g]) * (uint32_t)__popc((uint32_t)__builtin_amdgcn_readlane((int)rb, (int)(g0 + g)));
                     }
                 }
-                f(l, p0, m);
+                KF_FINE(fine(0);)
+                if (tot == 0) continue;
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(ctr, tot);
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                total += tot;
+                for (uint64_t hm = __ballot((mlo | mhi) != 0); hm; hm &= hm - 1) {  // the slice's dirty hits
+                    const int p = __builtin_ctzll(hm);
+                    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)mlo, p);
+                    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)mhi, p);
+                    const uint32_t qx = (uint32_t)__builtin_amdgcn_readlane((int)rx, p);
+                    const uint32_t qb = (uint32_t)__builtin_amdgcn_readlane((int)rb, p);
+                    const bool mine = (((uint64_t)hi << 32 | lo) >> lane) & 1u;
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0));
+                    const uint32_t n = (uint32_t)__popc(lo) + (uint32_t)__popc(hi);
+                    for (uint32_t b = qb; b; b &= b - 1, base += n)
+                        if (mine) put(base + rank, cor_entry(qx + (uint32_t)__builtin_ctz(b), l, 1));
+                }
+                KF_FINE(fine(1);)
             }
         }
+        return total;
     };
     // f(l, reference hit) for every dirty pair, each lane on its own
     auto dirty_walk = [&](auto typed, auto &&f) {
@@ -809,41 +871,6 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
             }
         }
     };
-    // the slot of a lane's first of c entries, the wave calling together: one counter
-    // atomic per wave (an inclusive scan of the lanes' counts)
-    auto slots = [&](uint32_t c, uint32_t *ctr) -> uint32_t {
-        if (!__ballot(c > 1)) {  // (one entry per lane at most: a ballot prefix)
-            const uint64_t m = __ballot(c != 0);
-            if (!m) return 0;
-            const uint32_t leader = (uint32_t)__builtin_ctzll(m);
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(ctr, (uint32_t)__popcll(m));
-            return (uint32_t)__shfl((int)base, (int)leader) +
-                   __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-        }
-        uint32_t x = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)x, o);
-            if (lane >= (uint32_t)o) x += y;
-        }
-        const uint32_t tot = (uint32_t)__shfl((int)x, 63);
-        uint32_t base = 0;
-        if (lane == 0 && tot) base = atomicAdd(ctr, tot);
-        return (uint32_t)__shfl((int)base, 0) + x - c;
-    };
-    // a lane's corrections from its mask (one entry per inner range of each dirty hit),
-    // put(slot, entry) from one slot reservation per wave; returns their count
-    auto list_mask = [&](uint32_t l, uint32_t p0, uint64_t m, uint32_t *ctr, auto &&put) -> uint32_t {
-        uint32_t c = 0;
-        for (uint64_t b = m; b; b &= b - 1) c += __popc(s_ref[p0 + (uint32_t)__builtin_ctzll(b)].w);
-        uint32_t at = slots(c, ctr);
-        for (uint64_t b = m; b; b &= b - 1) {
-            const uint4 q = s_ref[p0 + (uint32_t)__builtin_ctzll(b)];
-            for (uint32_t w = q.w; w; w &= w - 1, at++) put(at, cor_entry(q.x + __builtin_ctz(w), l, 1));
-        }
-        return c;
-    };
     // pairwise mode lists the dirty corrections while counting them, at the top of
     // s_cor downwards (the first kFCor); the walk lists them in a second pass
     // (TFBS_PATH_STEPBITS: the figure the report has carried since a wave kept one bit
@@ -854,13 +881,12 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     uint32_t nd = 0;
     if (nref) {
         auto count_and_list = [&](auto typed) {
-            if (pairwise)
-                dirty_masks(typed, [&](uint32_t l, uint32_t p0, uint64_t m) {
-                    nd += list_mask(l, p0, m, &s_ndirty, [&](uint32_t at, uint32_t v) {
-                        if (at < kFCor) s_cor[kFCor - 1 - at] = v;
-                    });
+            if (pairwise) {
+                const uint32_t c = dirty_hits(typed, &s_ndirty, [&](uint32_t at, uint32_t v) {
+                    if (at < kFCor) s_cor[kFCor - 1 - at] = v;
                 });
-            else
+                nd += lane == 0 ? c : 0u;  // (the wave's count once)
+            } else
                 dirty_walk(typed, [&](uint32_t, const uint4 &q) { nd += __popc(q.w); });
         };
         if (runs_lds) count_and_list(KfTyped{});
@@ -886,6 +912,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     __syncthreads();
     if (!in_lds && s_arena == kFNone) return give_up(4);  // the host grows the arena for the next call
     stamp(3, wall_clock64());
+    KF_FINE(fine(2);)
     uint32_t *const cor_g = A.cor_arena + (in_lds ? 0u : s_arena);  // (the arena share: global memory)
     auto cor_ld = [&](auto typed, uint32_t e) -> uint32_t {  // entry e of the list, by placement
         if constexpr (decltype(typed)::value) {
@@ -963,11 +990,12 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         wave_push(put, &s_ncor, need, want, v);
     }
     if (!dirty_listed && nref) {  // (the walk, or more dirty corrections than the top of s_cor holds)
+        KF_FINE(fine_start();)
         auto put_in = [&](uint32_t at, uint32_t v) {
             if (at < need) cor_st(typed, at, v);
         };
         if (pairwise)
-            dirty_masks(typed, [&](uint32_t l, uint32_t p0, uint64_t m) { (void)list_mask(l, p0, m, &s_ncor, put_in); });
+            (void)dirty_hits(typed, &s_ncor, put_in);
         else
             dirty_walk(typed, [&](uint32_t l, const uint4 &q) {
                 uint32_t at = atomicAdd(&s_ncor, (uint32_t)__popc(q.w));
@@ -1015,6 +1043,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     };
     if (in_lds && runs_lds) lists_and_rows(KfTyped{});
     else lists_and_rows(KfAny{});
+    __syncthreads();  // s_rbase written: row_of reads other threads' words from here on
     stamp(5, wall_clock64());
     auto row_of = [&](uint32_t j) { return s_rbase[j >> 5] + __popc(s_bits[j >> 5] & ((1u << (j & 31)) - 1u)); };
     // the counter block: LDS chunks of rows x U, or -- when that would take more than
@@ -1081,31 +1110,56 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         if (cnt_arena) return ld_global(cnt_g + x);
         return s_cnt[x];
     };
+    KF_FINE(fine_start();)
     // the corrections by row (key << 12 becomes row << 12: no row_of per chunk)
     for (uint32_t e = tid; e < ncor; e += kFBlock) {
         const uint32_t c = cor_at(e), v = (row_of(cor_key(c)) << 12) | (c & 4095u);
         if (e < nA) cor_st(typed, e, v);
         else s_cor[cor_top(e)] = v;
     }
+    KF_FINE(fine(3);)
     uint32_t dedup_bits = 0;  // bit i: haplotype lane + 64 i takes the reference's counts as its base
     for (uint32_t i = 0, l = lane; l < U; i++, l += 64)
         if (hap_info(l) != kFNone) dedup_bits |= 1u << i;
+    // R(j), the reference hits on key j (the same in every lane), by the wave together: a hit adds to
+    // the keys x + (a bit of w), so each hit counts at most once -- a ballot.  Hit `lane` (fx, fw: its
+    // first key and ranges, read once per chunk) is in registers; the hits past 64 are read again
+    auto ref_count = [&](uint32_t j, uint32_t fx, uint32_t fw) -> uint32_t {
+        uint32_t d = j - fx;
+        uint32_t R = (uint32_t)__popcll(__ballot(d < 32 && ((fw >> d) & 1u)));
+        for (uint32_t p0 = 64; p0 < nref; p0 += 64) {
+            uint32_t x = 0, w = 0;
+            if (p0 + lane < nref) {
+                const uint4 q = s_ref[p0 + lane];
+                x = q.x, w = q.w;
+            }
+            d = j - x;
+            R += (uint32_t)__popcll(__ballot(d < 32 && ((w >> d) & 1u)));
+        }
+        return R;
+    };
+    // rows [t0, t0 + nrow)'s keys into s_rkey[0, nrow), from the key words this thread scanned (rows
+    // [s_rbase[w], ..)): once for the region when its rows fit s_rkey, else per chunk
+    auto row_keys = [&](uint32_t t0, uint32_t nrow) {
+        constexpr uint32_t per = kPerW;
+#pragma unroll
+        for (uint32_t q = 0; q < per; q++) {
+            const uint32_t w = tid * per + q;
+            if (w >= nw) continue;
+            uint32_t t = s_rbase[w], b = s_bits[w];
+            if (t >= t0 + nrow || t + __popc(b) <= t0) continue;
+            for (; b; b &= b - 1, t++)
+                if (t - t0 < nrow) s_rkey[t - t0] = 32 * w + __builtin_ctz(b);
+        }
+    };
+    if constexpr (kFBlock == 1024) {
+    // The 1 024-thread shape keeps the chunk body it had (the row-lane body below takes it past its
+    // 128 registers): keys and R per chunk through s_rr, a wave's rows one after another
     for (uint32_t t0 = 0; t0 < T; t0 += rows_per) {
         const uint32_t nrow = min(rows_per, T - t0);
         __syncthreads();  // s_rbase / cor rows written, the previous chunk's readers done
         if (tid == 0) s_nvar = 0;
-        {  // each row's key, from the key words this thread scanned (rows [s_rbase[w], ..))
-            constexpr uint32_t per = kPerW;
-#pragma unroll
-            for (uint32_t q = 0; q < per; q++) {
-                const uint32_t w = tid * per + q;
-                if (w >= nw) continue;
-                uint32_t t = s_rbase[w], b = s_bits[w];
-                if (t >= t0 + nrow || t + __popc(b) <= t0) continue;
-                for (; b; b &= b - 1, t++)
-                    if (t - t0 < nrow) s_rkey[t - t0] = 32 * w + __builtin_ctz(b);
-            }
-        }
+        row_keys(t0, nrow);
         for (uint32_t rr = tid; rr < nrow; rr += kFBlock) s_rr[rr] = 0;
         __syncthreads();
         if (tid < nref)  // R: reference hits per key
@@ -1150,25 +1204,152 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         __syncthreads();
         const uint64_t ta = A.prof ? wall_clock64() : 0;
         if (tid == 0 && s_nvar) {  // the chunk's share of the compact lists
-            s_vbase = atomicAdd(A.var_tot, (unsigned long long)s_nvar);
-            s_obase = atomicAdd(A.var_tot + 1, (unsigned long long)s_nvar * U);
+            s_vb[0] = atomicAdd(A.var_tot, (unsigned long long)s_nvar);
+            s_vb[1] = atomicAdd(A.var_tot + 1, (unsigned long long)s_nvar * U);
         }
         __syncthreads();
         if (A.prof) t_atomics += wall_clock64() - ta;
         for (uint32_t rr = wave; rr < nrow; rr += kFWaves) {
             const uint32_t slot = s_rr[rr];
             if (slot == kFNone) continue;
-            const uint64_t vi = s_vbase + slot, off = s_obase + (uint64_t)slot * U;
+            const uint64_t vi = s_vb[0] + slot, off = s_vb[1] + (uint64_t)slot * U;
             if (vi >= A.var_keys_cap || off + U > A.var_cap) continue;  // the host grows the lists and reruns
             if (lane == 0) A.var_keys[vi] = DevVarKey{r, s_rkey[rr], off};
             for (uint32_t l = lane; l < U; l += 64) A.var_counts[off + l] = count_at(rr * U + l);
         }
+    }
+    } else {
+    const bool keys_once = T <= kFRows;
+    // (the rows' lane terms from a thread index the compiler takes as new per region: built from tid
+    // itself they are hoisted out of the region loop, registers for the kernel's whole run)
+    uint32_t ct = tid;
+    arrived(ct);
+    const uint32_t cl = ct & 63u;
+    if (keys_once) row_keys(0, T);
+    // a wave takes rows wv, wv + kFWaves, ..; its i-th row's key and results stay in lane i (a chunk
+    // has at most kFRows rows: 64 per wave), and no LDS read of a row waits for the row before
+    static_assert(kFRows <= 64 * kFWaves, "a wave's rows of a chunk: one per lane");
+    for (uint32_t t0 = 0; t0 < T; t0 += rows_per) {
+        const uint32_t nrow = min(rows_per, T - t0);
+        __syncthreads();  // cor rows and row keys written, the previous chunk's readers done
+        if (!keys_once) {
+            row_keys(t0, nrow);
+            __syncthreads();
+        }
+        const uint32_t kb = keys_once ? t0 : 0u;  // the chunk's keys: s_rkey[kb, kb + nrow)
+        KF_FINE(fine(4);)
+        uint32_t fx = 0, fw = 0;
+        if (lane < nref) {
+            const uint4 q = s_ref[lane];
+            fx = q.x, fw = q.w;
+        }
+        // (the keys of the wave's rows: one read, row i's in lane i, handed out by v_readlane)
+        const uint32_t my_rr = wv + cl * kFWaves;  // the row whose key and results this lane holds
+        const uint32_t my_j = s_rkey[kb + min(my_rr, nrow - 1)];
+        for (uint32_t rr = wv, ri = 0; rr < nrow; rr += kFWaves, ri++) {  // the base of every haplotype
+            const uint32_t j = (uint32_t)__builtin_amdgcn_readlane((int)my_j, (int)ri);
+            const uint32_t R = ref_count(j, fx, fw);
+            const bool dense = A.any_dense && !A.slot_mfma[j / n_inner];
+            for (uint32_t i = 0, l = lane; l < U; i++, l += 64) {
+                const uint32_t v = dense ? A.counts[dense_base + (uint64_t)j * rg.count_stride + l]
+                                         : ((dedup_bits >> i) & 1u ? R : 0u);
+                cnt_set(rr * U + l, v);
+            }
+        }
+        __syncthreads();
+        KF_FINE(fine(5);)
+        for (uint32_t e = tid; e < ncor; e += kFBlock) {
+            const uint32_t c = cor_at(e);
+            const uint32_t t = cor_key(c) - t0;  // (its row)
+            if (t < nrow) cnt_add(t * U + cor_hap(c), cor_neg(c) ? 0xFFFFFFFFu : 1u);
+        }
+        __syncthreads();
+        KF_FINE(fine(6);)
+        // classify: one wave per row.  A lane past U reads haplotype U - 1 again (no branch around the
+        // reads); the first haplotype's count is lane 0's first
+        uint32_t my_res = 0;  // the first haplotype's count (< 2^30) | KeyFlags << 30
+        {  // (the next row's first two reads are issued before this row's are used)
+            const uint32_t la = min(cl, U - 1), lb = min(cl + 64, U - 1);
+            uint32_t na = count_at(min(wv, nrow - 1) * U + la), nb = count_at(min(wv, nrow - 1) * U + lb);
+            for (uint32_t rr = wv, i = 0; rr < nrow; rr += kFWaves, i++) {
+                const uint32_t ca = na, cb = nb, nx = min(rr + kFWaves, nrow - 1) * U;
+                na = count_at(nx + la), nb = count_at(nx + lb);
+                const uint32_t c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ca);
+                uint32_t any = ca | cb, diff = (ca ^ c0) | (cb ^ c0);
+                for (uint32_t l = cl + 128; l < U; l += 64) {
+                    const uint32_t c = count_at(rr * U + l);
+                    any |= c;
+                    diff |= c ^ c0;
+                }
+                const bool a = __ballot(any != 0) != 0, v = __ballot(diff != 0) != 0;
+                if (cl == i) my_res = c0 | ((a ? KEY_ANY : 0u) | (v ? KEY_VARIES : 0u)) << 30;
+            }
+        }
+        if (my_rr < nrow) s_rr[my_rr] = my_res >> 30;
+        __syncthreads();
+        KF_FINE(fine(7);)
+        const uint64_t ta = A.prof ? wall_clock64() : 0;
+        // a varying row's slot in the chunk's share of the compact lists: the varying rows before it
+        // (a prefix over the rows' flags, 64 rows a ballot)
+        uint32_t slot = 0, nvar = 0;
+        for (uint32_t r0 = 0; r0 < nrow; r0 += 64) {
+            const uint64_t m = __ballot(r0 + cl < nrow && (s_rr[min(r0 + cl, nrow - 1)] & KEY_VARIES));
+            if ((my_rr >> 6) == (r0 >> 6)) slot = nvar + (uint32_t)__popcll(m & ((1ull << (my_rr & 63u)) - 1ull));
+            nvar += (uint32_t)__popcll(m);
+        }
+        // the share: both totals in one atomic instruction (lane 0 the keys, lane 1 the counts), issued
+        // in front of the rows' key_first / key_flags stores, so its wait does not drain them
+        unsigned long long got = 0;
+        if (nvar && ct < 2) got = atomicAdd(A.var_tot + ct, ct ? (unsigned long long)nvar * U : (unsigned long long)nvar);
+        if (my_rr < nrow) {
+            A.key_first[ko + my_j] = my_res & 0x3FFFFFFFu;
+            A.key_flags[ko + my_j] = (uint8_t)(my_res >> 30);
+        }
+        if (nvar == 0) continue;
+        if (ct < 2) s_vb[ct] = got;
+        __syncthreads();
+        KF_FINE(fine(8);)
+        if (A.prof) t_atomics += wall_clock64() - ta;  // (slots, the atomic, the rows' stores, the barrier)
+        // the varying rows: their keys by the lanes that hold them, one store; their counts row by
+        // row, the next row's first two reads issued before this row's are stored
+        auto uni64 = [](unsigned long long v) -> uint64_t {  // (the same in every lane: scalar registers)
+            return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+                   (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32;
+        };
+        const uint64_t vbase = uni64(s_vb[0]), obase = uni64(s_vb[1]);
+        const uint64_t my_off = obase + (uint64_t)slot * U;
+        // (a row past the lists' capacity is left out: the host grows the lists and reruns)
+        const bool my_put = my_rr < nrow && ((my_res >> 30) & KEY_VARIES) && vbase + slot < A.var_keys_cap &&
+                            my_off + U <= A.var_cap;
+        if (my_put) A.var_keys[vbase + slot] = DevVarKey{r, my_j, my_off};
+        uint64_t vm = __ballot(my_put);
+        if (vm) {
+            const uint32_t la = min(cl, U - 1), lb = min(cl + 64, U - 1);
+            uint32_t nx = (wv + (uint32_t)__builtin_ctzll(vm) * kFWaves) * U;
+            uint32_t na = count_at(nx + la), nb = count_at(nx + lb);
+            while (vm) {
+                const int i = __builtin_ctzll(vm);
+                vm &= vm - 1;
+                const uint32_t ca = na, cb = nb, x0 = nx;
+                if (vm) {
+                    nx = (wv + (uint32_t)__builtin_ctzll(vm) * kFWaves) * U;
+                    na = count_at(nx + la), nb = count_at(nx + lb);
+                }
+                const uint64_t off = obase + (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)slot, i) * U;
+                if (cl < U) A.var_counts[off + cl] = ca;
+                if (cl + 64 < U) A.var_counts[off + cl + 64] = cb;
+                for (uint32_t l = cl + 128; l < U; l += 64) A.var_counts[off + l] = count_at(x0 + l);
+            }
+        }
+        KF_FINE(fine(9);)
+    }
     }
     };
     if (in_lds && h16) chunks(KfTyped{});
     else chunks(KfAny{});
     stamp(6, wall_clock64());
     stamp(7, t_atomics);
+    KF_FINE(for (uint32_t k = 0; k < kKfProfFineN; k++) stamp(kKfProfFine + k, tf[k]);)
     stamp(8, U);
     stamp(9, n_ent);
     stamp(10, nD);

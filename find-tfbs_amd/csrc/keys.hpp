@@ -88,7 +88,12 @@ struct AsmArgs {
     uint32_t grid_cap;  // TFBS_KF_GRID: at most this many persistent workgroups per shape (0: what fits)
 };
 
-constexpr uint32_t kKfProfWords = 24;  // AsmArgs::prof: 0-7 phase clocks, 8-15 sizes, 16-19 the first phase's clocks, 20 the ticket's wait
+// AsmArgs::prof: 0-7 phase clocks, 8-15 sizes, 16-19 the first phase's clocks, 20 the ticket's wait; 24-33 the
+// dirty phase's and the chunks' own times (a kernel built with TFBS_KF_FINE writes them, else 0):
+// 24 pair loop, 25 listing, 26 the dirty scan; 27 remap, 28 row keys + R, 29 base fill, 30 corrections,
+// 31 classification, 32 var-list atomics, 33 varying rows
+constexpr uint32_t kKfProfWords = 40;
+constexpr uint32_t kKfProfFine = 24, kKfProfFineN = 10;
 
 // The words of the assembly's counter block (tfbs_ctx's asm_ctr: zeroed by the scan or by one
 // memset, its first kAsmCtrWords copied back once per assembly).  The kernels take pointers to
