@@ -463,10 +463,13 @@ class Scanner:
         post-scan stage: no rescoring, no spill buckets), "reruns_post" (since the scanner was made:
         assemblies that had left it out, reported a spill record or a candidate past the lists and
         ran again in full), "fused" (the stage ran in the scan kernel's last workgroup), "cand" (the
-        scan's candidates past the waves' lists)}."""
+        scan's candidates past the waves' lists), "in_place" (left out, and the assembly's kernels
+        read the scan's spill records where they lay, up to TFBS_SPILL_INPLACE of them)}."""
         out = (C.c_uint64 * 4)()
         check(lib().tfbs_ctx_post_figures(self.h, out))
-        return dict(zip(("left_out", "reruns_post", "fused", "cand"), (int(x) for x in out)))
+        left_out, reruns_post, how, cand = (int(x) for x in out)
+        return {"left_out": left_out, "reruns_post": reruns_post, "fused": int(how == 1), "cand": cand,
+                "in_place": int(how == 2)}
 
     def matches_all(self, haplotype):
         """pattern.rs:141-171 for every pattern: list (per pattern, creation order) of [(start, end)]."""

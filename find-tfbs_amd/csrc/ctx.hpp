@@ -88,6 +88,11 @@ struct Knobs {
     int asm_lean_mode = env_int("TFBS_ASM_LEAN", 1);  // lean assemblies (AsmStages): 0 never, 1 predicted, 2 always (tests)
     // the post-scan stage in the scan's tail (measured: C2 0.083 vs 0.068 ms -- a ticket atomic per scan workgroup)
     bool post_fuse_env = env_int("TFBS_POST_FUSE", 0) != 0;
+    // spill records an assembly without the post-scan stage reads in place at most (asm_skips_post;
+    // 0: it reads none, the stage is left out only after an assembly without a record).  The fused
+    // tail, asked for, keeps the records its own way
+    uint32_t spill_inplace =
+        post_fuse_env ? 0u : (uint32_t)std::min((int)kSpillInPlaceMax, std::max(0, env_int("TFBS_SPILL_INPLACE", (int)kSpillInPlaceMax)));
     // 0: plain launches
     bool step_graphs = env_int("TFBS_STEP_GRAPH", 1) != 0 && !getenv("TFBS_SCAN_PROF") && !kf_prof_on && !debug_over;
 };
@@ -194,9 +199,14 @@ struct ScanState {
 // buckets, launched or in the scan's tail) when the batch's last checked assembly saw neither a
 // spill record nor a candidate past the lists: that assembly reads no bucket (asm_args), and
 // one that then reports either runs again in full.  post_fused: the stage ran in the scan
-// kernel's tail.
+// kernel's tail.  A few records do not need the stage either: after a checked assembly with at
+// most Knobs::spill_inplace of them (and no candidate) it is left out too, and the assembly's
+// kernels read the records where the scan put them, every region's workgroup keeping its own
+// (AsmArgs::spill_inplace); inplace is that limit, and a report of more records runs it again in full.
+// (After an assembly with no record inplace is 0: no record is read, and one that appears is a rerun.)
 struct AsmStages {
     bool wide = true, leftover = true, post = true, post_fused = false;
+    uint32_t inplace = 0;  // post left out: the records it reads in place at most (0: none)
 };
 
 // Key assembly and reduction (tfbs_batch_assemble, tfbs_batch_reduce).
@@ -380,11 +390,12 @@ AsmArgs asm_args(tfbs_ctx *ctx, const Batch &B, int mode);
 int assembly_wait(tfbs_ctx *ctx, Batch &B);
 
 // A lean assembly without the post-scan stage (AsmStages::post): the batch's last
-// checked assembly saw no spill record and no candidate past the lists (TFBS_ASM_LEAN=2:
-// always -- the tests' rerun).
+// checked assembly saw no candidate past the lists and no more spill records than are read in
+// place (Knobs::spill_inplace; 0: no record) (TFBS_ASM_LEAN=2: always -- the tests' rerun).
 inline bool asm_skips_post(const tfbs_ctx *ctx) {
     return ctx->knobs.asm_lean_mode != 0 && !ctx->asmb.asm_full &&
-           (ctx->knobs.asm_lean_mode == 2 || (ctx->asmb.prev_spill == 0 && ctx->asmb.prev_cand == 0));
+           (ctx->knobs.asm_lean_mode == 2 ||
+            (ctx->asmb.prev_spill <= ctx->knobs.spill_inplace && ctx->asmb.prev_cand == 0));
 }
 
 // ctx_rows.hip: n bytes to fd at its offset, which moves past them.

@@ -86,11 +86,17 @@ static int enqueue_assembly(tfbs_ctx *ctx, Batch &B, bool post) {
         // (without the leftover pass post_scan_kernel copies the overflow counters to
         // asm_ctr + kCtrOver; asm_ctr[kCtrNeedWide]: set when the records needed the wide kernels)
         ctx->asmb.stages.post = true;
+        ctx->asmb.stages.inplace = 0;
         ctx->asmb.stages.post_fused = ctx->scan.post_fused;
         if (ctx->scan.post_fused) {  // the scan's last workgroup did it (lean: no wide kernels)
             ctx->asmb.stages.wide = false;
-        } else if (asm_skips_post(ctx)) {  // nothing for it last time: no launch, no buckets
+        } else if (asm_skips_post(ctx)) {  // nothing for it last time, or a few records: no launch, no buckets
             ctx->asmb.stages.post = ctx->asmb.stages.wide = false;
+            // (after an assembly without a record: none is read, as before -- the kernels then take
+            // the path of a launch without a spill list, which is what C2's 50 us step is measured on --
+            // and a record that does appear reruns the assembly in full)
+            ctx->asmb.stages.inplace = ctx->knobs.asm_lean_mode != 2 && ctx->asmb.prev_spill == 0
+                                           ? 0u : std::min(ctx->knobs.spill_inplace, ctx->scan.spill_cap);
         } else if ((rc = launch_post_fused(ctx->scan.last_margs, !ctx->scan.post_done, ctx->asmb.asm_ctr.p + kCtrWgDone,
                                            std::max<uint32_t>(1, nr), ctx->asmb.asm_ctr.p + kAsmCtrWords, ctx->scan.spill_boff.p,
                                            ctx->scan.spill_sorted.p, ctx->stream, ctx->asmb.stages.wide, ctx->asmb.asm_ctr.p,
@@ -105,8 +111,16 @@ static int enqueue_assembly(tfbs_ctx *ctx, Batch &B, bool post) {
     ctx->scan.post_fused = false;
     AsmArgs a = asm_args(ctx, B, 0);
     // (no stage: no bucket is read -- stale ones least of all -- and key_fast_kernel
-    // reports the scan's overflow counters, whatever they are, for assembly_wait)
-    if (mfma && !ctx->asmb.stages.post) a.spill_count = nullptr;
+    // reports the scan's overflow counters, whatever they are, for assembly_wait; the records
+    // are read in place up to stages.inplace, by this scan's count: ScanArgs::over[0])
+    if (mfma && !ctx->asmb.stages.post) {
+        if (ctx->asmb.stages.inplace) {
+            a.spill_raw = ctx->scan.spill.p;
+            a.spill_inplace = ctx->asmb.stages.inplace;
+        } else {
+            a.spill_count = nullptr;
+        }
+    }
     a.report_fast = mfma && !ctx->asmb.stages.post ? 1u : 0u;
     a.key_first = ctx->asmb.key_first.p;
     a.key_flags = ctx->asmb.key_flags.p;
@@ -298,7 +312,8 @@ int tfbs::assembly_wait(tfbs_ctx *ctx, Batch &B) {
         // buckets, or regions key_fast_kernel gave up): again with everything
         // (or a record or a candidate with the post-scan stage left out: whether that one needed
         // the wide kernels too shows when the rerun has rescored the candidates)
-        const bool need_post = !ctx->asmb.stages.post && (nspill || ncand);
+        // (or more records than it read in place)
+        const bool need_post = !ctx->asmb.stages.post && (nspill > ctx->asmb.stages.inplace || ncand);
         const bool need_wide = !ctx->asmb.stages.wide && ctx->asmb.asm_host[kCtrNeedWide], need_left = !ctx->asmb.stages.leftover && ctx->asmb.asm_host[kCtrRedoN];
         if (need_post || need_wide || need_left) {
             ctx->asmb.asm_full = true;
@@ -391,7 +406,8 @@ static uint64_t step_signature(const tfbs_ctx *ctx, const tfbs_batch *b) {
                        (uint64_t)ctx->img.counts_live, (uint64_t)ctx->img.mfma_group_words,
                        (uint64_t)(uintptr_t)ctx->asmb.var_owner, (uint64_t)ctx->knobs.asm_lean_mode,
                        (uint64_t)(ctx->asmb.prev_spill <= kPostSerial), (uint64_t)(ctx->asmb.prev_redo == 0),
-                       (uint64_t)(ctx->asmb.prev_cand == 0), (uint64_t)(ctx->asmb.prev_spill == 0)})
+                       (uint64_t)(ctx->asmb.prev_cand == 0), (uint64_t)(ctx->asmb.prev_spill == 0),
+                       (uint64_t)(ctx->asmb.prev_spill <= ctx->knobs.spill_inplace)})
         mix(v);
     return h;
 }
@@ -521,7 +537,7 @@ int tfbs_ctx_post_figures(tfbs_ctx *ctx, uint64_t out[4]) {
     if (ctx->asmb.asm_state != 2 || !ctx->asmb.asm_host) return tfbs::fail(TFBS_E_STATE, "no checked assembly on this ctx");
     out[0] = ctx->asmb.stages.post ? 0 : 1;
     out[1] = ctx->asmb.asm_reruns_post;
-    out[2] = ctx->asmb.stages.post && ctx->asmb.stages.post_fused ? 1 : 0;
+    out[2] = ctx->asmb.stages.post ? (ctx->asmb.stages.post_fused ? 1 : 0) : ctx->asmb.stages.inplace ? 2 : 0;
     out[3] = ctx->asmb.asm_host[kCtrOver + 1];
     return TFBS_OK;
 }

@@ -557,6 +557,12 @@ int tfbs_batch_download(tfbs_ctx *ctx, tfbs_batch *b) {
         if ((rc = ctx->img.counts.ensure(std::max<uint64_t>(B.n_counts, 1)))) return rc;
     }
     AsmArgs a = asm_args(ctx, B, 1);
+    // (a scan whose checked assembly left the post-scan stage out and read its few records in
+    // place -- no candidate, so check_overflow had nothing to do --: no buckets, the same reading)
+    if (a.spill_count && !ctx->scan.post_done && !ctx->asmb.stages.post && ctx->asmb.stages.inplace) {
+        a.spill_raw = ctx->scan.spill.p;
+        a.spill_inplace = ctx->asmb.stages.inplace;
+    }
     a.counts = ctx->img.counts.p;
     a.dense_base = 1;
     if ((rc = launch_key_asm(a, (uint32_t)B.regions.size(), ctx->stream))) return rc;

@@ -45,12 +45,22 @@ constexpr uint32_t kAsmKeyWin = 32 * kAsmKeyWords;
 
 // Region r's spill records (bucketed: spill_cnt[r] of them at spill_off[r] of spill_sorted;
 // spill_off[r] means nothing where there is none).
+// In place (AsmArgs::spill_inplace): every record the assembly reads, [0, n) of the scan's own
+// list spill_raw, in no order; the reader keeps those of its region (spill_mine).
 __device__ __forceinline__ uint2 spill_range(const AsmArgs &A, uint32_t r) {
     if (!A.spill_count || !*A.spill_count) return make_uint2(0, 0);
+    if (A.spill_inplace) return make_uint2(0, min(*A.spill_count, min(A.spill_inplace, A.spill_cap)));
     const uint32_t c = A.spill_cnt[r];
     if (c == 0) return make_uint2(0, 0);
     const uint32_t o = A.spill_off[r];
     return make_uint2(o, o + c);
+}
+__device__ __forceinline__ const uint32_t *spill_list(const AsmArgs &A) {
+    return A.spill_inplace ? A.spill_raw : A.spill_sorted;
+}
+// A record's first word: region | kind << 31.  (A bucket holds its region's records alone.)
+__device__ __forceinline__ bool spill_mine(const AsmArgs &A, uint32_t w, uint32_t r) {
+    return !A.spill_inplace || (w & 0x7FFFFFFFu) == r;
 }
 
 // The inner ranges [k0, k0 + nk) a reference hit (window i of a strand of length L)
@@ -103,8 +113,8 @@ __device__ __forceinline__ void visit_hits(const AsmArgs &A, uint32_t r, uint32_
         }
     const uint2 sp = spill_range(A, r);
     for (uint32_t e = sp.x + threadIdx.x; e < sp.y; e += kAsmBlock) {
-        const uint32_t *q = A.spill_sorted + 3 * (size_t)e;
-        if (!(q[0] >> 31) && q[1] - hb < U) f(q[1] - hb, q[2]);
+        const uint32_t *q = spill_list(A) + 3 * (size_t)e;
+        if (!(q[0] >> 31) && spill_mine(A, q[0], r) && q[1] - hb < U) f(q[1] - hb, q[2]);
     }
 }
 
@@ -117,8 +127,8 @@ __device__ __forceinline__ void visit_refs(const AsmArgs &A, uint32_t r, const D
                    A.ref_hits[2 * ((size_t)r * kRefPerRegion + t) + 1]));
     const uint2 sp = spill_range(A, r);
     for (uint32_t e = sp.x + threadIdx.x; e < sp.y; e += kAsmBlock) {
-        const uint32_t *q = A.spill_sorted + 3 * (size_t)e;
-        if (q[0] >> 31) f(make_ref(A, rg, q[1], q[2]));
+        const uint32_t *q = spill_list(A) + 3 * (size_t)e;
+        if ((q[0] >> 31) && spill_mine(A, q[0], r)) f(make_ref(A, rg, q[1], q[2]));
     }
 }
 
@@ -575,7 +585,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     __shared__ uint32_t s_rkey[kFRows], s_rr[kFRows];  // per row of a chunk: its key; R(key), then its varying slot
     __shared__ uint32_t s_loff[kFLists + 1], s_lidx[kFLists];
     __shared__ uint32_t s_w[kFWaves];
-    __shared__ uint32_t s_ncor, s_nref, s_nvar, s_arena, s_ndirty;
+    __shared__ uint32_t s_ncor, s_nref, s_nvar, s_arena, s_ndirty, s_nsp;
     __shared__ unsigned long long s_vb[2];  // a chunk's share of the compact lists: first key, first count
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     auto process = [&](const uint32_t r, const uint32_t by_ticket, const uint64_t t_ticket) {  // one region (every exit is workgroup-uniform)
@@ -609,13 +619,14 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     // every wave reads the 64 reference hits, lane by lane)
     const uint32_t *const none = reinterpret_cast<const uint32_t *>(A.regions + r);
     auto have = [&](bool c, const auto *p) { return c ? p : reinterpret_cast<decltype(p)>(none); };
-    const bool spills = A.spill_count != nullptr;
+    // (records in place, AsmArgs::spill_inplace: the scan's count here, no bucket)
+    const bool spills = A.spill_count != nullptr, inplace = spills && A.spill_inplace != 0, buckets = spills && !inplace;
     uint32_t n_rc = ld_global(have(A.mfma, A.ref_count + r));
     const uint2 rh = ld_global(have(A.mfma, reinterpret_cast<const uint2 *>(A.ref_hits) + (size_t)r * kRefPerRegion + (ft & 63u)));
     uint32_t rh_g = rh.x, rh_i = rh.y;
     uint32_t sp_n = ld_global(have(spills, A.spill_count));
-    uint32_t sp_c = ld_global(have(spills, A.spill_cnt + r));
-    uint32_t sp_o = ld_global(have(spills, A.spill_off + r));
+    uint32_t sp_c = ld_global(have(buckets, A.spill_cnt + r));
+    uint32_t sp_o = ld_global(have(buckets, A.spill_off + r));
     DevRegion rg = A.regions[r];
     uint4 ra = A.region_asm[r];
     arrived(n_rc), arrived(rh_g), arrived(rh_i), arrived(sp_n), arrived(sp_c), arrived(sp_o);
@@ -651,7 +662,7 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     const uint32_t run0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ra.x);
     const uint32_t nruns = (uint32_t)__builtin_amdgcn_readfirstlane((int)ra.y);
     const uint32_t lmax = (uint32_t)__builtin_amdgcn_readfirstlane((int)ra.z);
-    if (tid == 0) s_ncor = s_nref = s_ndirty = 0;  // (read behind block_excl_scan's barriers)
+    if (tid == 0) s_ncor = s_nref = s_ndirty = s_nsp = 0;  // (read behind block_excl_scan's barriers)
     // own hits: the wave lists of the region's haplotype groups (one hitn load per
     // thread), their entries read flat over the workgroup below
     const uint32_t g_lo = hb / A.hpb, g_hi = (hb + U - 1) / A.hpb;
@@ -685,9 +696,38 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     uint32_t m_len = ld_global(meta + (refs_on ? kGStrandInts * sn + kGLen : 0u));
     uint32_t m_depth = ld_global(meta + (refs_on ? (uint32_t)kGDepth : 0u));
     uint32_t m_slot = ld_global(meta + (refs_on ? kGStrandInts * sn + kGSlot : 0u));
+    // records in place: the thread's share of the scan's list, record ft + q * block, each one's
+    // first word (region | kind << 31); a thread past the count reads the last record
+    // (the 1 024-thread shape, at its register limit and beside the common one, reads them all in
+    // rounds of their own: kSpFront = 0)
+    constexpr uint32_t kSpFront = kFBlock == 1024 ? 0u : kSpillInPlace, kSpQ = kSpFront / kFBlock;
+    static_assert(kSpFront % kFBlock == 0 && kSpQ <= 16, "a thread's records: a mask bit and a kind bit each");
+    // (the count in a scalar register: a share past it is a branch of the wave's, no load, and an
+    // assembly that reads the buckets, or no record, issues none)
+    // (sp_all: every record read in place; those past the first kSpillInPlace -- C3: one step in
+    // two hundred -- are read where they are used, in rounds of their own)
+    const uint32_t sp_all = (uint32_t)__builtin_amdgcn_readfirstlane(
+        (int)(inplace ? min(sp_n, min(A.spill_inplace, A.spill_cap)) : 0u));
+    const uint32_t sp_raw = min(sp_all, kSpFront);
+    uint32_t sw[kSpQ ? kSpQ : 1];
+#pragma unroll
+    for (uint32_t q = 0; q < kSpQ; q++) {
+        sw[q] = 0xFFFFFFFFu;  // (no region's)
+        if (q * kFBlock < sp_raw) sw[q] = ld_global(A.spill_raw + 3 * (size_t)min(ft + q * kFBlock, sp_raw - 1));
+    }
 #pragma unroll
     for (uint32_t q = 0; q < kHapQ; q++) arrived(hx[q]);
     arrived(lcnt), arrived(run_a), arrived(run_b), arrived(m_len), arrived(m_depth), arrived(m_slot);
+    // the region's records among the thread's: bit q (its record q), bit 16 + q (a reference hit)
+    // (without a record nothing of it runs: a branch of the wave's)
+    uint32_t sp_m = 0;
+    if (sp_raw) {
+#pragma unroll
+        for (uint32_t q = 0; q < kSpQ; q++) {
+            arrived(sw[q]);
+            if (ft + q * kFBlock < sp_raw && (sw[q] & 0x7FFFFFFFu) == r) sp_m |= (1u | (sw[q] >> 31) << 16) << q;
+        }
+    }
 #pragma unroll
     for (uint32_t q = 0; q < kHapQ; q++)
         if (ft + q * kFBlock >= U) hx[q] = kFNone;
@@ -725,7 +765,26 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     }
     stamp(18, wall_clock64());
     // reference hits: the region's list, then its spill records of kind 1
-    const uint2 sp = sp_n && sp_c ? make_uint2(sp_o, sp_o + sp_c) : make_uint2(0, 0);  // (spill_range)
+    const uint2 sp = buckets && sp_n && sp_c ? make_uint2(sp_o, sp_o + sp_c) : make_uint2(0, 0);  // (spill_range)
+    // (in place: the region's records counted -- s_nsp, zeroed in front of block_excl_scan's
+    // barriers, read behind the next scan's --, its reference hits from the threads that hold them)
+    if (sp_m) atomicAdd(&s_nsp, (uint32_t)__popc(sp_m & 0xFFFFu));
+    if (refs_on)
+        for (uint32_t m = sp_m >> 16; m; m &= m - 1) {
+            const uint32_t *q = A.spill_raw + 3 * (size_t)(tid + (uint32_t)__builtin_ctz(m) * kFBlock);
+            const uint32_t at = atomicAdd(&s_nref, 1u);
+            if (at < kFRefs) s_ref[at] = make_ref(A, rg, q[1], q[2]);
+        }
+    for (uint32_t e = kSpFront + tid; e < sp_all; e += kFBlock) {  // (records past the front's round)
+        const uint32_t *q = A.spill_raw + 3 * (size_t)e;
+        const uint32_t w = q[0];
+        if ((w & 0x7FFFFFFFu) != r) continue;
+        atomicAdd(&s_nsp, 1u);
+        if (refs_on && (w >> 31)) {
+            const uint32_t at = atomicAdd(&s_nref, 1u);
+            if (at < kFRefs) s_ref[at] = make_ref(A, rg, q[1], q[2]);
+        }
+    }
     if (refs_on) {
         if (tid < n_list) {
             const uint32_t at = atomicAdd(&s_nref, 1u);
@@ -897,7 +956,9 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
     const bool dirty_listed = pairwise && nD <= kFCor;
     // the corrections' list: LDS when they fit (own hits from the bottom, the dirty
     // ones at the top), else a share of the launch's arena (the dirty ones first)
-    const uint32_t need = n_ent + (sp.y - sp.x) + nD;  // (an upper bound: entries of other regions' haplotypes)
+    // (an upper bound: entries of other regions' haplotypes; the region's spill records from its
+    // bucket, or counted in place -- the same figure, so the same placement)
+    const uint32_t need = n_ent + (sp.y - sp.x) + s_nsp + nD;
     const bool in_lds = need <= (kFCor < A.cor_lds ? kFCor : A.cor_lds);
     pw |= (stepbits ? TFBS_PATH_STEPBITS : 0u) | (dirty_listed ? TFBS_PATH_DIRTY_LISTED : 0u) |
           (in_lds ? 0u : TFBS_PATH_COR_ARENA);
@@ -985,6 +1046,28 @@ void key_fast_kernel(AsmArgs A, uint32_t first, uint32_t count, uint32_t which) 
         if (e < sp.y) {
             const uint32_t *q = A.spill_sorted + 3 * (size_t)e;
             want = !(q[0] >> 31) && q[1] - hb < U;
+            v = cor_entry(q[2], q[1] - hb, 0);
+        }
+        wave_push(put, &s_ncor, need, want, v);
+    }
+    // (in place: the own hits among the threads' records, a record per lane and turn of the wave)
+    for (uint32_t m = sp_m & ~(sp_m >> 16) & 0xFFFFu; __ballot(m != 0) != 0; m &= m - 1) {
+        bool want = false;
+        uint32_t v = 0;
+        if (m) {
+            const uint32_t *q = A.spill_raw + 3 * (size_t)(tid + (uint32_t)__builtin_ctz(m) * kFBlock);
+            want = q[1] - hb < U;
+            v = cor_entry(q[2], q[1] - hb, 0);
+        }
+        wave_push(put, &s_ncor, need, want, v);
+    }
+    for (uint32_t e0 = kSpFront; e0 < sp_all; e0 += kFBlock) {  // (and those past the front's round)
+        const uint32_t e = e0 + tid;
+        bool want = false;
+        uint32_t v = 0;
+        if (e < sp_all) {
+            const uint32_t *q = A.spill_raw + 3 * (size_t)e;
+            want = q[0] == r && q[1] - hb < U;  // (bit 31 clear: an own hit)
             v = cor_entry(q[2], q[1] - hb, 0);
         }
         wave_push(put, &s_ncor, need, want, v);

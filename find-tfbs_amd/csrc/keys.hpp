@@ -40,6 +40,13 @@ struct AsmArgs {
     // neither spill_off nor spill_cnt is read), bucketed up to spill_cap records
     const uint32_t *spill_count;
     uint32_t spill_cap;
+    // != 0: no post-scan stage ran and the records are read in place -- the first
+    // min(*spill_count, spill_inplace, spill_cap) of spill_raw (ScanArgs::spill: region | kind << 31,
+    // then the record's two words), each reader keeping its region's; the buckets are not read.
+    // At most kSpillInPlaceMax; more records than that (or a candidate past the lists): the host
+    // runs the assembly again in full (assembly_wait)
+    const uint32_t *spill_raw;
+    uint32_t spill_inplace;
     uint32_t *counts;           // dense counts: read (LUT/generic slots) / written (mode 1)
     uint32_t dense_base;        // != 0: counts exist (haps' count_off are valid)
     uint32_t *scratch;          // counters of regions with more haplotypes than the LDS block holds
@@ -93,6 +100,16 @@ struct AsmArgs {
 // 24 pair loop, 25 listing, 26 the dirty scan; 27 remap, 28 row keys + R, 29 base fill, 30 corrections,
 // 31 classification, 32 var-list atomics, 33 varying rows
 constexpr uint32_t kKfProfWords = 40;
+
+// Spill records an assembly without the post-scan stage reads in place at most: kSpillInPlaceMax
+// (TFBS_SPILL_INPLACE lowers it; 0: such an assembly reads none).  Every region's workgroup tests
+// all of them, so the limit is what that costs key_fast_kernel against the stage's launch.
+// key_fast_kernel's threads take the first kSpillInPlace, kSpillInPlace / block records each, with
+// the front's second load round; the others in rounds of their own.  C3's steps have 7 to 2 304
+// records (median 942, 1 in 100 more than 1 946): a limit of 2 048 sent one step in two hundred
+// through a rerun in full and a new step graph, which cost the step what the stage's launch had.
+constexpr uint32_t kSpillInPlace = 2048;
+constexpr uint32_t kSpillInPlaceMax = 8192;  // (kPostSerial: what the stage's one workgroup buckets)
 constexpr uint32_t kKfProfFine = 24, kKfProfFineN = 10;
 
 // The words of the assembly's counter block (tfbs_ctx's asm_ctr: zeroed by the scan or by one

@@ -542,12 +542,14 @@ int tfbs_ctx_region_asm(tfbs_ctx *ctx, uint32_t *region_asm, size_t cap_regions,
 int tfbs_ctx_assembly_figures(tfbs_ctx *ctx, uint64_t out[8]);
 /* The post-scan stage (the overflow candidates' rescoring and the spill records' buckets) of the
  * last checked assembly: out[0] 1 if it was left out (a lean assembly leaves it out when the
- * batch's last checked assembly saw no spill record and no candidate past the lists; under
- * TFBS_ASM_LEAN=2 always), out[1] since the ctx was made the assemblies that had left it out,
- * reported a record or a candidate and ran again in full (they count in out[5] of
- * tfbs_ctx_assembly_figures too), out[2] 1 if the stage ran in the scan kernel's last
- * workgroup (TFBS_POST_FUSE=1) and not as a launch, out[3] the scan's candidates past the
- * waves' lists (out[2] of tfbs_ctx_assembly_figures: its spill records). */
+ * batch's last checked assembly saw no candidate past the lists and at most TFBS_SPILL_INPLACE
+ * spill records -- default 8 192, 0: none --, which the assembly's kernels then read where the
+ * scan left them; under TFBS_ASM_LEAN=2 always), out[1] since the ctx was made the assemblies
+ * that had left it out, reported a candidate or more records than that and ran again in full
+ * (they count in out[5] of tfbs_ctx_assembly_figures too), out[2] 1 if the stage ran in the
+ * scan kernel's last workgroup (TFBS_POST_FUSE=1, which turns the in-place reading off) and
+ * not as a launch, 2 if it was left out and the records were read in place, out[3] the scan's
+ * candidates past the waves' lists (out[2] of tfbs_ctx_assembly_figures: its spill records). */
 int tfbs_ctx_post_figures(tfbs_ctx *ctx, uint64_t out[4]);
 /* What the key assembly branches on, from the host batch (no device; the tests' proofs).
  * tfbs_batch_region_layout: out[0] the region's first distinct haplotype in the batch (the
