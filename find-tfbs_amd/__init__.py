@@ -394,6 +394,32 @@ def scores_as_genotypes(left, right, min_spread=1):
     return maf.value, info.value.decode(), gts.value.decode()
 
 
+def affinity_mlog2(xs, device=-1):
+    """tfbs_affinity_mlog2: floor(1000 * log2(x)) of every x (u64; -1 for x = 0) as a list of ints,
+    on the host (device -1) or in one launch of the affinity rows' device function on HIP device
+    `device`."""
+    n = len(xs)
+    out = (C.c_int32 * max(1, n))()
+    check(lib().tfbs_affinity_mlog2((C.c_uint64 * max(1, n))(*xs), n, device, out))
+    return list(out[:n])
+
+
+def affinity_as_genotypes(left, right, top, min_spread=1):
+    """tfbs_affinity_as_genotypes (host only): the affinity rows' definition on one candidate row's
+    per-sample values (the two haplotypes' affinity sums, u64 below 2^63) -> (maf, info, genotypes),
+    info = "LOG2AFF=<lo>,<hi>;AFF=<xlo>,<xhi>;TOP=<top>;freqs=<zero>/<one>/<two>", or None when
+    there is no row."""
+    n = len(left)
+    maf = C.c_uint32()
+    info = C.create_string_buffer(224)
+    gts = C.create_string_buffer(16 + 11 * n)
+    r = check(lib().tfbs_affinity_as_genotypes((C.c_uint64 * max(1, n))(*left), (C.c_uint64 * max(1, n))(*right), n, top,
+                                               min_spread, C.byref(maf), info, len(info), gts, len(gts)))
+    if r != 1:
+        return None
+    return maf.value, info.value.decode(), gts.value.decode()
+
+
 # tfbs_batch_assembly_paths' bits (tfbs_amd.h TFBS_PATH_*)
 PATH_BITS = {"FAST": 1 << 0, "BIG": 1 << 1, "WALK": 1 << 2, "STEPBITS": 1 << 3, "DIRTY_LISTED": 1 << 4,
              "COR_ARENA": 1 << 5, "LISTS_SLICED": 1 << 6, "RUNS_L2": 1 << 7, "HAP_GLOBAL": 1 << 8, "U32": 1 << 9,
@@ -514,6 +540,13 @@ class Scanner:
         out = (C.c_double * 2)()
         check(lib().tfbs_ctx_last_affinity_ms(self.h, out))
         return out[0], out[1]
+
+    def last_affinity_rows_ms(self):
+        """tfbs_ctx_last_affinity_rows_ms: (affinity kernel, fold + statistics, text kernel ms from HIP
+        events, copy-back + host ms) of the last affinity_rows()."""
+        out = (C.c_double * 4)()
+        check(lib().tfbs_ctx_last_affinity_rows_ms(self.h, out))
+        return tuple(out)
 
     def last_scores_ms(self):
         """tfbs_ctx_last_scores_ms: (best kernel, fold + statistics, text kernel ms from HIP events,
@@ -1010,17 +1043,24 @@ class RegionBatch:
         """tfbs_batch_score_rows: the score rows of regions [r0, r1) of this batch, resident on the
         scanner (after an upload; no scan needed; the batch keeps its membership) -> (text, n_rows,
         next_position).  fake_position None: counted only -> ("", n_rows, None)."""
+        return self._rows_text(lib().tfbs_batch_score_rows, scanner, chromosome, min_maf, min_spread, fake_position, r0, r1)
+
+    def affinity_rows(self, scanner, chromosome, min_maf=0, min_spread=1, fake_position=1, r0=None, r1=None):
+        """tfbs_batch_affinity_rows: the affinity rows of regions [r0, r1) of this batch, as
+        score_rows (min_spread in milli-bits) -> (text, n_rows, next_position)."""
+        return self._rows_text(lib().tfbs_batch_affinity_rows, scanner, chromosome, min_maf, min_spread, fake_position, r0, r1)
+
+    def _rows_text(self, call, scanner, chromosome, min_maf, min_spread, fake_position, r0, r1):
         p = C.c_void_p()
         n = C.c_size_t()
         rows = C.c_uint64()
         a, z = 0 if r0 is None else r0, self.num_regions if r1 is None else r1
         if fake_position is None:
-            check(lib().tfbs_batch_score_rows(scanner.h, self.h, a, z, _u(chromosome), min_maf, min_spread, None, None,
-                                              None, C.byref(rows)))
+            check(call(scanner.h, self.h, a, z, _u(chromosome), min_maf, min_spread, None, None, None, C.byref(rows)))
             return "", rows.value, None
         fp = C.c_uint32(fake_position)
-        check(lib().tfbs_batch_score_rows(scanner.h, self.h, a, z, _u(chromosome), min_maf, min_spread, C.byref(fp),
-                                          C.byref(p), C.byref(n), C.byref(rows)))
+        check(call(scanner.h, self.h, a, z, _u(chromosome), min_maf, min_spread, C.byref(fp), C.byref(p), C.byref(n),
+                   C.byref(rows)))
         try:
             text = C.string_at(p, n.value).decode()
         finally:
@@ -1282,7 +1322,8 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
         after_position=0, verbose=False, device=0, regions_per_batch=0, devices=None, dipwm_file=None,
         hits_output=None, hits_mode="diff", best_output=None, best_mode="diff", effects_output=None,
         effects_mode="sites", scores_output=None, scores_min_spread=1, pwm_pvalue=None, mutscan_output=None,
-        mutscan_kinds=0, affinity_output=None, affinity_mode="diff"):
+        mutscan_kinds=0, affinity_output=None, affinity_mode="diff", affinity_rows_output=None,
+        affinity_rows_min_spread=1):
     """main.rs:234-393 `run` with the reference's argument order; writes the BGZF VCF.
     devices: list of HIP devices; batch g of merged regions runs on devices[g % n] (same
     text for any list; a device may repeat).  hits_output: also write every region's hit
@@ -1297,7 +1338,10 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     also write every region's mutation scan there as BGZF TSV (MUTSCAN_HEADER, then
     RegionBatch.mutscan_tsv's lines for the kinds of mutscan_kinds: a mask of MUT_* or names; 0 means
     gain and loss).  affinity_output: also write every region's binding affinities there as BGZF TSV
-    (AFFINITY_HEADER, then RegionBatch.affinity_tsv's lines in affinity_mode "all" or "diff")."""
+    (AFFINITY_HEADER, then RegionBatch.affinity_tsv's lines in affinity_mode "all" or "diff").
+    affinity_rows_output: also write the affinity rows (RegionBatch.affinity_rows with min_maf and
+    affinity_rows_min_spread, POS from 1) there as a further BGZF VCF under the main output's #CHROM
+    line."""
     a = _capi.tfbs_run_args()
     keep = [_u(x) if x is not None else None for x in (chromosome, bcf, ",".join(bed_files), reference_genome_file,
                                                         wanted_samples, pwm_file, pwm_threshold_directory,
@@ -1325,7 +1369,17 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     a.best_mode = BEST_MODES[best_mode]
     mo = _u(mutscan_output) if mutscan_output is not None else None
     ao = _u(affinity_output) if affinity_output is not None else None
-    if affinity_output is not None:
+    aro = _u(affinity_rows_output) if affinity_rows_output is not None else None
+    if affinity_rows_output is not None:
+        x = _capi.tfbs_run_ext_affinity_rows()
+        x.pwm_pvalue = pwm_pvalue or 0.0
+        x.mutscan_output = mo
+        x.mutscan_kinds = mutscan_kinds_mask(mutscan_kinds)
+        x.affinity_output = ao
+        x.affinity_mode = AFFINITY_MODES[affinity_mode]
+        x.affinity_rows_output = aro
+        x.affinity_rows_min_spread = affinity_rows_min_spread
+    elif affinity_output is not None:
         x = _capi.tfbs_run_ext_affinity()
         x.pwm_pvalue = pwm_pvalue or 0.0
         x.mutscan_output = mo

@@ -116,6 +116,12 @@ class tfbs_run_ext_affinity(C.Structure):
     _fields_ = tfbs_run_ext_mutscan._fields_ + [("affinity_output", C.c_char_p), ("affinity_mode", C.c_int)]
 
 
+class tfbs_run_ext_affinity_rows(C.Structure):
+    """tfbs_run_ext as the header has it since the affinity rows (their two fields at the end)."""
+    _fields_ = tfbs_run_ext_affinity._fields_ + [("affinity_rows_output", C.c_char_p),
+                                                 ("affinity_rows_min_spread", C.c_uint64)]
+
+
 # (name, restype, argtypes) for every symbol in include/tfbs_amd.h
 SIGNATURES = [
     ("tfbs_strerror", C.c_char_p, [C.c_int]),
@@ -264,6 +270,12 @@ SIGNATURES = [
     ("tfbs_batch_score_rows", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint64, u32p,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), u64p]),
     ("tfbs_ctx_last_scores_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
+    ("tfbs_affinity_mlog2", C.c_int, [u64p, C.c_size_t, C.c_int, i32p]),
+    ("tfbs_affinity_as_genotypes", C.c_int, [u64p, u64p, C.c_size_t, C.c_int32, C.c_uint64, u32p, C.c_char_p,
+                                             C.c_size_t, C.c_char_p, C.c_size_t]),
+    ("tfbs_batch_affinity_rows", C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_char_p, C.c_uint32, C.c_uint64, u32p,
+                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), u64p]),
+    ("tfbs_ctx_last_affinity_rows_ms", C.c_int, [vp, C.POINTER(C.c_double)]),
     ("tfbs_free", None, [C.c_void_p]),
     ("tfbs_counts_as_genotypes", C.c_int, [u32p, u32p, C.c_size_t, u32p, C.c_char_p, C.c_size_t, C.c_char_p,
                                            C.c_size_t]),

@@ -5,9 +5,12 @@
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <string>
 
+#include "affinity_log_table.hpp"
+#include "affinity_rows.hpp"
 #include "affinity_tables.hpp"
 #include "hits.hpp"
 #include "score_dist.hpp"
@@ -51,6 +54,39 @@ uint32_t affinity_max_strands(const Patterns &P) {
     uint32_t most = 0;
     for (const Pat &p : P.pats) most = std::max(most, ++n[p.pattern_id]);
     return most;
+}
+
+int32_t affinity_mlog2_host(uint64_t x) { return affinity_mlog2(x, kAffLogP); }
+
+std::string affinity_row_info(int64_t lo, int64_t hi, uint64_t xlo, uint64_t xhi, int32_t top, uint64_t zero,
+                              uint64_t one, uint64_t two) {
+    char buf[224];
+    const int m = snprintf(buf, sizeof buf,
+                           "LOG2AFF=%" PRId64 ",%" PRId64 ";AFF=%" PRIu64 ",%" PRIu64 ";TOP=%d;freqs=%" PRIu64 "/%" PRIu64
+                           "/%" PRIu64,
+                           lo, hi, xlo, xhi, top, zero, one, two);
+    return std::string(buf, (size_t)m);
+}
+
+bool affinity_as_genotypes(const uint64_t *left, const uint64_t *right, size_t n, int32_t top, uint64_t min_spread,
+                           uint32_t *maf, std::string &info, std::string &gts) {
+    if (n == 0) return false;
+    uint64_t xlo = left[0] + right[0], xhi = xlo;  // (each below 2^63: no wrap)
+    for (size_t i = 1; i < n; i++) {
+        const uint64_t x = left[i] + right[i];
+        xlo = std::min(xlo, x);
+        xhi = std::max(xhi, x);
+    }
+    const int64_t lo = affinity_mlog2_host(xlo), hi = affinity_mlog2_host(xhi);  // (mlog2 is monotone)
+    const uint64_t spread = (uint64_t)(hi - lo);
+    if (spread == 0 || spread < min_spread) return false;
+    uint64_t cnt[3] = {0, 0, 0};
+    gts.reserve(gts.size() + n * 11);
+    for (size_t i = 0; i < n; i++)
+        append_row_field(gts, (uint64_t)((int64_t)affinity_mlog2_host(left[i] + right[i]) - lo), spread, cnt);
+    *maf = (uint32_t)maf_of(cnt[0], cnt[1], cnt[2]);
+    info += affinity_row_info(lo, hi, xlo, xhi, top, cnt[0], cnt[1], cnt[2]);
+    return true;
 }
 
 namespace {
@@ -182,6 +218,28 @@ int tfbs_patterns_affinity_tops(const tfbs_patterns *p, int32_t *out) {
     if (int rc = tfbs::affinity_tops(tfbs::patterns_of(p), &tops)) return rc;
     std::copy(tops.begin(), tops.end(), out);
     return TFBS_OK;
+}
+
+int tfbs_affinity_mlog2(const uint64_t *x, size_t n, int device, int32_t *out) {
+    if (n && (!x || !out)) return tfbs::fail(TFBS_E_ARG, "null argument");
+    if (device < -1) return tfbs::fail(TFBS_E_ARG, "device is -1 (the host) or a HIP device");
+    if (device >= 0) return tfbs::affinity_mlog2_device(x, n, device, out);
+    for (size_t i = 0; i < n; i++) out[i] = tfbs::affinity_mlog2_host(x[i]);
+    return TFBS_OK;
+}
+
+int tfbs_affinity_as_genotypes(const uint64_t *left, const uint64_t *right, size_t n, int32_t top, uint64_t min_spread,
+                               uint32_t *maf, char *info, size_t info_cap, char *genotypes, size_t gt_cap) {
+    if (!maf || (n && (!left || !right))) return tfbs::fail(TFBS_E_ARG, "null argument");
+    for (size_t i = 0; i < n; i++)
+        if ((left[i] | right[i]) >> 63) return tfbs::fail(TFBS_E_ARG, "an affinity sum of 2^63 or more");
+    std::string a, g;
+    if (!tfbs::affinity_as_genotypes(left, right, n, top, min_spread, maf, a, g)) return 0;
+    if (!info || !genotypes || a.size() + 1 > info_cap || g.size() + 1 > gt_cap)
+        return tfbs::fail(TFBS_E_ARG, "output capacity too small");
+    memcpy(info, a.c_str(), a.size() + 1);
+    memcpy(genotypes, g.c_str(), g.size() + 1);
+    return 1;
 }
 
 int tfbs_batch_affinity_tsv(const tfbs_batch *b, const tfbs_affinity *aff, size_t n, const char *chromosome,

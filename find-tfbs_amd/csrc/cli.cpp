@@ -20,6 +20,7 @@ static void usage() {
             "       [--scores_output FILE [--scores_min_spread N]]\n"
             "       [--mutscan_output FILE [--mutscan_kinds gain,loss,change,same,none]]\n"
             "       [--affinity_output FILE [--affinity_mode all|diff]]\n"
+            "       [--affinity_rows_output FILE [--affinity_rows_min_spread N]]\n"
             "       [--forward_only] [--threads N] [--min_maf N] [--after_position P] [--samples FILE]\n"
             "       [--tabix] [--verbose] [--device D | --devices D1,D2,.. | --gpus N] [--regions_per_batch N]\n"
             "  --devices: one contiguous block of merged regions per listed HIP device (a device may repeat);\n"
@@ -54,7 +55,12 @@ static void usage() {
             "  range), pattern_id and distinct haplotype the sum over every window of floor(2^40 exp((score - top) / 1000)),\n"
             "  top the pattern_id's highest possible score: exact integers, ln(affinity) = top / 1000 + ln(sum) - 40 ln 2.\n"
             "  --affinity_mode all: one `aff` line each; diff (default): `hap` lines, then where a haplotype's sum\n"
-            "  differs from the most carried haplotype's a `base` line and `alt` lines with the sum's delta.\n");
+            "  differs from the most carried haplotype's a `base` line and `alt` lines with the sum's delta.\n"
+            "  --affinity_rows_output FILE: also write each sample's total binding affinity, as a further BGZF VCF: per\n"
+            "  (bed, inner range) and pattern_id one row whose per-sample GT:DS comes from floor(1000 log2) of the sum of\n"
+            "  the sample's two haplotypes' affinities (INFO LOG2AFF=<lowest>,<highest>;AFF=<their sums>;TOP=<top>); rows\n"
+            "  whose logarithms span less than --affinity_rows_min_spread N (milli-bits, default 1) are left out.\n"
+            "  --min_maf applies.\n");
 }
 
 int main(int argc, char **argv) {
@@ -141,6 +147,16 @@ int main(int argc, char **argv) {
                 return 2;
             }
             x.affinity_mode = m == "all" ? TFBS_AFFINITY_ALL : TFBS_AFFINITY_DIFF;
+        }
+        else if (k == "--affinity_rows_output") x.affinity_rows_output = val("--affinity_rows_output");
+        else if (k == "--affinity_rows_min_spread") {
+            char *end = nullptr;
+            const char *v = val("--affinity_rows_min_spread");
+            x.affinity_rows_min_spread = strtoull(v, &end, 10);
+            if (end == v || *end || *v == '-') {
+                fprintf(stderr, "error: --affinity_rows_min_spread is a count of milli-bits\n");
+                return 2;
+            }
         }
         else if (k == "--scores_output") x.scores_output = val("--scores_output");
         else if (k == "--scores_min_spread") x.scores_min_spread = strtoull(val("--scores_min_spread"), nullptr, 10);

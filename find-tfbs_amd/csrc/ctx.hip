@@ -52,6 +52,7 @@ void tfbs_ctx_destroy(tfbs_ctx *ctx) {
     tfbs::effects_state_destroy(ctx->effects_state);
     tfbs::mutscan_state_destroy(ctx->mutscan_state);
     tfbs::affinity_state_destroy(ctx->affinity_state);
+    tfbs::affinity_rows_state_destroy(ctx->affinity_rows_state);
     delete ctx;
 }
 

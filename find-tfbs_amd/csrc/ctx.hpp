@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "affinity_rows.hpp"
 #include "batch.hpp"
 #include "bgzf_gpu.hpp"
 #include "hip_util.hpp"
@@ -360,7 +361,7 @@ struct tfbs_ctx {
     tfbs::EncState enc;
     tfbs::RowsBgzf rows;
     tfbs::StepGraph step;
-    // hit lists, best sites, score rows, variant effects, mutation scans and affinities: tables, scratch and
+    // hit lists, best sites, score rows, variant effects, mutation scans, affinities and affinity rows: tables, scratch and
     // timers, each made by its entry point's first call (deleted by tfbs_ctx_destroy)
     tfbs::HitsState *hits_state = nullptr;
     tfbs::BestState *best_state = nullptr;
@@ -368,6 +369,7 @@ struct tfbs_ctx {
     tfbs::EffectsState *effects_state = nullptr;
     tfbs::MutscanState *mutscan_state = nullptr;
     tfbs::AffinityState *affinity_state = nullptr;
+    tfbs::AffinityRowsState *affinity_rows_state = nullptr;  // (its frame is scores_state's, its records' tables affinity_state's)
 };
 
 namespace tfbs {

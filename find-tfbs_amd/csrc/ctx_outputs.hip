@@ -1,5 +1,6 @@
-// The entry points of the hit lists, best sites, affinities, score rows, variant effects and mutation scans: the
-// resident image handed to their drivers (scan_hits.hip, scan_best.hip, scan_affinity.hip, score_rows.hip); the last two
+// The entry points of the hit lists, best sites, affinities, score rows, affinity rows, variant effects and mutation
+// scans: the resident image handed to their drivers (scan_hits.hip, scan_best.hip, scan_affinity.hip, score_rows.hip,
+// affinity_rows.hip); the last two
 // (scan_effects.hip, scan_mutscan.hip) read the batch's kept variants instead.
 #include "ctx.hpp"
 
@@ -102,6 +103,33 @@ int tfbs_batch_score_rows(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, co
 int tfbs_ctx_last_scores_ms(const tfbs_ctx *ctx, double out[4]) {
     if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
     scores_last_ms(ctx->scores_state, out);
+    return TFBS_OK;
+}
+
+// Affinity rows (affinity_rows.hip): as the score rows; the pattern set checked as the affinity call's.
+int tfbs_batch_affinity_rows(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, const char *chromosome,
+                             uint32_t min_maf, uint64_t min_spread, uint32_t *fake_position, char **text, size_t *len,
+                             uint64_t *n_rows) {
+    ScanImage img;
+    if (ctx && b && b->b.pats != ctx->pats) return tfbs::fail(TFBS_E_ARG, "batch and ctx use different pattern sets");
+    if (int rc = resident_image(ctx, b, r0, r1, !chromosome || !n_rows || (text && (!len || !fake_position)), &img))
+        return rc;
+    if (!b->b.keep_membership) return tfbs::fail(TFBS_E_STATE, "batch created without membership");
+    std::string out;
+    uint32_t fake = fake_position ? *fake_position : 1;
+    if (int rc = affinity_rows_run(&ctx->affinity_rows_state, &ctx->scores_state, &ctx->affinity_state, ctx->device,
+                                   ctx->stream, *ctx->pats, img, b->b, r0, r1, tfbs::strip_chr(chromosome), min_maf,
+                                   min_spread, &fake, text ? &out : nullptr, n_rows))
+        return rc;
+    if (!text) return TFBS_OK;
+    if (int rc = tfbs::text_out(out, text, len)) return rc;
+    *fake_position = fake;
+    return TFBS_OK;
+}
+
+int tfbs_ctx_last_affinity_rows_ms(const tfbs_ctx *ctx, double out[4]) {
+    if (!ctx || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
+    affinity_rows_last_ms(ctx->affinity_rows_state, out);
     return TFBS_OK;
 }
 

@@ -130,6 +130,7 @@ struct TextOut {
 // --scores_output: the batches' score rows (tfbs_batch_score_rows), a second VCF.  Batch g's
 // first POS is batch g - 1's plus its rows: a second chain as Ordered::chain, fed by the
 // count-only call as soon as a batch has counted its rows; the texts go out in batch order.
+// --affinity_rows_output (tfbs_batch_affinity_rows) is a second instance: a POS chain of its own.
 struct ScoresOut {
     TextOut out;
     uint64_t min_spread = 1;
@@ -174,6 +175,7 @@ struct RunSetup {
     TextOut *mutscan = nullptr;  // null without --mutscan_output: the same (variants are kept for either of the two)
     uint32_t mutscan_kinds = TFBS_MUT_GAIN | TFBS_MUT_LOSS;
     ScoresOut *scores = nullptr;  // null without --scores_output: the same
+    ScoresOut *affinity_rows = nullptr;  // null without --affinity_rows_output: the same
     TextOut *affinity = nullptr;  // null without --affinity_output: the same
     int affinity_mode = TFBS_AFFINITY_DIFF;
     std::string chrom;
@@ -499,6 +501,22 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
             if (n_text != n_rows) return fail(TFBS_E_STATE, "score rows: the count and the text disagree");
             if ((rc = S.scores->out.submit(g, std::string(text, len)))) return rc;
         }
+        if (S.affinity_rows) {  // the batch's affinity rows: as the score rows, on their own chain
+            ScoresOut &O = *S.affinity_rows;
+            uint64_t n_rows = 0, n_text = 0;
+            uint32_t fk = 0;
+            char *text = nullptr;
+            size_t len = 0;
+            if ((rc = tfbs_batch_affinity_rows(ctx, bb, 0, B.rh.size(), S.chrom.c_str(), a->min_maf, O.min_spread, nullptr,
+                                               nullptr, nullptr, &n_rows)) ||
+                (rc = O.chain(g, n_rows, &fk)) ||
+                (rc = tfbs_batch_affinity_rows(ctx, bb, 0, B.rh.size(), S.chrom.c_str(), a->min_maf, O.min_spread, &fk,
+                                               &text, &len, &n_text)))
+                return rc;
+            std::unique_ptr<char, void (*)(void *)> tguard(text, free);
+            if (n_text != n_rows) return fail(TFBS_E_STATE, "affinity rows: the count and the text disagree");
+            if ((rc = O.out.submit(g, std::string(text, len)))) return rc;
+        }
         if (a->verbose) {
             for (size_t r = 0; r < B.rh.size(); r++)
                 fprintf(stdout, "Peak %zu/%zu\t%llu\t%llu\t%u haplotypes\t%u variants\n", g * S.per_batch + r + 1,
@@ -697,7 +715,14 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     uint32_t mutscan_kinds = 0;
     const char *affinity_output = nullptr;
     int affinity_mode = TFBS_AFFINITY_ALL;
+    const char *affinity_rows_output = nullptr;
+    uint64_t affinity_rows_min_spread = 1;
     if (ext) {
+        if (ext->size >= offsetof(tfbs_run_ext, affinity_rows_output) + sizeof ext->affinity_rows_output)
+            affinity_rows_output = ext->affinity_rows_output;
+        if (ext->size >= offsetof(tfbs_run_ext, affinity_rows_min_spread) + sizeof ext->affinity_rows_min_spread &&
+            ext->affinity_rows_min_spread)
+            affinity_rows_min_spread = ext->affinity_rows_min_spread;
         if (ext->size >= offsetof(tfbs_run_ext, affinity_output) + sizeof ext->affinity_output)
             affinity_output = ext->affinity_output;
         if (ext->size >= offsetof(tfbs_run_ext, affinity_mode) + sizeof ext->affinity_mode)
@@ -854,6 +879,12 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
         scores_out.min_spread = scores_min_spread;
         S.scores = &scores_out;
     }
+    ScoresOut affinity_rows_out;
+    if (affinity_rows_output) {
+        if ((rc = affinity_rows_out.out.open(affinity_rows_output, threads, header.c_str()))) return rc;
+        affinity_rows_out.min_spread = affinity_rows_min_spread;
+        S.affinity_rows = &affinity_rows_out;
+    }
 
     // shards: batch g of merged regions on device g % n (one device:
     // every batch); rows in merged-peak order, POS counted across the devices
@@ -868,6 +899,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     }
     for (size_t g = 0; g < n_batches; g++) shards[g % n_sh].batches.push_back(g);
     if (S.scores) S.scores->batches(n_batches);
+    if (S.affinity_rows) S.affinity_rows->batches(n_batches);
     const std::string chr = strip_chr(S.chrom);
     uint32_t fake = 1;
     const bool timing = getenv("TFBS_RUN_TIMING") && atoi(getenv("TFBS_RUN_TIMING"));
@@ -977,6 +1009,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
                 if (rc) {
                     ord.abort(rc, tfbs_last_error());
                     if (S.scores) S.scores->abort();
+                    if (S.affinity_rows) S.affinity_rows->abort();
                     return;
                 }
                 ord.finished(g);
@@ -991,6 +1024,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
                 shards[k].err = tfbs_last_error();
                 ord.abort(shards[k].rc, shards[k].err);
                 if (S.scores) S.scores->abort();
+                if (S.affinity_rows) S.affinity_rows->abort();
             }
         };
         std::vector<std::thread> ts;
@@ -1019,6 +1053,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     if (S.mutscan && (rc = mutscan_out.finish())) return rc;
     if (S.affinity && (rc = affinity_out.finish())) return rc;
     if (S.scores && (rc = scores_out.out.finish())) return rc;
+    if (S.affinity_rows && (rc = affinity_rows_out.out.finish())) return rc;
     const double t_close = now() - t0;
     if (timing)
         for (size_t k = 0; k < n_sh; k++)

@@ -23,6 +23,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "affinity_rows.hpp"
 #include "affinity_tables.hpp"
 #include "range_sweep.hpp"
 
@@ -116,25 +117,52 @@ void affinity_state_destroy(AffinityState *s) { delete s; }
 
 void affinity_last_ms(const AffinityState *s, double out[2]) { range_last_ms<DevAffRec>(s, out); }
 
-int affinity_run(AffinityState **state, int device, void *stream_, const Patterns &P, const ScanImage &img,
-                 const Batch &B, size_t r0, size_t r1, std::vector<tfbs_affinity> *out) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
+int affinity_prepare(AffinityState **state, int device, void *stream, const Patterns &P, uint32_t *n_strands) {
     HIP_TRY(hipSetDevice(device));
-    if (int rc = first_use(state, P, stream, 2, "affinity tables")) return rc;
-    AffinityState &S = **state;
+    if (int rc = first_use(state, P, static_cast<hipStream_t>(stream), 2, "affinity tables")) return rc;
+    *n_strands = (*state)->n_strands;
+    return TFBS_OK;
+}
+
+int affinity_region_check(const AffinityState *state, const Batch &B, size_t r, const RegionH &R) {
+    uint64_t longest = 0;
+    for (uint32_t h = 0; h < R.hap_count; h++) longest = std::max<uint64_t>(longest, B.haps[R.hap_begin + h].len);
+    if (longest * state->max_strands >= (1ull << 23))
+        return fail(TFBS_E_ARG, "region " + std::to_string(r) + ": its longest haplotype times the most strands of "
+                                    "one pattern_id reaches 2^23: an affinity sum could pass 2^63");
+    return TFBS_OK;
+}
+
+namespace {
+
+AffArgs aff_args(const AffinityState &S) {  // the kind's own arguments
     AffArgs A{};
     A.tables = S.tables.p;
     A.tops = S.tops.p;
+    return A;
+}
+
+}  // namespace
+
+int affinity_launch_chunk(AffinityState *state, void *stream, const ScanImage &img, const uint32_t *ids,
+                          const uint64_t *hap_off, size_t nh, uint64_t nrec, const uint64_t **d_hap_off,
+                          const DevAffRec **recs, double *kernel_ms) {
+    if (int rc = range_launch_chunk(*state, static_cast<hipStream_t>(stream), img, ids, hap_off, nh, nrec,
+                                    scan_affinity_kernel, aff_args(*state), kernel_ms))
+        return rc;
+    *d_hap_off = state->hap_off.p;
+    *recs = state->recs.p;
+    return TFBS_OK;
+}
+
+int affinity_run(AffinityState **state, int device, void *stream, const Patterns &P, const ScanImage &img,
+                 const Batch &B, size_t r0, size_t r1, std::vector<tfbs_affinity> *out) {
+    uint32_t n_strands = 0;
+    if (int rc = affinity_prepare(state, device, stream, P, &n_strands)) return rc;
+    AffinityState &S = **state;
     return range_run(
-        S, stream, img, B, r0, r1, "affinity", "TFBS_AFFINITY_SCRATCH_MB", scan_affinity_kernel, A,
-        [&](size_t r, const RegionH &R) {
-            uint64_t longest = 0;
-            for (uint32_t h = 0; h < R.hap_count; h++) longest = std::max<uint64_t>(longest, B.haps[R.hap_begin + h].len);
-            if (longest * S.max_strands >= (1ull << 23))
-                return fail(TFBS_E_ARG, "region " + std::to_string(r) + ": its longest haplotype times the most strands of "
-                                            "one pattern_id reaches 2^23: an affinity sum could pass 2^63");
-            return (int)TFBS_OK;
-        },
+        S, static_cast<hipStream_t>(stream), img, B, r0, r1, "affinity", "TFBS_AFFINITY_SCRATCH_MB", scan_affinity_kernel,
+        aff_args(S), [&](size_t r, const RegionH &R) { return affinity_region_check(&S, B, r, R); },
         [](const RegionH &, const DevHap &hm, uint32_t hap, uint32_t p, uint32_t x, const DevAffRec &q, tfbs_affinity &o) {
             o = tfbs_affinity{hm.region, hap, p, x, q.n_windows, q.n_nonzero, q.sum};
         },

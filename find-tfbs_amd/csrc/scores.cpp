@@ -16,6 +16,20 @@ std::string score_info(int64_t lo, int64_t hi, uint64_t zero, uint64_t one, uint
     return std::string(buf, (size_t)m);
 }
 
+void append_row_field(std::string &gts, uint64_t d, uint64_t spread, uint64_t (&cnt)[3]) {
+    uint32_t cls, t;
+    score_class(d, spread, &cls, &t);
+    cnt[cls]++;
+    if (d == 0) gts += "\t0|0:0.0";
+    else if (d == spread) gts += "\t1|1:2.0";
+    else {
+        char buf[16];
+        const int m = snprintf(buf, sizeof buf, "\t%s:%u.%04u", cls == 0 ? "0|0" : cls == 1 ? "0|1" : "1|1", t / 10000,
+                               t % 10000);
+        gts.append(buf, (size_t)m);
+    }
+}
+
 bool scores_as_genotypes(const int32_t *left, const int32_t *right, size_t n, uint64_t min_spread, uint32_t *maf,
                          std::string &info, std::string &gts) {
     if (n == 0) return false;
@@ -29,20 +43,7 @@ bool scores_as_genotypes(const int32_t *left, const int32_t *right, size_t n, ui
     if (spread == 0 || spread < min_spread) return false;
     uint64_t cnt[3] = {0, 0, 0};
     gts.reserve(gts.size() + n * 11);
-    for (size_t i = 0; i < n; i++) {
-        const uint64_t d = (uint64_t)((int64_t)left[i] + right[i] - lo);
-        uint32_t cls, t;
-        score_class(d, spread, &cls, &t);
-        cnt[cls]++;
-        if (d == 0) gts += "\t0|0:0.0";
-        else if (d == spread) gts += "\t1|1:2.0";
-        else {
-            char buf[16];
-            const int m = snprintf(buf, sizeof buf, "\t%s:%u.%04u", cls == 0 ? "0|0" : cls == 1 ? "0|1" : "1|1",
-                                   t / 10000, t % 10000);
-            gts.append(buf, (size_t)m);
-        }
-    }
+    for (size_t i = 0; i < n; i++) append_row_field(gts, (uint64_t)((int64_t)left[i] + right[i] - lo), spread, cnt);
     *maf = (uint32_t)maf_of(cnt[0], cnt[1], cnt[2]);
     info += score_info(lo, hi, cnt[0], cnt[1], cnt[2]);
     return true;

@@ -39,6 +39,10 @@ std::string strip_chr(const std::string &c);
 // The row's INFO value: "SCORES=<lo>,<hi>;freqs=<zero>/<one>/<two>".
 std::string score_info(int64_t lo, int64_t hi, uint64_t zero, uint64_t one, uint64_t two);
 
+// A sample's field from d = x - lo appended to gts ("\t0|0:0.0", "\t1|1:2.0" or 11 bytes), its
+// class counted: the score rows' and the affinity rows' host definitions share it.
+void append_row_field(std::string &gts, uint64_t d, uint64_t spread, uint64_t (&cnt)[3]);
+
 // The specification on one candidate row's per-sample values (left[s], right[s]: the two
 // haplotypes' best scores): true and info / gts appended when the row exists (n > 0,
 // spread > 0, spread >= min_spread); *maf set.

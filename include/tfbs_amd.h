@@ -1111,6 +1111,57 @@ int tfbs_batch_score_rows(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, co
  * scratch chunks), out[3] the copy-back and host part (wall). */
 int tfbs_ctx_last_scores_ms(const tfbs_ctx *ctx, double out[4]);
 
+/* ------------------------------------------------------------------ */
+/* Affinity rows: per-sample log2 binding affinity as a second VCF      */
+/* ------------------------------------------------------------------ */
+/* The third measure of how a sample binds, added up over the sample: keys are the score rows'
+ * (a (bed, non-empty inner range) pair, taken once, in the order inner start, inner end, bed;
+ * under it pattern_id ascends).  The value of distinct haplotype h for pattern id q under a key
+ * is the affinity TSV's: A(h) = the sum of `sum` over q's strands, N(h) = the sum of n_windows;
+ * N == 0 is "none".  A candidate row (key, q) writes no row when a haplotype that a sample
+ * carries is "none".  Otherwise sample s with haplotypes a = memb[2s], b = memb[2s + 1] has
+ * x_s = A(a) + A(b) (u64; each term is below 2^63 by tfbs_batch_affinity's refusal) and
+ *     y_s = mlog2(x_s),  mlog2(x) = floor(1000 * log2(x)) for x >= 1 (0 .. 63999),  mlog2(0) = -1
+ * (the monotone extension: x = 0 with N > 0 is real, every window beyond the weight's cutoff).
+ * lo = min y, hi = max y, spread = hi - lo (at most 64000).  No row when n_samples == 0,
+ * spread == 0 or spread < min_spread (milli-bits; 0 counts as 1).  With d = y_s - lo the class,
+ * t and the 8- or 11-byte field are the score rows'; maf is their rule on the three counts and
+ * the row is written iff maf >= min_maf, as
+ *   <chr>\t<POS>\t<bed>,<name>,<start>-<end>\t.\t.\t.\tPASS\tLOG2AFF=<lo>,<hi>;AFF=<xlo>,<xhi>;TOP=<top>;freqs=<zero>/<one>/<two>\tGT:DS<fields>\n
+ * xlo / xhi the exact minimum and maximum of x in unsigned decimal (lo = mlog2(xlo), hi =
+ * mlog2(xhi)), top tfbs_patterns_affinity_tops' value of q; <chr>, <name> and POS as in the score
+ * rows.  Back to nats: ln(affinity_s) ~ top / 1000 + ln 2 * ((lo + DS / 2 * spread) / 1000 - 40).
+ *
+ * mlog2 is exact: with e = bitlen(x) - 1 and xn = x << (63 - e) it is 1000 e + max{j : P[j] <= xn}
+ * over P[j] = ceil(2^63 * 2^(j / 1000)), 1 000 u64 written by tools/gen_affinity_tables.py with an
+ * exact integer 1000th root.  out[i] = mlog2(x[i]); device -1 computes on the host, >= 0 with one
+ * launch of the statistics kernel's own function on that HIP device. */
+int tfbs_affinity_mlog2(const uint64_t *x, size_t n, int device, int32_t *out);
+/* Host only: the definition on one candidate row's per-sample values (left[s], right[s] = A of
+ * the sample's two haplotypes).  1 = row (info = "LOG2AFF=...;AFF=...;TOP=...;freqs=...",
+ * genotypes = the fields, both 0-terminated), 0 = no row; TFBS_E_ARG when a value is 2^63 or
+ * more or a buffer is too short. */
+int tfbs_affinity_as_genotypes(const uint64_t *left, const uint64_t *right, size_t n, int32_t top, uint64_t min_spread,
+                               uint32_t *maf, char *info, size_t info_cap, char *genotypes, size_t gt_cap);
+/* The affinity rows of regions [r0, r1) of the batch resident on ctx: the arguments, the
+ * count-only form (text == NULL) and the TFBS_E_STATE / TFBS_E_ARG cases are
+ * tfbs_batch_score_rows'; a pattern set or a region that tfbs_batch_affinity refuses is refused
+ * here with the same code and message.  Needs no scan; leaves every scan / reduce / encode /
+ * rows / hits / best / affinity / scores / effects / mutscan result, their timers and the step
+ * graph untouched.  The work runs on the device (affinity_rows.hip): the affinity kernel's
+ * records are folded to (A, none) where they lie, a row's statistics and logarithms come from
+ * the region's distinct haplotype pairs, and the score rows' text kernel writes the fields; the
+ * text equals tfbs_affinity_as_genotypes' byte for byte.  Device scratch is bounded by
+ * TFBS_AFFINITY_ROWS_SCRATCH_MB (default 256, fractions allowed, read at the call; at least one
+ * region's records and one row's text); the result does not depend on it. */
+int tfbs_batch_affinity_rows(tfbs_ctx *ctx, tfbs_batch *b, size_t r0, size_t r1, const char *chromosome,
+                             uint32_t min_maf, uint64_t min_spread, uint32_t *fake_position, char **text, size_t *len,
+                             uint64_t *n_rows);
+/* The last tfbs_batch_affinity_rows' times (ms): out[0] the affinity kernel, out[1] the fold and
+ * statistics kernels, out[2] the text kernel (HIP events on the ctx stream, summed over the
+ * scratch chunks), out[3] the copy-back and host part (wall). */
+int tfbs_ctx_last_affinity_rows_ms(const tfbs_ctx *ctx, double out[4]);
+
 void tfbs_free(void *p);
 
 /* counts_as_genotypes alone (main.rs:439-498): 1 = row (strings written), 0 = no variation. */
@@ -1187,6 +1238,12 @@ typedef struct tfbs_run_ext {
                                        (tfbs_batch_affinity_tsv under TFBS_AFFINITY_HEADER), NULL = none: the run
                                        does nothing more than without it */
     int affinity_mode;              /* --affinity_mode: TFBS_AFFINITY_ALL / TFBS_AFFINITY_DIFF */
+    const char *affinity_rows_output;   /* --affinity_rows_output: the batches' affinity rows
+                                           (tfbs_batch_affinity_rows) as a further BGZF VCF under the main output's
+                                           #CHROM line, POS from 1 on a chain of its own, min_maf as the main rows';
+                                           NULL = none: the run does nothing more than without it */
+    uint64_t affinity_rows_min_spread;  /* --affinity_rows_min_spread: tfbs_batch_affinity_rows' min_spread
+                                           (milli-bits; 0 counts as 1) */
 } tfbs_run_ext;
 int tfbs_run_ex(const tfbs_run_args *args, const tfbs_run_ext *ext);
 
