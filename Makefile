@@ -8,7 +8,7 @@ LIBDIR := $(PKG)/lib
 OBJDIR := $(PKG)/lib/obj
 JOBS ?= 8
 
-HOST_SRCS := $(SRC)/patterns.cpp $(SRC)/plan.cpp $(SRC)/plan_dinuc.cpp $(SRC)/mfma.cpp $(SRC)/batch.cpp $(SRC)/group_host.cpp $(SRC)/aggregate.cpp $(SRC)/hits.cpp $(SRC)/best.cpp $(SRC)/scores.cpp $(SRC)/effects.cpp $(SRC)/mutscan.cpp $(SRC)/synth.cpp $(SRC)/score_dist.cpp $(SRC)/io.cpp $(SRC)/inflate.cpp $(SRC)/run.cpp $(SRC)/affinity.cpp
+HOST_SRCS := $(SRC)/patterns.cpp $(SRC)/plan.cpp $(SRC)/plan_dinuc.cpp $(SRC)/mfma.cpp $(SRC)/batch.cpp $(SRC)/group_host.cpp $(SRC)/aggregate.cpp $(SRC)/hits.cpp $(SRC)/best.cpp $(SRC)/scores.cpp $(SRC)/effects.cpp $(SRC)/mutscan.cpp $(SRC)/synth.cpp $(SRC)/score_dist.cpp $(SRC)/io.cpp $(SRC)/inflate.cpp $(SRC)/run.cpp $(SRC)/io_capi.cpp $(SRC)/affinity.cpp
 HIP_SRCS := $(SRC)/ctx.hip $(SRC)/ctx_scan.hip $(SRC)/ctx_assembly.hip $(SRC)/ctx_encode.hip $(SRC)/ctx_rows.hip $(SRC)/ctx_outputs.hip $(SRC)/pinned.hip $(SRC)/scan_kernels.hip $(SRC)/scan_dinuc.hip $(SRC)/scan_hits.hip $(SRC)/scan_best.hip $(SRC)/score_rows.hip $(SRC)/scan_effects.hip $(SRC)/scan_mutscan.hip $(SRC)/scan_mfma.hip $(SRC)/window_lists.hip $(SRC)/key_kernels.hip $(SRC)/bgzf_gpu.hip $(SRC)/build_gpu.hip $(SRC)/score_dist.hip $(SRC)/scan_affinity.hip $(SRC)/affinity_rows.hip
 HDRS := $(wildcard $(SRC)/*.hpp) include/tfbs_amd.h
 HOST_OBJS := $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))

@@ -964,21 +964,50 @@ class RegionBatch:
         """tfbs_batch_upload: the packed batch resident on the scanner (what hits() needs)."""
         check(lib().tfbs_batch_upload(scanner.h, self.h))
 
+    def _span(self, r0, r1):
+        return 0 if r0 is None else r0, self.num_regions if r1 is None else r1
+
+    def _records(self, call, ctype, dtype, *args):
+        """A record call's malloc'd array of ctype (call(*args, &p, &n)) as a numpy structured array."""
+        import numpy as np
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(call(*args, C.byref(p), C.byref(n)))
+        try:
+            return np.frombuffer(C.string_at(p, n.value * C.sizeof(ctype)), dtype=dtype).copy()
+        finally:
+            lib().tfbs_free(p)
+
+    def _tsv(self, call, arr, dtype, header_text, header, *args):
+        """A *_tsv call's text for the records arr (call(batch, records, n, *args, &p, &n))."""
+        import numpy as np
+        arr = np.ascontiguousarray(arr, dtype=dtype)
+        p = C.c_void_p()
+        n = C.c_size_t()
+        check(call(self.h, arr.ctypes.data_as(C.c_void_p), len(arr), *args, C.byref(p), C.byref(n)))
+        try:
+            text = C.string_at(p, n.value).decode()
+        finally:
+            lib().tfbs_free(p)
+        return (header_text if header else "") + text
+
+    def _by_sample(self, recs, region, field, what):
+        """(recs[field], recs["n_windows"]) of one region as [2 * n_samples][n_patterns][n_ranges]."""
+        import numpy as np
+        mine = recs[recs["region"] == region]
+        nh, nr = self.region_stats(region)[0], len(self.ranges(region))
+        npat = len(mine) // (nh * nr) if nh * nr else 0
+        if npat * nh * nr != len(mine) or (nh * nr and npat != len(self.patterns)):
+            raise ValueError("%s does not hold region %d in full" % (what, region))
+        memb = np.asarray(self.membership(region), dtype=np.int64)
+        return mine[field].reshape(nh, npat, nr)[memb], mine["n_windows"].reshape(nh, npat, nr)[memb]
+
     def hits(self, scanner, r0=0, r1=None):
         """tfbs_batch_hits: find_all_matches (main.rs:94-154) for regions [r0, r1) of this batch,
         resident on the scanner (after an upload; no scan needed): a numpy structured array
         (HIT_DTYPE: region, haplotype, pattern, window, start, end, score) sorted by (region,
         haplotype, pattern, window)."""
-        import numpy as np
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_hits(scanner.h, self.h, r0, self.num_regions if r1 is None else r1, C.byref(p),
-                                    C.byref(n)))
-        try:
-            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_hit)), dtype=HIT_DTYPE).copy()
-        finally:
-            lib().tfbs_free(p)
-        return out
+        return self._records(lib().tfbs_batch_hits, _capi.tfbs_hit, HIT_DTYPE, scanner.h, self.h, *self._span(r0, r1))
 
     def hits_count(self, scanner, r0=0, r1=None):
         """tfbs_batch_hits_count: the hits of each region of [r0, r1) (numpy uint64), count pass only."""
@@ -1011,33 +1040,14 @@ class RegionBatch:
         """tfbs_batch_hits_tsv: the TSV of a hits() result over whole regions; mode "all" (one
         `hit` line per hit) or "diff" (every region of the batch: `hap` lines, the baseline's
         `base` lines, the others' `gain` / `loss` lines); header: HITS_HEADER first."""
-        import numpy as np
-        hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_hits_tsv(self.h, hits.ctypes.data_as(C.c_void_p), len(hits), _u(chromosome),
-                                        HITS_MODES[mode], C.byref(p), C.byref(n)))
-        try:
-            text = C.string_at(p, n.value).decode()
-        finally:
-            lib().tfbs_free(p)
-        return (HITS_HEADER if header else "") + text
+        return self._tsv(lib().tfbs_batch_hits_tsv, hits, HIT_DTYPE, HITS_HEADER, header, _u(chromosome), HITS_MODES[mode])
 
     def best(self, scanner, r0=None, r1=None):
         """tfbs_batch_best: the best-scoring site per (distinct haplotype, pattern strand, inner
         range) of regions [r0, r1) of this batch, resident on the scanner (after an upload; no
         scan needed): a dense numpy structured array (BEST_DTYPE) sorted by (region, haplotype,
         pattern, range); a region's block reshapes to [n_haplotypes][n_patterns][n_ranges]."""
-        import numpy as np
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_best(scanner.h, self.h, 0 if r0 is None else r0,
-                                    self.num_regions if r1 is None else r1, C.byref(p), C.byref(n)))
-        try:
-            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_best)), dtype=BEST_DTYPE).copy()
-        finally:
-            lib().tfbs_free(p)
-        return out
+        return self._records(lib().tfbs_batch_best, _capi.tfbs_best, BEST_DTYPE, scanner.h, self.h, *self._span(r0, r1))
 
     def score_rows(self, scanner, chromosome, min_maf=0, min_spread=1, fake_position=1, r0=None, r1=None):
         """tfbs_batch_score_rows: the score rows of regions [r0, r1) of this batch, resident on the
@@ -1083,32 +1093,13 @@ class RegionBatch:
         """tfbs_batch_best_tsv: the TSV of a best() result over whole regions; mode "all" (one
         `best` line per (key, pattern_id, haplotype)) or "diff" (`hap` lines, then `base` and
         `alt` lines where a haplotype's best differs from the baseline's); header: BEST_HEADER first."""
-        import numpy as np
-        best = np.ascontiguousarray(best, dtype=BEST_DTYPE)
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_best_tsv(self.h, best.ctypes.data_as(C.c_void_p), len(best), _u(chromosome),
-                                        BEST_MODES[mode], C.byref(p), C.byref(n)))
-        try:
-            text = C.string_at(p, n.value).decode()
-        finally:
-            lib().tfbs_free(p)
-        return (BEST_HEADER if header else "") + text
+        return self._tsv(lib().tfbs_batch_best_tsv, best, BEST_DTYPE, BEST_HEADER, header, _u(chromosome), BEST_MODES[mode])
 
     def best_by_sample(self, best, region):
         """(scores, n_windows): int32 / uint32 arrays [2 * n_samples][n_patterns][n_ranges] of one
         region, row id = the records of the distinct haplotype that haplotype id 2 * sample + side
         carries (membership); `best` must hold that region in full."""
-        import numpy as np
-        mine = best[best["region"] == region]
-        nh, nr = self.region_stats(region)[0], len(self.ranges(region))
-        npat = len(mine) // (nh * nr) if nh * nr else 0
-        if npat * nh * nr != len(mine) or (nh * nr and npat != len(self.patterns)):
-            raise ValueError("best does not hold region %d in full" % region)
-        memb = np.asarray(self.membership(region), dtype=np.int64)
-        scores = mine["score"].reshape(nh, npat, nr)
-        counts = mine["n_windows"].reshape(nh, npat, nr)
-        return scores[memb], counts[memb]
+        return self._by_sample(best, region, "score", "best")
 
     def affinity(self, scanner, r0=None, r1=None):
         """tfbs_batch_affinity: the total binding affinity per (distinct haplotype, pattern strand,
@@ -1116,47 +1107,21 @@ class RegionBatch:
         scan needed): a dense numpy structured array (AFFINITY_DTYPE) sorted by (region, haplotype,
         pattern, range); `sum` is the exact integer sum of affinity_weight(top - score) over the
         range's windows."""
-        import numpy as np
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_affinity(scanner.h, self.h, 0 if r0 is None else r0,
-                                        self.num_regions if r1 is None else r1, C.byref(p), C.byref(n)))
-        try:
-            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_affinity)), dtype=AFFINITY_DTYPE).copy()
-        finally:
-            lib().tfbs_free(p)
-        return out
+        return self._records(lib().tfbs_batch_affinity, _capi.tfbs_affinity, AFFINITY_DTYPE, scanner.h, self.h,
+                             *self._span(r0, r1))
 
     def affinity_tsv(self, aff, chromosome, mode="diff", header=False):
         """tfbs_batch_affinity_tsv: the TSV of an affinity() result over whole regions; mode "all"
         (one `aff` line per (key, pattern_id, haplotype)) or "diff" (`hap` lines, then `base` and
         `alt` lines where a haplotype's sum differs from the baseline's); header: AFFINITY_HEADER first."""
-        import numpy as np
-        aff = np.ascontiguousarray(aff, dtype=AFFINITY_DTYPE)
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_affinity_tsv(self.h, aff.ctypes.data_as(C.c_void_p), len(aff), _u(chromosome),
-                                            AFFINITY_MODES[mode], C.byref(p), C.byref(n)))
-        try:
-            text = C.string_at(p, n.value).decode()
-        finally:
-            lib().tfbs_free(p)
-        return (AFFINITY_HEADER if header else "") + text
+        return self._tsv(lib().tfbs_batch_affinity_tsv, aff, AFFINITY_DTYPE, AFFINITY_HEADER, header, _u(chromosome),
+                         AFFINITY_MODES[mode])
 
     def affinity_by_sample(self, aff, region):
         """(sums, n_windows): uint64 / uint32 arrays [2 * n_samples][n_patterns][n_ranges] of one
         region, row id = the records of the distinct haplotype that haplotype id 2 * sample + side
         carries (membership); `aff` must hold that region in full."""
-        import numpy as np
-        mine = aff[aff["region"] == region]
-        nh, nr = self.region_stats(region)[0], len(self.ranges(region))
-        npat = len(mine) // (nh * nr) if nh * nr else 0
-        if npat * nh * nr != len(mine) or (nh * nr and npat != len(self.patterns)):
-            raise ValueError("aff does not hold region %d in full" % region)
-        memb = np.asarray(self.membership(region), dtype=np.int64)
-        sums = mine["sum"].reshape(nh, npat, nr)
-        counts = mine["n_windows"].reshape(nh, npat, nr)
-        return sums[memb], counts[memb]
+        return self._by_sample(aff, region, "sum", "aff")
 
     def variants(self, region):
         """tfbs_batch_region_variant: the region's records in BCF order as (pos, ref, alt, n_alleles,
@@ -1184,32 +1149,14 @@ class RegionBatch:
         the record on the REF and on the ALT allele, on a scanner made from this batch's patterns
         (no upload, no scan needed): a dense numpy structured array (EFFECT_DTYPE) sorted by
         (region, variant, pattern); a region's block reshapes to [n_variants][n_patterns]."""
-        import numpy as np
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_effects(scanner.h, self.h, 0 if r0 is None else r0,
-                                       self.num_regions if r1 is None else r1, C.byref(p), C.byref(n)))
-        try:
-            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_effect)), dtype=EFFECT_DTYPE).copy()
-        finally:
-            lib().tfbs_free(p)
-        return out
+        return self._records(lib().tfbs_batch_effects, _capi.tfbs_effect, EFFECT_DTYPE, scanner.h, self.h, *self._span(r0, r1))
 
     def effects_tsv(self, eff, chromosome, mode="sites", header=False):
         """tfbs_batch_effects_tsv: the TSV of an effects() result over whole regions; per record a
         `var` line, then per pattern strand mode "sites": its `gain`, `loss` and `change` lines, or
         "all": `same` and `none` lines too; header: EFFECTS_HEADER first."""
-        import numpy as np
-        eff = np.ascontiguousarray(eff, dtype=EFFECT_DTYPE)
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_effects_tsv(self.h, eff.ctypes.data_as(C.c_void_p), len(eff), _u(chromosome),
-                                           EFFECT_MODES[mode], C.byref(p), C.byref(n)))
-        try:
-            text = C.string_at(p, n.value).decode()
-        finally:
-            lib().tfbs_free(p)
-        return (EFFECTS_HEADER if header else "") + text
+        return self._tsv(lib().tfbs_batch_effects_tsv, eff, EFFECT_DTYPE, EFFECTS_HEADER, header, _u(chromosome),
+                         EFFECT_MODES[mode])
 
     def mutscan(self, scanner, r0=None, r1=None, kinds=MUT_SITES):
         """tfbs_batch_mutscan: per (pattern strand, column of the region's reference window, other
@@ -1217,17 +1164,8 @@ class RegionBatch:
         and the record's kind, for the kinds in the mask, on a scanner made from this batch's patterns
         (no upload, no scan needed; needs keep_variants): a sparse numpy structured array
         (MUTATION_DTYPE) sorted by (region, pattern, column, alt)."""
-        import numpy as np
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_mutscan(scanner.h, self.h, 0 if r0 is None else r0,
-                                       self.num_regions if r1 is None else r1, mutscan_kinds_mask(kinds), C.byref(p),
-                                       C.byref(n)))
-        try:
-            out = np.frombuffer(C.string_at(p, n.value * C.sizeof(_capi.tfbs_mutation)), dtype=MUTATION_DTYPE).copy()
-        finally:
-            lib().tfbs_free(p)
-        return out
+        return self._records(lib().tfbs_batch_mutscan, _capi.tfbs_mutation, MUTATION_DTYPE, scanner.h, self.h,
+                             *self._span(r0, r1), mutscan_kinds_mask(kinds))
 
     def mutscan_count(self, scanner, r0=None, r1=None, kinds=MUT_SITES):
         """tfbs_batch_mutscan_count: len(mutscan(...)) from the count pass alone."""
@@ -1240,17 +1178,7 @@ class RegionBatch:
     def mutscan_tsv(self, m, chromosome, header=False):
         """tfbs_batch_mutscan_tsv: one line per record of a mutscan() result (any subset, in its
         order); header: MUTSCAN_HEADER first."""
-        import numpy as np
-        m = np.ascontiguousarray(m, dtype=MUTATION_DTYPE)
-        p = C.c_void_p()
-        n = C.c_size_t()
-        check(lib().tfbs_batch_mutscan_tsv(self.h, m.ctypes.data_as(C.c_void_p), len(m), _u(chromosome), C.byref(p),
-                                           C.byref(n)))
-        try:
-            text = C.string_at(p, n.value).decode()
-        finally:
-            lib().tfbs_free(p)
-        return (MUTSCAN_HEADER if header else "") + text
+        return self._tsv(lib().tfbs_batch_mutscan_tsv, m, MUTATION_DTYPE, MUTSCAN_HEADER, header, _u(chromosome))
 
     def rows(self, chromosome, min_maf=0, fake_position=1):
         """Rows for every region (main.rs:415-429); returns (text, next fake_position)."""
@@ -1367,42 +1295,18 @@ def run(chromosome, bcf, bed_files, reference_genome_file, wanted_samples, pwm_f
     bo = _u(best_output) if best_output is not None else None
     a.best_output = bo
     a.best_mode = BEST_MODES[best_mode]
-    mo = _u(mutscan_output) if mutscan_output is not None else None
-    ao = _u(affinity_output) if affinity_output is not None else None
-    aro = _u(affinity_rows_output) if affinity_rows_output is not None else None
-    if affinity_rows_output is not None:
-        x = _capi.tfbs_run_ext_affinity_rows()
-        x.pwm_pvalue = pwm_pvalue or 0.0
-        x.mutscan_output = mo
-        x.mutscan_kinds = mutscan_kinds_mask(mutscan_kinds)
-        x.affinity_output = ao
-        x.affinity_mode = AFFINITY_MODES[affinity_mode]
-        x.affinity_rows_output = aro
-        x.affinity_rows_min_spread = affinity_rows_min_spread
-    elif affinity_output is not None:
-        x = _capi.tfbs_run_ext_affinity()
-        x.pwm_pvalue = pwm_pvalue or 0.0
-        x.mutscan_output = mo
-        x.mutscan_kinds = mutscan_kinds_mask(mutscan_kinds)
-        x.affinity_output = ao
-        x.affinity_mode = AFFINITY_MODES[affinity_mode]
-    elif mutscan_output is not None:
-        x = _capi.tfbs_run_ext_mutscan()
-        x.pwm_pvalue = pwm_pvalue or 0.0
-        x.mutscan_output = mo
-        x.mutscan_kinds = mutscan_kinds_mask(mutscan_kinds)
-    elif pwm_pvalue is None:
-        x = _capi.tfbs_run_ext_scores()
-    else:
-        x = _capi.tfbs_run_ext_pvalue()
-        x.pwm_pvalue = pwm_pvalue
+    # the full tfbs_run_ext layout whatever is asked for (the shorter ones of _capi serve older callers)
+    x = _capi.tfbs_run_ext_affinity_rows()
     x.size = C.sizeof(x)
-    so = _u(scores_output) if scores_output is not None else None
-    x.scores_output = so
-    x.scores_min_spread = scores_min_spread
-    eo = _u(effects_output) if effects_output is not None else None
-    x.effects_output = eo
+    opt = [_u(v) if v is not None else None for v in (effects_output, scores_output, mutscan_output, affinity_output,
+                                                      affinity_rows_output)]
+    x.effects_output, x.scores_output, x.mutscan_output, x.affinity_output, x.affinity_rows_output = opt
     x.effects_mode = EFFECT_MODES[effects_mode]
+    x.scores_min_spread = scores_min_spread
+    x.pwm_pvalue = pwm_pvalue or 0.0
+    x.mutscan_kinds = mutscan_kinds_mask(mutscan_kinds)
+    x.affinity_mode = AFFINITY_MODES[affinity_mode]
+    x.affinity_rows_min_spread = affinity_rows_min_spread
     check(lib().tfbs_run_ex(C.byref(a), C.byref(x)))
 
 

@@ -12,7 +12,7 @@
 #include "affinity_log_table.hpp"
 #include "affinity_rows.hpp"
 #include "affinity_tables.hpp"
-#include "hits.hpp"
+#include "key_tsv.hpp"
 #include "score_dist.hpp"
 
 namespace tfbs {
@@ -91,46 +91,32 @@ bool affinity_as_genotypes(const uint64_t *left, const uint64_t *right, size_t n
 
 namespace {
 
-struct Value {  // of (haplotype, pattern_id, key): the fold over the pattern_id's strands
-    uint64_t a = 0, n = 0;
-    bool none() const { return n == 0; }
-};
-
-Value value_of(const tfbs_affinity *hap_block, const std::vector<uint32_t> &strands, uint32_t nr, uint32_t slot) {
-    Value v;
-    for (uint32_t p : strands) {
-        const tfbs_affinity &x = hap_block[(size_t)p * nr + slot];
-        v.a += x.sum;
-        v.n += x.n_windows;
+struct AffinityPolicy {
+    using Rec = tfbs_affinity;
+    struct Value {  // the sums over the pattern_id's strands
+        uint64_t a = 0, n = 0;
+        bool none() const { return n == 0; }
+    };
+    static constexpr const char *word = "affinity", *all_kind = "aff", *hap_dots = "\t.\t.\t.\t.\t";
+    std::vector<int32_t> tops;
+    Value value_of(const tfbs_affinity *hap_block, const std::vector<uint32_t> &strands, uint32_t nr, uint32_t slot) const {
+        Value v;
+        for (uint32_t p : strands) {
+            const tfbs_affinity &x = hap_block[(size_t)p * nr + slot];
+            v.a += x.sum;
+            v.n += x.n_windows;
+        }
+        return v;
     }
-    return v;
-}
-
-inline bool differs(const Value &a, const Value &b) { return a.none() != b.none() || a.a != b.a; }
-
-struct AffLine {
-    std::string &out;
-    const std::string &chrom;
-    const Batch &B;
-    char region[48];
-    void hap(uint32_t h, uint32_t carriers, const std::string &ids) {
-        char buf[64];
-        tsv_key_head(out, chrom, region, B, nullptr, nullptr);
-        out.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%u\t%u\thap\t.\t.\t.\t.\t", h, carriers));
-        out += ids;
-        out += '\n';
-    }
-    void value(const InnerKey &k, const Pat &first, uint32_t h, uint32_t carriers, const char *kind, int32_t top,
-               const Value &v, const Value *base) {
-        char buf[160];
-        tsv_key_head(out, chrom, region, B, &k, &first);
-        out.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%u\t%u\t%s\t%d\t", h, carriers, kind, top));
+    bool differs(const Value &a, const Value &b) const { return a.none() != b.none() || a.a != b.a; }
+    void columns(std::string &out, const Batch &, uint32_t first, const Value &v, const Value *base) const {
+        char buf[96];
+        out.append(buf, (size_t)snprintf(buf, sizeof buf, "%d\t", tops[first]));
         if (!v.none()) out.append(buf, (size_t)snprintf(buf, sizeof buf, "%" PRIu64 "\t%" PRIu64 "\t", v.n, v.a));
         else out += ".\t.\t";
         if (base && !v.none() && !base->none())
             out.append(buf, (size_t)snprintf(buf, sizeof buf, "%" PRId64, (int64_t)(v.a - base->a)));
         else out += '.';
-        out += "\t.\n";
     }
 };
 
@@ -140,70 +126,9 @@ int affinity_tsv(const Batch &B, const tfbs_affinity *aff, size_t n, const std::
                  std::string &out) {
     if (mode != TFBS_AFFINITY_ALL && mode != TFBS_AFFINITY_DIFF)
         return fail(TFBS_E_ARG, "affinity mode is TFBS_AFFINITY_ALL or TFBS_AFFINITY_DIFF");
-    const Patterns &P = *B.pats;
-    const uint32_t np = (uint32_t)P.pats.size();
-    std::vector<int32_t> tops;
-    if (int rc = affinity_tops(P, &tops)) return rc;
-    std::map<uint16_t, std::vector<uint32_t>> by_pid;  // ascending pattern_id -> its strands in creation order
-    for (uint32_t p = 0; p < np; p++) by_pid[P.pats[p].pattern_id].push_back(p);
-    AffLine L{out, chrom, B, {0}};
-    size_t at = 0;
-    uint32_t prev = 0;
-    bool any = false;
-    while (at < n) {
-        const uint32_t r = aff[at].region;
-        if (r >= B.rh.size() || (any && r <= prev))
-            return fail(TFBS_E_ARG, "affinity records: regions not ascending inside the batch");
-        any = true;
-        prev = r;
-        const RegionH &R = B.rh[r];
-        const uint32_t U = R.hap_count, nr = (uint32_t)R.ranges.size();
-        const size_t block = (size_t)U * np * nr;
-        if (block == 0 || n - at < block) return fail(TFBS_E_ARG, "affinity records: not a whole region");
-        const tfbs_affinity *blk = aff + at;
-        size_t x = 0;
-        for (uint32_t h = 0; h < U; h++)  // dense and sorted: the block reshapes to [h][p][k]
-            for (uint32_t p = 0; p < np; p++)
-                for (uint32_t k = 0; k < nr; k++, x++)
-                    if (blk[x].region != r || blk[x].haplotype != h || blk[x].pattern != p || blk[x].range != k)
-                        return fail(TFBS_E_ARG,
-                                    "affinity records: not a whole region sorted by (haplotype, pattern, range)");
-        at += block;
-        snprintf(L.region, sizeof L.region, "%" PRIu64 "-%" PRIu64, R.ms, R.me);
-        auto val = [&](uint32_t h, const std::vector<uint32_t> &strands, const InnerKey &k) {
-            return value_of(blk + (size_t)h * np * nr, strands, nr, (uint32_t)k.slot);
-        };
-        auto carriers = [&](uint32_t h) { return B.hap_carriers[R.hap_begin + h]; };
-        uint32_t base = 0;
-        if (mode == TFBS_AFFINITY_DIFF) {
-            std::vector<std::vector<uint32_t>> ids;
-            if (int rc = region_baseline(B, R, ids, &base)) return rc;
-            for (uint32_t h = 0; h < U; h++) L.hap(h, carriers(h), carrier_id_text(B, ids, h, base));
-        }
-        for (const InnerKey &k : R.keys) {  // sorted by (s, e, bed): the rows' order; each once
-            if (k.slot < 0) continue;       // an empty inner range
-            for (const auto &ps : by_pid) {
-                const Pat &first = P.pats[ps.second[0]];
-                const int32_t top = tops[ps.second[0]];
-                if (mode == TFBS_AFFINITY_ALL) {
-                    for (uint32_t h = 0; h < U; h++)
-                        L.value(k, first, h, carriers(h), "aff", top, val(h, ps.second, k), nullptr);
-                    continue;
-                }
-                const Value vb = val(base, ps.second, k);
-                bool wrote = false;
-                for (uint32_t h = 0; h < U; h++) {
-                    if (h == base) continue;
-                    const Value vh = val(h, ps.second, k);
-                    if (!differs(vh, vb)) continue;
-                    if (!wrote) L.value(k, first, base, carriers(base), "base", top, vb, nullptr);
-                    wrote = true;
-                    L.value(k, first, h, carriers(h), "alt", top, vh, &vb);
-                }
-            }
-        }
-    }
-    return TFBS_OK;
+    AffinityPolicy pol;
+    if (int rc = affinity_tops(*B.pats, &pol.tops)) return rc;
+    return key_tsv(pol, B, aff, n, chrom, mode == TFBS_AFFINITY_DIFF, out);
 }
 
 }  // namespace tfbs

@@ -63,6 +63,14 @@ static void usage() {
             "  --min_maf applies.\n");
 }
 
+// A flag that takes one of two words: the word's code, or the error and exit status 2.
+static int mode_flag(const char *name, const std::string &value, const char *word0, int code0, const char *word1, int code1) {
+    if (value == word0) return code0;
+    if (value == word1) return code1;
+    fprintf(stderr, "error: %s is %s or %s\n", name, word0, word1);
+    exit(2);
+}
+
 int main(int argc, char **argv) {
     tfbs_run_args a;
     memset(&a, 0, sizeof a);
@@ -94,32 +102,11 @@ int main(int argc, char **argv) {
         else if (k == "--pwm_file" || k == "-p") a.pwm_file = val("--pwm_file");
         else if (k == "--dipwm_file") a.dipwm_file = val("--dipwm_file");
         else if (k == "--hits_output") a.hits_output = val("--hits_output");
-        else if (k == "--hits_mode") {
-            const std::string m = val("--hits_mode");
-            if (m != "all" && m != "diff") {
-                fprintf(stderr, "error: --hits_mode is all or diff\n");
-                return 2;
-            }
-            a.hits_mode = m == "all" ? TFBS_HITS_ALL : TFBS_HITS_DIFF;
-        }
+        else if (k == "--hits_mode") a.hits_mode = mode_flag("--hits_mode", val("--hits_mode"), "all", TFBS_HITS_ALL, "diff", TFBS_HITS_DIFF);
         else if (k == "--best_output") a.best_output = val("--best_output");
-        else if (k == "--best_mode") {
-            const std::string m = val("--best_mode");
-            if (m != "all" && m != "diff") {
-                fprintf(stderr, "error: --best_mode is all or diff\n");
-                return 2;
-            }
-            a.best_mode = m == "all" ? TFBS_BEST_ALL : TFBS_BEST_DIFF;
-        }
+        else if (k == "--best_mode") a.best_mode = mode_flag("--best_mode", val("--best_mode"), "all", TFBS_BEST_ALL, "diff", TFBS_BEST_DIFF);
         else if (k == "--effects_output") x.effects_output = val("--effects_output");
-        else if (k == "--effects_mode") {
-            const std::string m = val("--effects_mode");
-            if (m != "sites" && m != "all") {
-                fprintf(stderr, "error: --effects_mode is sites or all\n");
-                return 2;
-            }
-            x.effects_mode = m == "all" ? TFBS_EFFECTS_ALL : TFBS_EFFECTS_SITES;
-        }
+        else if (k == "--effects_mode") x.effects_mode = mode_flag("--effects_mode", val("--effects_mode"), "sites", TFBS_EFFECTS_SITES, "all", TFBS_EFFECTS_ALL);
         else if (k == "--mutscan_output") x.mutscan_output = val("--mutscan_output");
         else if (k == "--mutscan_kinds") {
             const std::string list = val("--mutscan_kinds");
@@ -140,14 +127,7 @@ int main(int argc, char **argv) {
             }
         }
         else if (k == "--affinity_output") x.affinity_output = val("--affinity_output");
-        else if (k == "--affinity_mode") {
-            const std::string m = val("--affinity_mode");
-            if (m != "all" && m != "diff") {
-                fprintf(stderr, "error: --affinity_mode is all or diff\n");
-                return 2;
-            }
-            x.affinity_mode = m == "all" ? TFBS_AFFINITY_ALL : TFBS_AFFINITY_DIFF;
-        }
+        else if (k == "--affinity_mode") x.affinity_mode = mode_flag("--affinity_mode", val("--affinity_mode"), "all", TFBS_AFFINITY_ALL, "diff", TFBS_AFFINITY_DIFF);
         else if (k == "--affinity_rows_output") x.affinity_rows_output = val("--affinity_rows_output");
         else if (k == "--affinity_rows_min_spread") {
             char *end = nullptr;

@@ -101,10 +101,6 @@ int best_run(BestState **state, int device, void *stream, const Patterns &P, con
              size_t r0, size_t r1, std::vector<tfbs_best> *out);
 // The last best_run's times (ms): the kernel (HIP events, summed over the chunks), copy-back + host part (wall).
 void best_last_ms(const BestState *s, double out[2]);
-// The first seven columns of a line of the best and the affinity TSV (best.cpp): chrom, region,
-// then bed / inner range / name / pattern_id, or "." for all five (k null: a `hap` line).
-void tsv_key_head(std::string &out, const std::string &chrom, const char *region, const Batch &B, const InnerKey *k,
-                  const Pat *p);
 // tfbs_batch_best_tsv's text appended to out (no header line); the records are whole regions.
 int best_tsv(const Batch &B, const tfbs_best *best, size_t n, const std::string &chrom, int mode, std::string &out);
 

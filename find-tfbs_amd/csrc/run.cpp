@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <map>
 #include <memory>
 #include <set>
@@ -36,6 +37,7 @@
 #include "io.hpp"
 #include "patterns.hpp"
 #include "rows.hpp"
+#include "run_order.hpp"
 
 namespace tfbs {
 int batch_row_bodies(const Batch &B, uint32_t min_maf, std::string &out, uint32_t threads);
@@ -97,16 +99,38 @@ struct Shard {
     double t_setup = 0, t_boot = 0, t_end = 0;  // readers + ctx + grouper; the first batches' stages; flush + ctx release
 };
 
-// --hits_output, --best_output, --effects_output, --affinity_output: the batches' texts (tfbs_batch_hits_tsv,
-// tfbs_batch_best_tsv, tfbs_batch_effects_tsv, tfbs_batch_affinity_tsv) written in batch order by the host BGZF writer, whichever shard hands them in first.
+double seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+struct ScopeTimer {  // adds the scope's seconds (from t0) to acc on every exit
+    double &acc;
+    double t0 = seconds();
+    ~ScopeTimer() { acc += seconds() - t0; }
+};
+
+// a switch in the environment: set to a number other than 0 / set to 0
+bool env_is_on(const char *name) {
+    const char *v = getenv(name);
+    return v && atoi(v);
+}
+bool env_is_off(const char *name) {
+    const char *v = getenv(name);
+    return v && atoi(v) == 0;
+}
+
+// A side output's file: the batches' texts written in batch order by the host BGZF writer,
+// whichever shard hands them in first.
 struct TextOut {
-    std::mutex mu;
     tfbs::BgzfWriter w;
-    std::string path;                       // written as path + ".part", renamed by finish()
-    std::map<size_t, std::string> pending;  // batches past `next`, waiting for their turn
-    size_t next = 0;
-    int rc = TFBS_OK;
+    std::string path;  // written as path + ".part", renamed by finish()
     std::string err;
+    struct Write {
+        TextOut *o;
+        int operator()(const char *p, size_t n) const {
+            const int e = o->w.write(p, n);
+            if (e) o->err = tfbs_last_error();
+            return e;
+        }
+    };
+    tfbs::InOrder<Write> seq{Write{this}};
     int open(const char *path_, uint32_t threads, const char *header) {
         path = path_;
         if (int e = w.open(path + ".part", threads)) return e;
@@ -119,65 +143,77 @@ struct TextOut {
         return TFBS_OK;
     }
     int submit(size_t g, std::string &&text) {
-        std::lock_guard<std::mutex> l(mu);
-        pending[g] = std::move(text);
-        for (auto it = pending.begin(); !rc && it != pending.end() && it->first == next; it = pending.erase(it), next++)
-            if ((rc = w.write(it->second.data(), it->second.size()))) err = tfbs_last_error();
-        return rc ? tfbs::fail(rc, err) : TFBS_OK;
+        const int e = seq.submit(g, std::move(text));
+        return e ? tfbs::fail(e, err) : TFBS_OK;
     }
 };
 
-// --scores_output: the batches' score rows (tfbs_batch_score_rows), a second VCF.  Batch g's
-// first POS is batch g - 1's plus its rows: a second chain as Ordered::chain, fed by the
-// count-only call as soon as a batch has counted its rows; the texts go out in batch order.
-// --affinity_rows_output (tfbs_batch_affinity_rows) is a second instance: a POS chain of its own.
-struct ScoresOut {
+// One side output of the run (--hits_output, --best_output, --effects_output, --mutscan_output,
+// --affinity_output, --scores_output, --affinity_rows_output): its file and what makes batch
+// g's text from the batch while its image is still resident.  Without its flag there is no
+// entry: the run does nothing more.
+struct SideOut {
     TextOut out;
-    uint64_t min_spread = 1;
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<int64_t> base;  // POS of batch g's first row, -1 unknown
-    bool failed = false;
-    void batches(size_t n) {
-        base.assign(n + 1, -1);
-        base[0] = 1;
-    }
-    int chain(size_t g, uint64_t n_rows, uint32_t *fake) {
-        std::unique_lock<std::mutex> l(mu);
-        cv.wait(l, [&] { return failed || base[g] >= 0; });
-        if (failed) return tfbs::fail(TFBS_E_STATE, "another device's shard failed");
-        *fake = (uint32_t)base[g];
-        base[g + 1] = base[g] + (int64_t)n_rows;
-        cv.notify_all();
-        return TFBS_OK;
-    }
-    void abort() {
-        std::lock_guard<std::mutex> l(mu);
-        failed = true;
-        cv.notify_all();
-    }
+    std::unique_ptr<tfbs::PosChain> chain;  // the two row outputs: a POS chain of their own, beside the main output's
+    bool keep_variants = false;             // its batches keep their variants (effects, mutscan)
+    std::function<int(tfbs_ctx *, tfbs_batch *, size_t g, std::string &text)> make;
 };
 
-// Best records (48 bytes each) the run flow holds at once: whole regions up to this many, one
-// region at least (the text does not depend on the split: tfbs_batch_best_tsv takes whole regions).
+// Records of a dense output the run flow holds at once: whole regions up to this many, one
+// region at least (the texts do not depend on the split: the *_tsv calls take whole regions).
+// Best records are 48 bytes each, effect records 72 (the mutation scan shares their limit),
+// affinity records 32.
 constexpr size_t kBestRunRecords = 1u << 20;
-// The same for effect records (72 bytes each; tfbs_batch_effects_tsv takes whole regions too).
 constexpr size_t kEffectsRunRecords = 1u << 20;
-// The same for affinity records (32 bytes each; tfbs_batch_affinity_tsv takes whole regions too).
 constexpr size_t kAffinityRunRecords = 1u << 20;
+
+// A record output's maker: fetch(ctx, batch, q0, q1, &recs, &n) then tsv(B, recs, n, text) over
+// slices of whole regions that hold at most `limit` records by records_of(B, r).
+template <class T, class Fetch, class Tsv, class RecordsOf>
+auto records_maker(Fetch fetch, Tsv tsv, RecordsOf records_of, size_t limit) {
+    return [=](tfbs_ctx *ctx, tfbs_batch *bb, size_t, std::string &text) {
+        const tfbs::Batch &B = bb->b;
+        return tfbs::for_whole_regions(
+            B.rh.size(), [&](size_t r) { return (size_t)records_of(B, r); }, limit, [&](size_t q0, size_t q1) {
+                T *recs = nullptr;
+                size_t n = 0;
+                if (int rc = fetch(ctx, bb, q0, q1, &recs, &n)) return rc;
+                std::unique_ptr<T, void (*)(void *)> guard(recs, free);
+                return tsv(B, recs, n, text);
+            });
+    };
+}
+
+// A row output's maker (rows: tfbs_batch_score_rows or tfbs_batch_affinity_rows): the batch's
+// rows counted, numbered from the output's chain as soon as they are, then made as text.
+auto rows_maker(decltype(&tfbs_batch_score_rows) rows, std::string label, tfbs::PosChain *chain, std::string chrom,
+                uint32_t min_maf, uint64_t min_spread) {
+    return [=](tfbs_ctx *ctx, tfbs_batch *bb, size_t g, std::string &text) {
+        const size_t n = bb->b.rh.size();
+        uint64_t n_rows = 0, n_text = 0;
+        uint32_t fk = 0;
+        char *p = nullptr;
+        size_t len = 0;
+        if (int rc = rows(ctx, bb, 0, n, chrom.c_str(), min_maf, min_spread, nullptr, nullptr, nullptr, &n_rows)) return rc;
+        if (int rc = chain->chain(g, n_rows, &fk)) return tfbs::fail(rc, "another device's shard failed");
+        if (int rc = rows(ctx, bb, 0, n, chrom.c_str(), min_maf, min_spread, &fk, &p, &len, &n_text)) return rc;
+        std::unique_ptr<char, void (*)(void *)> guard(p, free);
+        if (n_text != n_rows) return tfbs::fail(TFBS_E_STATE, label + ": the count and the text disagree");
+        text.assign(p, len);
+        return TFBS_OK;
+    };
+}
 
 struct RunSetup {
     const tfbs_run_args *a;
-    TextOut *hits = nullptr;  // null without --hits_output: the run does nothing more
-    TextOut *best = nullptr;  // null without --best_output: the same
-    TextOut *effects = nullptr;  // null without --effects_output: the same (the batches keep no variants)
-    int effects_mode = TFBS_EFFECTS_SITES;
-    TextOut *mutscan = nullptr;  // null without --mutscan_output: the same (variants are kept for either of the two)
-    uint32_t mutscan_kinds = TFBS_MUT_GAIN | TFBS_MUT_LOSS;
-    ScoresOut *scores = nullptr;  // null without --scores_output: the same
-    ScoresOut *affinity_rows = nullptr;  // null without --affinity_rows_output: the same
-    TextOut *affinity = nullptr;  // null without --affinity_output: the same
-    int affinity_mode = TFBS_AFFINITY_DIFF;
+    std::vector<std::unique_ptr<SideOut>> sides;  // hits, best, effects, mutscan, affinity, scores, affinity rows
+    bool keep_variants() const {
+        return std::any_of(sides.begin(), sides.end(), [](const auto &o) { return o->keep_variants; });
+    }
+    void abort_chains() const {  // a failed run: no shard waits for a batch that will not come
+        for (auto &o : sides)
+            if (o->chain) o->chain->abort();
+    }
     std::string chrom;
     tfbs_patterns *pp;
     std::vector<std::pair<std::string, std::vector<std::pair<uint64_t, uint64_t>>>> beds;
@@ -195,7 +231,7 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
     using namespace tfbs;
     const tfbs_run_args *a = S.a;
     if (sh.batches.empty()) return TFBS_OK;
-    const double t_in = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t_in = seconds();
     Bcf bcf;
     int rc = bcf.open(a->bcf, sh.threads);
     if (rc) return rc;
@@ -216,7 +252,7 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
     std::thread dev_setup([&] {
         int r = tfbs_ctx_create(sh.device, S.pp, &ctx);
         if (!r) r = tfbs_ctx_set_host_threads(ctx, sh.threads);
-        if (!r && !(getenv("TFBS_RUN_BUILD_DEVICE") && atoi(getenv("TFBS_RUN_BUILD_DEVICE")) == 0)) {
+        if (!r && !env_is_off("TFBS_RUN_BUILD_DEVICE")) {
             grouper.reset(make_gpu_grouper(sh.device));
             if (!grouper) r = fail(TFBS_E_NODEVICE, "no device for the grouper");
         }
@@ -245,7 +281,6 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
     };
     using BatchPtr = std::unique_ptr<tfbs_batch, void (*)(tfbs_batch *)>;
     std::vector<const BcfRecord *> recs;
-    auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     struct BcfPhases {
         Bcf &b;
         Shard &sh;
@@ -264,24 +299,21 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
         double fetch = 0, build = 0, bcf = 0, ids = 0, fasta = 0, create = 0;
     };
     auto fetch = [&](size_t g, Pending &p, std::string &err, Times &t) -> int {
-        const double t_in = clock();
-        struct Done {
-            double &acc, t0;
-            ~Done() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0; }
-        } done{t.fetch, t_in};
+        const double t_in = seconds();
+        ScopeTimer done{t.fetch, t_in};
         const size_t b0 = g * S.per_batch, b1 = std::min(S.merged.size(), b0 + S.per_batch);
         tfbs_batch *bb = nullptr;
         int rc = tfbs_batch_create(S.pp, (uint32_t)S.sel.size(), 1, &bb);
-        t.create += clock() - t_in;
+        t.create += seconds() - t_in;
         if (rc) return err = tfbs_last_error(), rc;
         p.bp = BatchPtr(bb, tfbs_batch_destroy);
         Batch &B = bb->b;
-        B.keep_variants = S.effects != nullptr || S.mutscan != nullptr;
+        B.keep_variants = S.keep_variants();
         for (auto &b : S.beds) B.beds.push_back(b.first);
         p.ins.clear();
         p.ins.reserve(b1 - b0);
         for (size_t r = b0; r < b1; r++) {
-            const double tf = clock();
+            const double tf = seconds();
             const auto &m = S.merged[r];
             RegionInput in;
             in.R.ms = m.first;
@@ -323,10 +355,10 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
                 err = "chromosome " + S.chrom + " not in the BCF header";
                 return TFBS_E_ARG;
             }
-            const double tb = clock();
+            const double tb = seconds();
             t.fasta += tb - tf;
             if ((rc = bcf.fetch(rid, in.R.es, in.R.ee + 1, recs))) return err = tfbs_last_error(), rc;
-            const double ti = clock();
+            const double ti = seconds();
             // the next region of the batch starts at beg_next: a record it cannot return
             // gives its carriers away instead of a copy
             uint64_t beg_next = 0, ee_next = 0;
@@ -344,7 +376,7 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
                 if (rc) return err = tfbs_last_error(), rc;
                 in.recs.push_back(std::move(rec));
             }
-            const double te = clock();
+            const double te = seconds();
             t.ids += te - ti;
             t.bcf += te - tb;
             p.ins.push_back(std::move(in));
@@ -352,11 +384,11 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
         return TFBS_OK;
     };
     auto build = [&](Pending &p, std::string &err, Times &t) -> int {
-        const double tb = clock();
+        const double tb = seconds();
         p.bp->b.grouper = grouper;
         const int rc = add_regions(p.bp->b, p.ins, sh.threads);
         std::vector<RegionInput>().swap(p.ins);
-        t.build += clock() - tb;
+        t.build += seconds() - tb;
         return rc ? (err = tfbs_last_error(), rc) : TFBS_OK;
     };
     auto account = [&](const Times &t) {
@@ -367,7 +399,6 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
         sh.t_ids += t.ids;
         sh.t_create += t.create;
     };
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const size_t nb = sh.batches.size();
     Pending cur, nxt, nxt2;
     std::string err;
@@ -375,12 +406,8 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
         Times t;
         if ((rc = fetch(sh.batches[0], cur, err, t))) return fail(rc, err);
         if ((rc = dev_ready())) return rc;
-        sh.t_setup = now() - t_in;  // (readers, the first fetch, the device side: the longer)
-        const double tb0 = now();
-        struct Boot {
-            double &acc, t0;
-            ~Boot() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0; }
-        } boot{sh.t_boot, tb0};
+        sh.t_setup = seconds() - t_in;  // (readers, the first fetch, the device side: the longer)
+        ScopeTimer boot{sh.t_boot};
         if ((rc = build(cur, err, t)) || (nb > 1 && (rc = fetch(sh.batches[1], nxt, err, t)))) return fail(rc, err);
         account(t);
     }
@@ -402,120 +429,19 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
         } joiner{th_fetch, th_build};
         tfbs_batch *bb = cur.bp.get();
         Batch &B = bb->b;
-        double t0 = now();
+        double t0 = seconds();
         if ((rc = tfbs_batch_upload(ctx, bb)) || (rc = tfbs_scan(ctx, bb)) || (rc = tfbs_batch_assemble(ctx, bb)) ||
             (rc = tfbs_batch_reduce(ctx, bb)) ||
             (rc = tfbs_batch_encode_flags(ctx, bb, 0, B.rh.size(), out.device_rows ? TFBS_ENC_DEVICE_CODES : 0)))
             return rc;
-        double t1 = now();
+        double t1 = seconds();
         sh.t_gpu += t1 - t0;
         sh.regions += B.rh.size();
         if ((rc = out(g, ctx, bb))) return rc;
-        sh.t_rows += now() - t1;
-        if (S.hits) {  // the batch's hit list (its image is still resident), as text, in batch order
-            tfbs_hit *hits = nullptr;
-            size_t nh = 0;
-            if ((rc = tfbs_batch_hits(ctx, bb, 0, B.rh.size(), &hits, &nh))) return rc;
-            std::unique_ptr<tfbs_hit, void (*)(void *)> hguard(hits, free);
+        sh.t_rows += seconds() - t1;
+        for (auto &o : S.sides) {  // the side outputs: the batch's text (its image is still resident), in batch order
             std::string text;
-            if ((rc = hits_tsv(B, hits, nh, strip_chr(S.chrom), a->hits_mode, text)) ||
-                (rc = S.hits->submit(g, std::move(text))))
-                return rc;
-        }
-        if (S.best) {  // the batch's best sites: dense records, so a bounded number of whole regions at a time
-            std::string text;
-            const size_t np = B.pats->pats.size();
-            auto records_of = [&](size_t r) { return (size_t)B.rh[r].hap_count * np * B.rh[r].ranges.size(); };
-            for (size_t q0 = 0; q0 < B.rh.size();) {
-                size_t q1 = q0 + 1, recs = records_of(q0);  // regions [q0, q1): one at least
-                while (q1 < B.rh.size() && recs + records_of(q1) <= kBestRunRecords) recs += records_of(q1++);
-                tfbs_best *best = nullptr;
-                size_t nbest = 0;
-                if ((rc = tfbs_batch_best(ctx, bb, q0, q1, &best, &nbest))) return rc;
-                std::unique_ptr<tfbs_best, void (*)(void *)> bguard(best, free);
-                if ((rc = best_tsv(B, best, nbest, strip_chr(S.chrom), a->best_mode, text))) return rc;
-                q0 = q1;
-            }
-            if ((rc = S.best->submit(g, std::move(text)))) return rc;
-        }
-        if (S.effects) {  // the batch's variant effects: dense records too, whole regions at a time
-            std::string text;
-            const size_t np = B.pats->pats.size();
-            auto records_of = [&](size_t r) { return (size_t)B.kept[r].vars.size() * np; };
-            for (size_t q0 = 0; q0 < B.rh.size();) {
-                size_t q1 = q0 + 1, recs = records_of(q0);  // regions [q0, q1): one at least
-                while (q1 < B.rh.size() && recs + records_of(q1) <= kEffectsRunRecords) recs += records_of(q1++);
-                tfbs_effect *eff = nullptr;
-                size_t neff = 0;
-                if ((rc = tfbs_batch_effects(ctx, bb, q0, q1, &eff, &neff))) return rc;
-                std::unique_ptr<tfbs_effect, void (*)(void *)> eguard(eff, free);
-                if ((rc = effects_tsv(B, eff, neff, strip_chr(S.chrom), S.effects_mode, text))) return rc;
-                q0 = q1;
-            }
-            if ((rc = S.effects->submit(g, std::move(text)))) return rc;
-        }
-        if (S.mutscan) {  // the batch's mutation scan: whole regions at a time, bounded as the effects are
-            std::string text;
-            const size_t np = B.pats->pats.size();
-            auto records_of = [&](size_t r) { return (size_t)B.kept[r].ref.size() * 3 * np; };  // (at most)
-            for (size_t q0 = 0; q0 < B.rh.size();) {
-                size_t q1 = q0 + 1, recs = records_of(q0);  // regions [q0, q1): one at least
-                while (q1 < B.rh.size() && recs + records_of(q1) <= kEffectsRunRecords) recs += records_of(q1++);
-                tfbs_mutation *mut = nullptr;
-                size_t nmut = 0;
-                if ((rc = tfbs_batch_mutscan(ctx, bb, q0, q1, S.mutscan_kinds, &mut, &nmut))) return rc;
-                std::unique_ptr<tfbs_mutation, void (*)(void *)> mguard(mut, free);
-                if ((rc = mutscan_tsv(B, mut, nmut, strip_chr(S.chrom), text))) return rc;
-                q0 = q1;
-            }
-            if ((rc = S.mutscan->submit(g, std::move(text)))) return rc;
-        }
-        if (S.affinity) {  // the batch's binding affinities: dense records as the best sites', whole regions at a time
-            std::string text;
-            const size_t np = B.pats->pats.size();
-            auto records_of = [&](size_t r) { return (size_t)B.rh[r].hap_count * np * B.rh[r].ranges.size(); };
-            for (size_t q0 = 0; q0 < B.rh.size();) {
-                size_t q1 = q0 + 1, recs = records_of(q0);  // regions [q0, q1): one at least
-                while (q1 < B.rh.size() && recs + records_of(q1) <= kAffinityRunRecords) recs += records_of(q1++);
-                tfbs_affinity *aff = nullptr;
-                size_t naff = 0;
-                if ((rc = tfbs_batch_affinity(ctx, bb, q0, q1, &aff, &naff))) return rc;
-                std::unique_ptr<tfbs_affinity, void (*)(void *)> aguard(aff, free);
-                if ((rc = affinity_tsv(B, aff, naff, strip_chr(S.chrom), S.affinity_mode, text))) return rc;
-                q0 = q1;
-            }
-            if ((rc = S.affinity->submit(g, std::move(text)))) return rc;
-        }
-        if (S.scores) {  // the batch's score rows: counted, then numbered from the chain and written as text
-            uint64_t n_rows = 0, n_text = 0;
-            uint32_t fk = 0;
-            char *text = nullptr;
-            size_t len = 0;
-            if ((rc = tfbs_batch_score_rows(ctx, bb, 0, B.rh.size(), S.chrom.c_str(), a->min_maf, S.scores->min_spread,
-                                            nullptr, nullptr, nullptr, &n_rows)) ||
-                (rc = S.scores->chain(g, n_rows, &fk)) ||
-                (rc = tfbs_batch_score_rows(ctx, bb, 0, B.rh.size(), S.chrom.c_str(), a->min_maf, S.scores->min_spread,
-                                            &fk, &text, &len, &n_text)))
-                return rc;
-            std::unique_ptr<char, void (*)(void *)> tguard(text, free);
-            if (n_text != n_rows) return fail(TFBS_E_STATE, "score rows: the count and the text disagree");
-            if ((rc = S.scores->out.submit(g, std::string(text, len)))) return rc;
-        }
-        if (S.affinity_rows) {  // the batch's affinity rows: as the score rows, on their own chain
-            ScoresOut &O = *S.affinity_rows;
-            uint64_t n_rows = 0, n_text = 0;
-            uint32_t fk = 0;
-            char *text = nullptr;
-            size_t len = 0;
-            if ((rc = tfbs_batch_affinity_rows(ctx, bb, 0, B.rh.size(), S.chrom.c_str(), a->min_maf, O.min_spread, nullptr,
-                                               nullptr, nullptr, &n_rows)) ||
-                (rc = O.chain(g, n_rows, &fk)) ||
-                (rc = tfbs_batch_affinity_rows(ctx, bb, 0, B.rh.size(), S.chrom.c_str(), a->min_maf, O.min_spread, &fk,
-                                               &text, &len, &n_text)))
-                return rc;
-            std::unique_ptr<char, void (*)(void *)> tguard(text, free);
-            if (n_text != n_rows) return fail(TFBS_E_STATE, "affinity rows: the count and the text disagree");
-            if ((rc = O.out.submit(g, std::string(text, len)))) return rc;
+            if ((rc = o->make(ctx, bb, g, text)) || (rc = o->out.submit(g, std::move(text)))) return rc;
         }
         if (a->verbose) {
             for (size_t r = 0; r < B.rh.size(); r++)
@@ -523,10 +449,10 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
                         S.merged.size(), (unsigned long long)B.rh[r].ms, (unsigned long long)B.rh[r].me,
                         B.rh[r].hap_count, B.rh[r].n_variants);
         }
-        t0 = now();
+        t0 = seconds();
         if (th_fetch.joinable()) th_fetch.join();
         if (th_build.joinable()) th_build.join();
-        sh.t_wait += now() - t0;
+        sh.t_wait += seconds() - t0;
         account(ta);
         account(tb);
         if (rb) return fail(rb, eb);
@@ -535,11 +461,7 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
         nxt = std::move(nxt2);
         nxt2 = Pending();
     }
-    const double te = now();
-    struct End {  // the flush and the ctx's release (cguard, after this)
-        double &acc, t0;
-        ~End() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0; }
-    } end_t{sh.t_end, te};
+    ScopeTimer end_t{sh.t_end};  // the flush and the ctx's release (cguard, after this)
     if ((rc = rows_flush(ctx))) return rc;
     double rs[2];
     if (tfbs_ctx_rows_bgzf_seconds(ctx, rs) == TFBS_OK) sh.rows_plan = rs[0], sh.rows_dev = rs[1];
@@ -548,13 +470,10 @@ int run_shard(const RunSetup &S, Shard &sh, Out &&out) {
 }
 
 // The batches' output in batch order across the devices' threads: the POS chain
-// (batch g's first POS = batch g - 1's + its rows, published as soon as g - 1 has
-// counted them, before it deflates) and the ordered writer (each batch's BGZF
-// blocks -- in a memory file -- or row bodies, written out in order).
-struct Ordered {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<int64_t> base;  // POS of batch g's first row, -1 unknown
+// (published as soon as a batch has counted its rows, before it deflates) and, under
+// the chain's mutex, the ordered writer (each batch's BGZF blocks -- in a memory
+// file -- or row bodies, written out in order).
+struct Ordered : tfbs::PosChain {
     struct Item {
         bool ready = false;
         int fd = -1;           // BGZF blocks (memory file), or
@@ -572,19 +491,9 @@ struct Ordered {
     std::vector<int64_t> off;
     std::vector<uint8_t> done_;
     size_t sized = 0;  // off[0 .. sized] known
-    bool failed = false;
     int first_rc = TFBS_OK;  // the failure that stopped the others
     std::string first_err;
-    explicit Ordered(size_t n) : base(n + 1, -1), items(n), size(n, 0), off(n + 1, -1), done_(n, 0) { base[0] = 1; }
-    int chain(size_t g, uint64_t n_rows, uint32_t *fake) {
-        std::unique_lock<std::mutex> l(mu);
-        cv.wait(l, [&] { return failed || base[g] >= 0; });
-        if (failed) return tfbs::fail(TFBS_E_STATE, "another device's shard failed");
-        *fake = (uint32_t)base[g];
-        base[g + 1] = base[g] + (int64_t)n_rows;
-        cv.notify_all();
-        return TFBS_OK;
-    }
+    explicit Ordered(size_t n) : PosChain(n), items(n), size(n, 0), off(n + 1, -1), done_(n, 0) {}
     void submit(size_t g, Item &&it, uint64_t bytes = 0) {
         std::lock_guard<std::mutex> l(mu);
         items[g] = std::move(it);
@@ -697,6 +606,14 @@ std::vector<int> parse_devices(const tfbs_run_args *a) {
     return d;
 }
 
+// *dst = ext->field where the caller's `size` covers the field; else *dst stays.
+template <class F>
+void ext_get(const tfbs_run_ext *ext, F tfbs_run_ext::*field, F *dst) {
+    if (!ext) return;
+    const size_t end = (size_t)((const char *)&(ext->*field) - (const char *)ext) + sizeof(F);
+    if (ext->size >= end) *dst = ext->*field;
+}
+
 }  // namespace
 
 extern "C" {
@@ -705,42 +622,26 @@ int tfbs_run(const tfbs_run_args *a) { return tfbs_run_ex(a, nullptr); }
 
 int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     using namespace tfbs;
-    // only what the caller's `size` covers is read
-    const char *effects_output = nullptr;
-    int effects_mode = TFBS_EFFECTS_SITES;
-    const char *scores_output = nullptr;
-    uint64_t scores_min_spread = 1;
-    double pwm_pvalue = 0;
-    const char *mutscan_output = nullptr;
+    // only what the caller's `size` covers is read; the rest keeps these defaults
+    const char *effects_output = nullptr, *scores_output = nullptr, *mutscan_output = nullptr;
+    const char *affinity_output = nullptr, *affinity_rows_output = nullptr;
+    int effects_mode = TFBS_EFFECTS_SITES, affinity_mode = TFBS_AFFINITY_ALL;
+    uint64_t scores_min_spread = 0, affinity_rows_min_spread = 0;
     uint32_t mutscan_kinds = 0;
-    const char *affinity_output = nullptr;
-    int affinity_mode = TFBS_AFFINITY_ALL;
-    const char *affinity_rows_output = nullptr;
-    uint64_t affinity_rows_min_spread = 1;
-    if (ext) {
-        if (ext->size >= offsetof(tfbs_run_ext, affinity_rows_output) + sizeof ext->affinity_rows_output)
-            affinity_rows_output = ext->affinity_rows_output;
-        if (ext->size >= offsetof(tfbs_run_ext, affinity_rows_min_spread) + sizeof ext->affinity_rows_min_spread &&
-            ext->affinity_rows_min_spread)
-            affinity_rows_min_spread = ext->affinity_rows_min_spread;
-        if (ext->size >= offsetof(tfbs_run_ext, affinity_output) + sizeof ext->affinity_output)
-            affinity_output = ext->affinity_output;
-        if (ext->size >= offsetof(tfbs_run_ext, affinity_mode) + sizeof ext->affinity_mode)
-            affinity_mode = ext->affinity_mode;
-        if (ext->size >= offsetof(tfbs_run_ext, mutscan_output) + sizeof ext->mutscan_output)
-            mutscan_output = ext->mutscan_output;
-        if (ext->size >= offsetof(tfbs_run_ext, mutscan_kinds) + sizeof ext->mutscan_kinds)
-            mutscan_kinds = ext->mutscan_kinds;
-        if (ext->size >= offsetof(tfbs_run_ext, pwm_pvalue) + sizeof ext->pwm_pvalue) pwm_pvalue = ext->pwm_pvalue;
-        if (ext->size >= offsetof(tfbs_run_ext, scores_output) + sizeof ext->scores_output)
-            scores_output = ext->scores_output;
-        if (ext->size >= offsetof(tfbs_run_ext, scores_min_spread) + sizeof ext->scores_min_spread &&
-            ext->scores_min_spread)
-            scores_min_spread = ext->scores_min_spread;
-        if (ext->size >= offsetof(tfbs_run_ext, effects_output) + sizeof ext->effects_output)
-            effects_output = ext->effects_output;
-        if (ext->size >= offsetof(tfbs_run_ext, effects_mode) + sizeof ext->effects_mode) effects_mode = ext->effects_mode;
-    }
+    double pwm_pvalue = 0;
+    ext_get(ext, &tfbs_run_ext::effects_output, &effects_output);
+    ext_get(ext, &tfbs_run_ext::effects_mode, &effects_mode);
+    ext_get(ext, &tfbs_run_ext::scores_output, &scores_output);
+    ext_get(ext, &tfbs_run_ext::scores_min_spread, &scores_min_spread);
+    ext_get(ext, &tfbs_run_ext::pwm_pvalue, &pwm_pvalue);
+    ext_get(ext, &tfbs_run_ext::mutscan_output, &mutscan_output);
+    ext_get(ext, &tfbs_run_ext::mutscan_kinds, &mutscan_kinds);
+    ext_get(ext, &tfbs_run_ext::affinity_output, &affinity_output);
+    ext_get(ext, &tfbs_run_ext::affinity_mode, &affinity_mode);
+    ext_get(ext, &tfbs_run_ext::affinity_rows_output, &affinity_rows_output);
+    ext_get(ext, &tfbs_run_ext::affinity_rows_min_spread, &affinity_rows_min_spread);
+    if (!scores_min_spread) scores_min_spread = 1;  // (0 counts as 1)
+    if (!affinity_rows_min_spread) affinity_rows_min_spread = 1;
     if (!a || !a->chromosome || !a->bcf || !a->bed_files || !a->reference || (!a->pwm_file && !a->dipwm_file) ||
         (!a->pwm_threshold_dir && !(pwm_pvalue > 0)) || !a->pwm_names || !a->output)
         return fail(TFBS_E_ARG, "missing required argument");
@@ -838,59 +739,73 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     header += "\n";
     rc = w.write(header.data(), header.size());
     if (rc) return rc;
-    TextOut hits_out, best_out, effects_out;
-    if (a->hits_output) {
-        if (a->hits_mode != TFBS_HITS_ALL && a->hits_mode != TFBS_HITS_DIFF)
-            return fail(TFBS_E_ARG, "hits_mode is TFBS_HITS_ALL or TFBS_HITS_DIFF");
-        if ((rc = hits_out.open(a->hits_output, threads, TFBS_HITS_HEADER))) return rc;
-        S.hits = &hits_out;
-    }
-    if (a->best_output) {
-        if (a->best_mode != TFBS_BEST_ALL && a->best_mode != TFBS_BEST_DIFF)
-            return fail(TFBS_E_ARG, "best_mode is TFBS_BEST_ALL or TFBS_BEST_DIFF");
-        if ((rc = best_out.open(a->best_output, threads, TFBS_BEST_HEADER))) return rc;
-        S.best = &best_out;
-    }
-    if (effects_output) {
-        if (effects_mode != TFBS_EFFECTS_SITES && effects_mode != TFBS_EFFECTS_ALL)
-            return fail(TFBS_E_ARG, "effects_mode is TFBS_EFFECTS_SITES or TFBS_EFFECTS_ALL");
-        if ((rc = effects_out.open(effects_output, threads, TFBS_EFFECTS_HEADER))) return rc;
-        S.effects = &effects_out;
-        S.effects_mode = effects_mode;
-    }
-    TextOut mutscan_out;
-    if (mutscan_output) {
-        if (mutscan_kinds > TFBS_MUT_ALL) return fail(TFBS_E_ARG, "mutscan_kinds is a mask of TFBS_MUT_*");
-        if ((rc = mutscan_out.open(mutscan_output, threads, TFBS_MUTSCAN_HEADER))) return rc;
-        S.mutscan = &mutscan_out;
-        if (mutscan_kinds) S.mutscan_kinds = mutscan_kinds;
-    }
-    TextOut affinity_out;
-    if (affinity_output) {
-        if (affinity_mode != TFBS_AFFINITY_ALL && affinity_mode != TFBS_AFFINITY_DIFF)
-            return fail(TFBS_E_ARG, "affinity_mode is TFBS_AFFINITY_ALL or TFBS_AFFINITY_DIFF");
-        if ((rc = affinity_out.open(affinity_output, threads, TFBS_AFFINITY_HEADER))) return rc;
-        S.affinity = &affinity_out;
-        S.affinity_mode = affinity_mode;
-    }
-    ScoresOut scores_out;
-    if (scores_output) {
-        if ((rc = scores_out.out.open(scores_output, threads, header.c_str()))) return rc;
-        scores_out.min_spread = scores_min_spread;
-        S.scores = &scores_out;
-    }
-    ScoresOut affinity_rows_out;
-    if (affinity_rows_output) {
-        if ((rc = affinity_rows_out.out.open(affinity_rows_output, threads, header.c_str()))) return rc;
-        affinity_rows_out.min_spread = affinity_rows_min_spread;
-        S.affinity_rows = &affinity_rows_out;
-    }
+    S.per_batch = a->regions_per_batch ? a->regions_per_batch : 512;
+    const size_t n_batches = (S.merged.size() + S.per_batch - 1) / S.per_batch;
+    const std::string chr = strip_chr(S.chrom);
+
+    // The side outputs, one table entry for each that is asked for, in this order: a bad mode
+    // is refused before the entry's file is opened, and nothing after it is.
+    auto side = [&](const char *path, const char *refusal, const char *head, decltype(SideOut::make) make,
+                    bool keep_variants = false, std::unique_ptr<PosChain> chain = nullptr) -> int {
+        if (!path) return TFBS_OK;
+        if (refusal) return fail(TFBS_E_ARG, refusal);
+        auto o = std::make_unique<SideOut>();
+        if (int e = o->out.open(path, threads, head)) return e;
+        o->make = std::move(make);
+        o->keep_variants = keep_variants;
+        o->chain = std::move(chain);
+        S.sides.push_back(std::move(o));
+        return TFBS_OK;
+    };
+    auto rows_side = [&](const char *path, decltype(&tfbs_batch_score_rows) rows, const char *label, uint64_t min_spread) {
+        auto chain = std::make_unique<PosChain>(n_batches);
+        auto make = rows_maker(rows, label, chain.get(), S.chrom, a->min_maf, min_spread);
+        return side(path, nullptr, header.c_str(), make, false, std::move(chain));
+    };
+    auto unless = [](int mode, int x, int y, const char *refusal) { return mode == x || mode == y ? nullptr : refusal; };
+    auto no_records = [](const Batch &, size_t) { return 0; };  // (the hit list: the whole batch in one call)
+    auto key_records = [](const Batch &B, size_t r) { return (size_t)B.rh[r].hap_count * B.pats->pats.size() * B.rh[r].ranges.size(); };
+    auto var_records = [](const Batch &B, size_t r) { return B.kept[r].vars.size() * B.pats->pats.size(); };
+    auto snv_records = [](const Batch &B, size_t r) { return B.kept[r].ref.size() * 3 * B.pats->pats.size(); };  // (at most)
+    const int hits_mode = a->hits_mode, best_mode = a->best_mode;
+    const uint32_t kinds = mutscan_kinds ? mutscan_kinds : TFBS_MUT_GAIN | TFBS_MUT_LOSS;
+    if ((rc = side(a->hits_output,
+                   unless(hits_mode, TFBS_HITS_ALL, TFBS_HITS_DIFF, "hits_mode is TFBS_HITS_ALL or TFBS_HITS_DIFF"), TFBS_HITS_HEADER,
+                   records_maker<tfbs_hit>(tfbs_batch_hits, [=](const Batch &B, const tfbs_hit *x, size_t n, std::string &t) {
+                       return hits_tsv(B, x, n, chr, hits_mode, t);
+                   }, no_records, 0))) ||
+        (rc = side(a->best_output,
+                   unless(best_mode, TFBS_BEST_ALL, TFBS_BEST_DIFF, "best_mode is TFBS_BEST_ALL or TFBS_BEST_DIFF"), TFBS_BEST_HEADER,
+                   records_maker<tfbs_best>(tfbs_batch_best, [=](const Batch &B, const tfbs_best *x, size_t n, std::string &t) {
+                       return best_tsv(B, x, n, chr, best_mode, t);
+                   }, key_records, kBestRunRecords))) ||
+        (rc = side(effects_output,
+                   unless(effects_mode, TFBS_EFFECTS_SITES, TFBS_EFFECTS_ALL, "effects_mode is TFBS_EFFECTS_SITES or TFBS_EFFECTS_ALL"),
+                   TFBS_EFFECTS_HEADER,
+                   records_maker<tfbs_effect>(tfbs_batch_effects, [=](const Batch &B, const tfbs_effect *x, size_t n, std::string &t) {
+                       return effects_tsv(B, x, n, chr, effects_mode, t);
+                   }, var_records, kEffectsRunRecords), true)) ||
+        (rc = side(mutscan_output, mutscan_kinds > TFBS_MUT_ALL ? "mutscan_kinds is a mask of TFBS_MUT_*" : nullptr,
+                   TFBS_MUTSCAN_HEADER,
+                   records_maker<tfbs_mutation>(
+                       [=](tfbs_ctx *c, tfbs_batch *b, size_t q0, size_t q1, tfbs_mutation **m, size_t *n) {
+                           return tfbs_batch_mutscan(c, b, q0, q1, kinds, m, n);
+                       },
+                       [=](const Batch &B, const tfbs_mutation *x, size_t n, std::string &t) { return mutscan_tsv(B, x, n, chr, t); },
+                       snv_records, kEffectsRunRecords), true)) ||
+        (rc = side(affinity_output,
+                   unless(affinity_mode, TFBS_AFFINITY_ALL, TFBS_AFFINITY_DIFF, "affinity_mode is TFBS_AFFINITY_ALL or TFBS_AFFINITY_DIFF"),
+                   TFBS_AFFINITY_HEADER,
+                   records_maker<tfbs_affinity>(tfbs_batch_affinity, [=](const Batch &B, const tfbs_affinity *x, size_t n, std::string &t) {
+                       return affinity_tsv(B, x, n, chr, affinity_mode, t);
+                   }, key_records, kAffinityRunRecords))) ||
+        (rc = rows_side(scores_output, tfbs_batch_score_rows, "score rows", scores_min_spread)) ||
+        (rc = rows_side(affinity_rows_output, tfbs_batch_affinity_rows, "affinity rows", affinity_rows_min_spread)))
+        return rc;
 
     // shards: batch g of merged regions on device g % n (one device:
     // every batch); rows in merged-peak order, POS counted across the devices
-    S.per_batch = a->regions_per_batch ? a->regions_per_batch : 512;
     const std::vector<int> devs = parse_devices(a);
-    const size_t n_batches = (S.merged.size() + S.per_batch - 1) / S.per_batch;
     const size_t n_sh = std::max<size_t>(1, std::min(devs.size(), n_batches));
     std::vector<Shard> shards(n_sh);
     for (size_t k = 0; k < n_sh; k++) {
@@ -898,16 +813,12 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
         shards[k].threads = std::max<uint32_t>(1, threads / (uint32_t)n_sh);
     }
     for (size_t g = 0; g < n_batches; g++) shards[g % n_sh].batches.push_back(g);
-    if (S.scores) S.scores->batches(n_batches);
-    if (S.affinity_rows) S.affinity_rows->batches(n_batches);
-    const std::string chr = strip_chr(S.chrom);
     uint32_t fake = 1;
-    const bool timing = getenv("TFBS_RUN_TIMING") && atoi(getenv("TFBS_RUN_TIMING"));
+    const bool timing = env_is_on("TFBS_RUN_TIMING");
     // TFBS_GPU_BGZF=0: rows formatted on the host and deflated by the writer's host
     // threads (zlib); default: BGZF blocks made on each device (bgzf_gpu.hip)
-    const bool gpu_bgzf = !(getenv("TFBS_GPU_BGZF") && atoi(getenv("TFBS_GPU_BGZF")) == 0);
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = now();
+    const bool gpu_bgzf = !env_is_off("TFBS_GPU_BGZF");
+    const double t_start = seconds();
     double t_write = 0;
     if (n_sh == 1) {  // one device: its batches in order, straight to the output
         struct One {
@@ -930,8 +841,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
                 if (int rc = tfbs::batch_row_bodies(bb->b, S.a->min_maf, bodies, std::max(1u, S.a->threads))) return rc;
                 return write_prefixed(w, chr, bodies.data(), bodies.size(), &fake);
             }
-        } one{gpu_bgzf, !(getenv("TFBS_RUN_ASYNC_WRITE") && atoi(getenv("TFBS_RUN_ASYNC_WRITE")) == 0), S, w, chr, fake,
-              t_write};
+        } one{gpu_bgzf, !env_is_off("TFBS_RUN_ASYNC_WRITE"), S, w, chr, fake, t_write};
         shards[0].rc = run_shard(S, shards[0], one);
         if (shards[0].rc) shards[0].err = tfbs_last_error();
     } else {  // several: each batch's output to the ordered writer
@@ -952,7 +862,10 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
                     uint32_t fk = 0;
                     const int rc = tfbs::rows_bgzf_chained(
                         ctx, bb, 0, n, S.chrom.c_str(), S.a->min_maf, &fk, it.fd, nullptr, nullptr,
-                        [&](uint64_t rows, uint32_t *base) { return ord.chain(g, rows, base); });
+                        [&](uint64_t rows, uint32_t *base) {
+                            const int e = ord.chain(g, rows, base);
+                            return e ? tfbs::fail(e, "another device's shard failed") : TFBS_OK;
+                        });
                     if (rc) {
                         close(it.fd);
                         return rc;
@@ -993,7 +906,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
                 Ordered::Item it;
                 int64_t at = 0;
                 if (gpu_bgzf ? !ord.placed(g, it, at) : !ord.take(g, it)) return;
-                const double t0 = now();
+                const double t0 = seconds();
                 int rc;
                 if (it.fd >= 0) {
                     rc = copy_fd_at(it.fd, ord.size[g], out_fd, (uint64_t)at);
@@ -1004,12 +917,11 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
                 }
                 {
                     std::lock_guard<std::mutex> l(tw_mu);
-                    t_write += now() - t0;
+                    t_write += seconds() - t0;
                 }
                 if (rc) {
                     ord.abort(rc, tfbs_last_error());
-                    if (S.scores) S.scores->abort();
-                    if (S.affinity_rows) S.affinity_rows->abort();
+                    S.abort_chains();
                     return;
                 }
                 ord.finished(g);
@@ -1023,8 +935,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
             if (shards[k].rc) {
                 shards[k].err = tfbs_last_error();
                 ord.abort(shards[k].rc, shards[k].err);
-                if (S.scores) S.scores->abort();
-                if (S.affinity_rows) S.affinity_rows->abort();
+                S.abort_chains();
             }
         };
         std::vector<std::thread> ts;
@@ -1045,16 +956,11 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     for (auto &sh : shards)
         if (sh.rc) return fail(sh.rc, sh.err);
     // the reference flushes twice before drop (main.rs:271, 275): two empty blocks
-    double t0 = now();
+    double t0 = seconds();
     if ((rc = w.flush()) || (rc = w.flush()) || (rc = w.close())) return rc;
-    if (S.hits && (rc = hits_out.finish())) return rc;
-    if (S.best && (rc = best_out.finish())) return rc;
-    if (S.effects && (rc = effects_out.finish())) return rc;
-    if (S.mutscan && (rc = mutscan_out.finish())) return rc;
-    if (S.affinity && (rc = affinity_out.finish())) return rc;
-    if (S.scores && (rc = scores_out.out.finish())) return rc;
-    if (S.affinity_rows && (rc = affinity_rows_out.out.finish())) return rc;
-    const double t_close = now() - t0;
+    for (auto &o : S.sides)
+        if ((rc = o->out.finish())) return rc;
+    const double t_close = seconds() - t0;
     if (timing)
         for (size_t k = 0; k < n_sh; k++)
             fprintf(stderr,
@@ -1070,7 +976,7 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
                     shards[k].b_inflate, shards[k].b_scan, shards[k].b_wait, shards[k].b_decode, shards[k].t_create, shards[k].rows_plan,
                     shards[k].rows_dev, shards[k].drain[0], shards[k].drain[1], shards[k].drain[2],
                     shards[k].t_setup, shards[k].t_boot, shards[k].t_end,
-                    shards[k].t_wait, shards[k].t_gpu, shards[k].t_rows, t_write, t_close, now() - t_start);
+                    shards[k].t_wait, shards[k].t_gpu, shards[k].t_rows, t_write, t_close, seconds() - t_start);
     if (a->tabix) {
         const std::string cmd = "zcat '" + part + "' | bgzip > '" + out + "'; tabix -f -p vcf '" + out + "'; rm '" +
                                 part + "'";
@@ -1078,127 +984,6 @@ int tfbs_run_ex(const tfbs_run_args *a, const tfbs_run_ext *ext) {
     } else if (rename(part.c_str(), out.c_str()) != 0) {
         return fail(TFBS_E_IO, "Could not rename " + part + " into " + out);
     }
-    return TFBS_OK;
-}
-
-// ----------------------------------------------------------------------------
-// File-format entry points (f2-f4), for tests and embedding.
-// ----------------------------------------------------------------------------
-struct tfbs_bcf {
-    tfbs::Bcf b;
-    std::vector<const tfbs::BcfRecord *> cur;
-};
-
-int tfbs_bcf_open(const char *path, tfbs_bcf **out) {
-    if (!path || !out) return tfbs::fail(TFBS_E_ARG, "null argument");
-    auto *b = new tfbs_bcf();
-    int rc = b->b.open(path);
-    if (rc) {
-        delete b;
-        return rc;
-    }
-    *out = b;
-    return TFBS_OK;
-}
-void tfbs_bcf_close(tfbs_bcf *b) { delete b; }
-int tfbs_bcf_select(tfbs_bcf *b, const size_t *idx, size_t n) {
-    if (!b || (n && !idx)) return tfbs::fail(TFBS_E_ARG, "null argument");
-    b->cur.clear();
-    return b->b.select(std::vector<size_t>(idx, idx + n));
-}
-size_t tfbs_bcf_num_samples(const tfbs_bcf *b) { return b ? b->b.samples.size() : 0; }
-int tfbs_bcf_indexed(const tfbs_bcf *b) { return b && b->b.indexed() ? 1 : 0; }
-const char *tfbs_bcf_sample_name(const tfbs_bcf *b, size_t i) {
-    return (b && i < b->b.samples.size()) ? b->b.samples[i].c_str() : nullptr;
-}
-int tfbs_bcf_fetch(tfbs_bcf *b, const char *chrom, uint64_t beg, uint64_t end, size_t *n) {
-    if (!b || !chrom || !n) return tfbs::fail(TFBS_E_ARG, "null argument");
-    const int rid = b->b.contig_index(chrom);
-    if (rid < 0) return tfbs::fail(TFBS_E_ARG, std::string("unknown contig ") + chrom);
-    const int rc = b->b.fetch(rid, beg, end, b->cur);
-    if (rc) return rc;
-    *n = b->cur.size();
-    return TFBS_OK;
-}
-int tfbs_bcf_record(const tfbs_bcf *b, size_t i, uint64_t *pos, uint32_t *rlen, uint32_t *n_alleles, const char **ref,
-                    const char **alt, const int32_t **gt) {
-    if (!b || i >= b->cur.size()) return tfbs::fail(TFBS_E_ARG, "bad record index");
-    const tfbs::BcfRecord *r = b->cur[i];
-    if (pos) *pos = r->pos;
-    if (rlen) *rlen = r->rlen;
-    if (n_alleles) *n_alleles = r->n_alleles;
-    if (ref) *ref = r->ref.c_str();
-    if (alt) *alt = r->n_alleles >= 2 ? r->alt.c_str() : nullptr;
-    if (gt) *gt = r->gt.empty() ? nullptr : r->gt.data();
-    return TFBS_OK;
-}
-
-int tfbs_bcf_set_carriers_mode(tfbs_bcf *b, int on) {
-    if (!b) return tfbs::fail(TFBS_E_ARG, "null argument");
-    b->cur.clear();
-    return b->b.set_carriers_mode(on != 0);
-}
-int tfbs_bcf_record_carriers(const tfbs_bcf *b, size_t i, const uint32_t **ids, size_t *n, int *gt_status) {
-    if (!b || i >= b->cur.size()) return tfbs::fail(TFBS_E_ARG, "bad record index");
-    const tfbs::BcfRecord *r = b->cur[i];
-    if (ids) *ids = r->carriers.data();
-    if (n) *n = r->carriers.size();
-    if (gt_status) *gt_status = r->gt_status;
-    return TFBS_OK;
-}
-
-int tfbs_fasta_fetch(const char *path, const char *chrom, uint64_t start, uint64_t stop, char **out, size_t *n) {
-    if (!path || !chrom || !out || !n) return tfbs::fail(TFBS_E_ARG, "null argument");
-    tfbs::Fasta f;
-    int rc = f.open(path);
-    if (rc) return rc;
-    std::string s;
-    rc = f.fetch(chrom, start, stop, s);
-    if (rc) return rc;
-    char *p = (char *)malloc(s.size() + 1);
-    memcpy(p, s.data(), s.size());
-    p[s.size()] = 0;
-    *out = p;
-    *n = s.size();
-    return TFBS_OK;
-}
-
-int tfbs_bgzf_write_file(const char *path, const char *text, size_t n, int flushes) {
-    if (!path || (n && !text)) return tfbs::fail(TFBS_E_ARG, "null argument");
-    tfbs::BgzfWriter w;
-    int rc = w.open(path);
-    if (!rc) rc = w.write(text, n);
-    for (int i = 0; !rc && i < flushes; i++) rc = w.flush();
-    if (!rc) rc = w.close();
-    return rc;
-}
-
-int tfbs_bgzf_read_file(const char *path, char **out, size_t *n) {
-    if (!path || !out || !n) return tfbs::fail(TFBS_E_ARG, "null argument");
-    std::ifstream in(path, std::ios::binary);
-    if (!in) return tfbs::fail(TFBS_E_IO, std::string("Could not open file ") + path);
-    std::string raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>()), txt;
-    int rc = tfbs::bgzf_inflate(raw, txt);
-    if (rc) return rc;
-    char *p = (char *)malloc(txt.size() + 1);
-    memcpy(p, txt.data(), txt.size());
-    p[txt.size()] = 0;
-    *out = p;
-    *n = txt.size();
-    return TFBS_OK;
-}
-
-int tfbs_merge_ranges(const uint64_t *starts, const uint64_t *ends, size_t n, uint64_t *out_s, uint64_t *out_e,
-                      size_t *n_out) {
-    if (!n_out || (n && (!starts || !ends || !out_s || !out_e))) return tfbs::fail(TFBS_E_ARG, "null argument");
-    std::vector<std::pair<uint64_t, uint64_t>> r(n);
-    for (size_t i = 0; i < n; i++) r[i] = {starts[i], ends[i]};
-    auto m = tfbs::merge_ranges(r);
-    for (size_t i = 0; i < m.size(); i++) {
-        out_s[i] = m[i].first;
-        out_e[i] = m[i].second;
-    }
-    *n_out = m.size();
     return TFBS_OK;
 }
 
