@@ -19,6 +19,7 @@ argument meaning, error behaviour) over the C ABI of include/tfbs_amd.h:
 The reference panics where TfbsError is raised.  The scan always runs on a HIP
 device; without one, Scanner() raises TfbsError(TFBS_E_NODEVICE).
 """
+import array
 import contextlib
 import ctypes as C
 from collections import namedtuple
@@ -224,6 +225,41 @@ class PatternSet:
                                             meta, nm.value, C.byref(nm)))
         return {"image": bytes(img)[:nb.value], "meta": list(meta[:nm.value]),
                 "supers": [{n: getattr(sup[k], n) for n, _ in sup[k]._fields_} for k in range(ns.value)]}
+
+    def lut_plan(self, tile_blocks=20, mfma=False):
+        """The LUT and generic plan a Scanner uploads with TFBS_TILE_BLOCKS=tile_blocks and
+        TFBS_MFMA=mfma, copied and not interpreted (tfbs_patterns_lut_plan, a diagnostic): dict(tiles,
+        units, gen_tiles, gen_pats = [dict of the entry's fields, a unit's per-strand fields as
+        lists], lut = the table blocks' ints (1024 per block) and gen_w = the generic weights (5 per
+        column) as array('i'), slot_pid, slot_mfma = lists, one entry per count slot)."""
+        sz = _capi.tfbs_lut_plan_sizes()
+        check(lib().tfbs_patterns_lut_plan(self.h, tile_blocks, 1 if mfma else 0, None, C.byref(sz)))
+        buf = _capi.tfbs_lut_plan_buffers()
+        keep = {}
+        for name, n, ctype in (("tiles", sz.n_tiles, _capi.tfbs_lut_tile), ("units", sz.n_units, _capi.tfbs_lut_unit),
+                               ("lut", sz.lut_ints, C.c_int32), ("gen_tiles", sz.n_gen_tiles, _capi.tfbs_lut_tile),
+                               ("gen_pats", sz.n_gen_pats, _capi.tfbs_lut_gen_pat), ("gen_w", sz.gen_w_ints, C.c_int32),
+                               ("slot_pid", sz.n_slots, C.c_uint16), ("slot_mfma", sz.n_slots, C.c_uint8)):
+            keep[name] = (ctype * max(1, n))()
+            setattr(buf, name, keep[name])
+            setattr(buf, name + "_cap", n)
+        check(lib().tfbs_patterns_lut_plan(self.h, tile_blocks, 1 if mfma else 0, C.byref(buf), C.byref(sz)))
+
+        def fields(x):
+            return {n: (getattr(x, n) if isinstance(getattr(x, n), int) else list(getattr(x, n))) for n, _ in x._fields_}
+
+        def ints(name, n):
+            a = array.array("i")
+            a.frombytes(bytes(keep[name])[:4 * n])
+            return a
+
+        assert array.array("i").itemsize == 4
+        return {"tiles": [fields(keep["tiles"][k]) for k in range(sz.n_tiles)],
+                "units": [fields(keep["units"][k]) for k in range(sz.n_units)],
+                "gen_tiles": [fields(keep["gen_tiles"][k]) for k in range(sz.n_gen_tiles)],
+                "gen_pats": [fields(keep["gen_pats"][k]) for k in range(sz.n_gen_pats)],
+                "lut": ints("lut", sz.lut_ints), "gen_w": ints("gen_w", sz.gen_w_ints),
+                "slot_pid": list(keep["slot_pid"][:sz.n_slots]), "slot_mfma": list(keep["slot_mfma"][:sz.n_slots])}
 
     def subset(self, keep_pattern_id):
         """A new PatternSet of the patterns whose pattern_id passes keep_pattern_id (both

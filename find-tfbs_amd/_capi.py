@@ -48,6 +48,37 @@ class tfbs_mfma_super(C.Structure):
         [("t0", C.c_int32)] + [(n, C.c_uint32) for n in ("acc0", "lmin", "lmax", "tile0")]
 
 
+class tfbs_lut_tile(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("first", "last", "lut_begin", "nblocks", "slot_begin", "nslots", "lmin")]
+
+
+class tfbs_lut_unit(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("lut_off", "nblk", "nstrand", "kind")] + [("init", C.c_uint32 * 4)] + \
+        [("thr", C.c_int32 * 8), ("min_score", C.c_int32 * 8)] + \
+        [(n, C.c_uint32 * 8) for n in ("len", "slot_local", "orig_index")]
+
+
+class tfbs_lut_gen_pat(C.Structure):
+    _fields_ = [("col_off", C.c_uint32), ("min_score", C.c_int32), ("len", C.c_uint32), ("slot_local", C.c_uint32),
+                ("orig_index", C.c_uint32)]
+
+
+class tfbs_lut_plan_sizes(C.Structure):
+    _fields_ = [(n, C.c_size_t) for n in ("n_tiles", "n_units", "lut_ints", "n_gen_tiles", "n_gen_pats",
+                                          "gen_w_ints", "n_slots")]
+
+
+class tfbs_lut_plan_buffers(C.Structure):
+    _fields_ = [("tiles", C.POINTER(tfbs_lut_tile)), ("tiles_cap", C.c_size_t),
+                ("units", C.POINTER(tfbs_lut_unit)), ("units_cap", C.c_size_t),
+                ("lut", i32p), ("lut_cap", C.c_size_t),
+                ("gen_tiles", C.POINTER(tfbs_lut_tile)), ("gen_tiles_cap", C.c_size_t),
+                ("gen_pats", C.POINTER(tfbs_lut_gen_pat)), ("gen_pats_cap", C.c_size_t),
+                ("gen_w", i32p), ("gen_w_cap", C.c_size_t),
+                ("slot_pid", u16p), ("slot_pid_cap", C.c_size_t),
+                ("slot_mfma", u8p), ("slot_mfma_cap", C.c_size_t)]
+
+
 class tfbs_run_args(C.Structure):
     _fields_ = [
         ("chromosome", C.c_char_p), ("bcf", C.c_char_p), ("bed_files", C.c_char_p), ("reference", C.c_char_p),
@@ -143,6 +174,8 @@ SIGNATURES = [
     ("tfbs_patterns_mfma_plan", C.c_int, [vp, C.c_uint32, u8p, C.c_size_t, C.POINTER(C.c_size_t),
                                           C.POINTER(tfbs_mfma_super), C.c_size_t, C.POINTER(C.c_size_t), i32p,
                                           C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("tfbs_patterns_lut_plan", C.c_int, [vp, C.c_uint32, C.c_int, C.POINTER(tfbs_lut_plan_buffers),
+                                         C.POINTER(tfbs_lut_plan_sizes)]),
     ("tfbs_patterns_score_tails", C.c_int, [vp, C.c_int, C.c_size_t, i32p, C.c_size_t, u64p, u64p]),
     ("tfbs_patterns_pvalue_thresholds", C.c_int, [vp, C.c_int, C.c_double, i32p]),
     ("tfbs_patterns_with_min_scores", C.c_int, [vp, i32p, C.POINTER(vp)]),

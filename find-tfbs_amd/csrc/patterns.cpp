@@ -666,6 +666,58 @@ int tfbs_patterns_mfma_plan(const tfbs_patterns *p, uint32_t lds_kb, uint8_t *im
     return TFBS_OK;
 }
 
+int tfbs_patterns_lut_plan(const tfbs_patterns *p, uint32_t tile_blocks, int mfma, const tfbs_lut_plan_buffers *buf,
+                           tfbs_lut_plan_sizes *sizes) {
+    if (!p || !sizes) return tfbs::fail(TFBS_E_ARG, "null argument");
+    tfbs::Plan plan;
+    tfbs::PlanOptions opt;
+    opt.tile_blocks = tile_blocks;
+    opt.mfma = mfma != 0;
+    int rc = p->p.build_plan(opt, &plan);
+    if (rc) return rc;
+    const size_t n_slots = plan.slot_pid.size();  // (a set's dinucleotide slots come last)
+    *sizes = tfbs_lut_plan_sizes{plan.fast_tiles.size(), plan.fast_units.size(), plan.lut.size(),
+                                 plan.gen_tiles.size(),  plan.gen_pats.size(),   plan.gen_w.size(), n_slots};
+    if (!buf) return TFBS_OK;
+    if ((buf->tiles && buf->tiles_cap < sizes->n_tiles) || (buf->units && buf->units_cap < sizes->n_units) ||
+        (buf->lut && buf->lut_cap < sizes->lut_ints) || (buf->gen_tiles && buf->gen_tiles_cap < sizes->n_gen_tiles) ||
+        (buf->gen_pats && buf->gen_pats_cap < sizes->n_gen_pats) || (buf->gen_w && buf->gen_w_cap < sizes->gen_w_ints) ||
+        (buf->slot_pid && buf->slot_pid_cap < n_slots) || (buf->slot_mfma && buf->slot_mfma_cap < n_slots))
+        return tfbs::fail(TFBS_E_ARG, "output capacity too small");
+    auto tile = [](const tfbs::DevTile &t) {
+        return tfbs_lut_tile{t.first, t.last, t.lut_begin, t.nblocks, t.slot_begin, t.nslots, t.lmin};
+    };
+    if (buf->tiles)
+        for (size_t k = 0; k < plan.fast_tiles.size(); k++) buf->tiles[k] = tile(plan.fast_tiles[k]);
+    if (buf->gen_tiles)
+        for (size_t k = 0; k < plan.gen_tiles.size(); k++) buf->gen_tiles[k] = tile(plan.gen_tiles[k]);
+    if (buf->units)
+        for (size_t k = 0; k < plan.fast_units.size(); k++) {
+            const tfbs::DevUnit &U = plan.fast_units[k];
+            tfbs_lut_unit &o = buf->units[k];
+            o.lut_off = U.lut_off;
+            o.nblk = U.nblk;
+            o.nstrand = U.nstrand;
+            o.kind = U.kind;
+            std::copy(U.init, U.init + 4, o.init);
+            std::copy(U.thr, U.thr + 8, o.thr);
+            std::copy(U.min_score, U.min_score + 8, o.min_score);
+            std::copy(U.len, U.len + 8, o.len);
+            std::copy(U.slot_local, U.slot_local + 8, o.slot_local);
+            std::copy(U.orig_index, U.orig_index + 8, o.orig_index);
+        }
+    if (buf->gen_pats)
+        for (size_t k = 0; k < plan.gen_pats.size(); k++) {
+            const tfbs::DevPattern &d = plan.gen_pats[k];
+            buf->gen_pats[k] = tfbs_lut_gen_pat{d.col_off, d.min_score, d.len, d.slot_local, d.orig_index};
+        }
+    if (buf->lut) std::copy(plan.lut.begin(), plan.lut.end(), buf->lut);
+    if (buf->gen_w) std::copy(plan.gen_w.begin(), plan.gen_w.end(), buf->gen_w);
+    if (buf->slot_pid) std::copy(plan.slot_pid.begin(), plan.slot_pid.begin() + n_slots, buf->slot_pid);
+    if (buf->slot_mfma) std::copy(plan.slot_mfma.begin(), plan.slot_mfma.begin() + n_slots, buf->slot_mfma);
+    return TFBS_OK;
+}
+
 }  // extern "C"
 
 namespace tfbs {

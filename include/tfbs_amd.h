@@ -175,6 +175,56 @@ typedef struct tfbs_mfma_super {
 int tfbs_patterns_mfma_plan(const tfbs_patterns *p, uint32_t lds_kb, uint8_t *image, size_t image_cap,
                             size_t *image_bytes, tfbs_mfma_super *supers, size_t supers_cap, size_t *n_supers,
                             int32_t *meta, size_t meta_cap, size_t *meta_ints);
+/* Host-only, read-only diagnostic of the LUT and generic plan: copies of the arrays a
+ * device context uploads for scan_fast_kernel and scan_generic_kernel and nothing derived
+ * from them.  The plan is built once per call as tfbs_ctx_create builds it with
+ * TFBS_TILE_BLOCKS=tile_blocks (not clamped here) and TFBS_MFMA=mfma.  tiles / units: the
+ * fast tiles and their units (plan.cpp; a unit's tables are blocks lut_off .. lut_off +
+ * nblk - 1 of its tile, a tile's blocks lut_begin .. lut_begin + nblocks - 1 of lut);
+ * lut: the table blocks, 1024 ints each (256 codes x 16 bytes: eight int16 halves of an
+ * OCTET16 unit, four int32 of a QUAD32 unit); gen_tiles / gen_pats / gen_w: the generic
+ * kernel's tiles (first / last index gen_pats), its strands and their weights (five per
+ * column from col_off, N last); slot_pid / slot_mfma: per count slot its pattern_id and
+ * whether the matrix cores score it.  *sizes always receives the entry counts; buf may
+ * be NULL (sizes only), each of its arrays may be NULL, and an array whose capacity (in
+ * entries) is too small is TFBS_E_ARG, as is a NULL p or sizes. */
+typedef struct tfbs_lut_tile {
+    uint32_t first, last, lut_begin, nblocks, slot_begin, nslots, lmin;
+} tfbs_lut_tile;
+typedef struct tfbs_lut_unit {
+    uint32_t lut_off, nblk, nstrand, kind; /* kind 0: OCTET16, 1: QUAD32 */
+    uint32_t init[4];
+    int32_t thr[8], min_score[8];
+    uint32_t len[8], slot_local[8], orig_index[8];
+} tfbs_lut_unit;
+typedef struct tfbs_lut_gen_pat {
+    uint32_t col_off;
+    int32_t min_score;
+    uint32_t len, slot_local, orig_index;
+} tfbs_lut_gen_pat;
+typedef struct tfbs_lut_plan_sizes {
+    size_t n_tiles, n_units, lut_ints, n_gen_tiles, n_gen_pats, gen_w_ints, n_slots;
+} tfbs_lut_plan_sizes;
+typedef struct tfbs_lut_plan_buffers {
+    tfbs_lut_tile *tiles;
+    size_t tiles_cap;
+    tfbs_lut_unit *units;
+    size_t units_cap;
+    int32_t *lut;
+    size_t lut_cap;
+    tfbs_lut_tile *gen_tiles;
+    size_t gen_tiles_cap;
+    tfbs_lut_gen_pat *gen_pats;
+    size_t gen_pats_cap;
+    int32_t *gen_w;
+    size_t gen_w_cap;
+    uint16_t *slot_pid;
+    size_t slot_pid_cap;
+    uint8_t *slot_mfma;
+    size_t slot_mfma_cap;
+} tfbs_lut_plan_buffers;
+int tfbs_patterns_lut_plan(const tfbs_patterns *p, uint32_t tile_blocks, int mfma, const tfbs_lut_plan_buffers *buf,
+                           tfbs_lut_plan_sizes *sizes);
 
 /* ------------------------------------------------------------------ */
 /* Thresholds from a p-value: exact score distributions                  */
